@@ -10,6 +10,13 @@ the data path; RCCL only for the barrier / MAX-reduce and the final state gather
 
 Inputs (synthetic frames rendered on the device, templates, states) are resident
 in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`,
+`ms_per_step`, ...).  Everything else it can measure or check - per-kernel
+breakdown and rooflines (HIP event brackets), the CPU baseline and the parity
+legs against the oracle, the host-fed leg - runs only with --full.
+--dump-outputs DIR writes the state the timed path left after its last step as
+DIR/<name>.npy (float64; the inputs are the same from run to run).
 """
 import argparse
 import json
@@ -37,9 +44,10 @@ def parse_args():
     ap.add_argument("--features", type=int, default=None, help="known features per sequence (default: 100; 12 with --mapping)")
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--height", type=int, default=240)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="sequences of the CPU-baseline sample (-1: one per hardware thread of the host; 0: skip)")
-    ap.add_argument("--cpu-frames", type=int, default=25, help="frames of the CPU-baseline / parity sample")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--cpu-sample", type=int, default=-1,
+                    help="--full: sequences of the CPU-baseline sample (-1: one per hardware thread of the host; 0: skip)")
+    ap.add_argument("--cpu-frames", type=int, default=25, help="--full: frames of the CPU-baseline / parity sample")
+    ap.add_argument("--no-profile", action="store_true", help="--full: do not bracket kernels with HIP events")
     ap.add_argument("--feature-sigma", type=float, default=0.005,
                     help="prior std-dev (m) of every map feature; > 0 makes the covariance dense (0: AddNewKnownFeature zeros)")
     ap.add_argument("--graph", action="store_true", help="replay the step as a HIP graph (small batches are launch-bound)")
@@ -49,13 +57,20 @@ def parse_args():
     ap.add_argument("--step-fusion", type=int, default=-1,
                     help="sl2_set_step_fusion: 0 = one stage per launch, 1 = the engine's rule (default), 2 = fused small-map step whatever the batch size")
     ap.add_argument("--no-host-fed", action="store_true",
-                    help="skip the host-fed leg (frames starting in pinned host memory, copied under the previous step): an extra "
+                    help="--full: skip the host-fed leg (frames starting in pinned host memory, copied under the previous step): an extra "
                          "block of the line, measured after the timed region on an engine of its own; never `value`")
     ap.add_argument("--mapping", action="store_true",
                     help="the reference's DEFAULT workload instead of the headline: --features known features (use 6-12), the shipped "
                          "parameters (select 10, keep 12 visible, 100 depth particles), a camera that translates past the 0.2 m/s "
                          "gate, GoOneStep(enable_mapping = true): features are initialised, converted and deleted along the way")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel breakdown and rooflines, CPU baseline, "
+                         "parity against the oracle, host-fed leg (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (rank 0's sequences) as DIR/<name>.npy, float64")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.features is None:
         a.features = 12 if a.mapping else 100
     if a.mapping and a.feature_sigma == 0.005:
@@ -125,7 +140,145 @@ def workload_name(B, W, H, N, world):
     return "custom: " + shape
 
 
-def per_rank_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render, tdev, world, nseq=2, nframes=8):
+SPEC_SEQFRAMES_PER_WORKER = 20000     # about 2 s of host work: below that a worker process costs more than it saves
+
+
+def _specs_of(job):
+    from scenelib2_amd import synth
+    cam, N, n_render, ids, kw = job
+    return [synth.SequenceSpec(cam, N, n_render, synth.BASE_SEED + i, **kw) for i in ids]
+
+
+def _specs_worker():
+    """Entry point of a make_specs worker process: a pickled job on stdin, the pickled specs on stdout."""
+    import pickle
+    job = pickle.load(sys.stdin.buffer)
+    pickle.dump(_specs_of(job), sys.stdout.buffer, protocol=pickle.HIGHEST_PROTOCOL)
+    sys.stdout.buffer.flush()
+
+
+def make_specs(cam, N, n_render, seq_ids, spec_kw, world=1):
+    """synth.SequenceSpec of every sequence of the rank.  A spec integrates its camera path frame by frame on the host (about
+    0.1 ms per sequence-frame), so large runs share the sequences out over worker processes.  A worker is a fresh interpreter
+    that imports this file as a module and runs _specs_worker: it neither runs the caller's __main__ nor imports torch, and
+    never opens the GPU.  The specs are the same either way."""
+    ids = [int(i) for i in seq_ids]
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except AttributeError:
+        ncpu = os.cpu_count() or 1
+    workers = max(1, min(16 // max(1, world), ncpu, len(ids) * (n_render + 1) // SPEC_SEQFRAMES_PER_WORKER))
+    if workers == 1:
+        return _specs_of((cam, N, n_render, ids, spec_kw))
+    import pickle
+    import subprocess
+    entry = "import sys; sys.path.insert(0, %r); import bench; bench._specs_worker()" % ROOT
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", entry]
+    chunks = [c.tolist() for c in np.array_split(np.array(ids, dtype=np.int64), workers) if c.size]
+    procs = []
+    try:
+        for c in chunks:                 # every worker gets its job first (a few kB: fits the pipe), then all compute at once
+            p = subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.PIPE)
+            procs.append(p)
+            p.stdin.write(pickle.dumps((cam, N, n_render, c, spec_kw), protocol=pickle.HIGHEST_PROTOCOL))
+            p.stdin.close()
+        parts = []
+        for p in procs:
+            out = p.stdout.read()
+            if p.wait() != 0:
+                raise RuntimeError("bench.py: a camera-path worker exited with status %d" % p.returncode)
+            parts.append(pickle.loads(out))
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    return [s for p in parts for s in p]
+
+
+DUMP_SEED = 20240925          # the seeded sample of sequences whose whole state and covariance --dump-outputs writes
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step, float64, at most 64 MB in all:
+    vehicle_state [B][13] and vehicle_covariance [B][13][13] of every sequence (a seeded sample of 4096 beyond that),
+    and for a seeded sample of sequences (at most 16, fewer when the covariance is large) total_state [S][n],
+    total_covariance [S][r][n] (zero-padded to the largest n; state_size says where each ends; r = n, or a seeded sample
+    of rows, covariance_rows, when even one covariance is too large) and feature_measurements [S][max_features][8] =
+    label (-1: empty slot), visible, selected, successful, z (2), h (2)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    B = eng.batch
+    vseq = np.arange(B) if B <= 4096 else np.sort(rng.choice(B, 4096, replace=False))
+    xv, Pxx = eng.get_vehicle_state()
+    sizes = eng.total_state_sizes()
+    S = int(max(1, min(B, 16, (DUMP_BYTES // 2) // (8 * int(sizes.max()) ** 2))))
+    sseq = np.sort(rng.choice(B, S, replace=False))
+    n = int(sizes[sseq].max())
+    rows = np.arange(n)
+    if S * 8 * n * n > DUMP_BYTES // 2:
+        rows = np.sort(rng.choice(n, (DUMP_BYTES // 2) // (8 * n), replace=False))
+    x = np.zeros((S, n))
+    P = np.zeros((S, rows.size, n))
+    meas = np.zeros((S, eng.max_features, 8))
+    meas[:, :, 0] = -1.0
+    for j, b in enumerate(sseq):
+        k = int(sizes[b])
+        x[j, :k] = eng.total_state(int(b))
+        Pb = np.zeros((n, n))
+        Pb[:k, :k] = eng.total_covariance(int(b))
+        P[j] = Pb[rows]
+        for i, f in enumerate(eng.features(int(b))):
+            meas[j, i] = [f["label"], f["visible"], f["selected"], f["success"], f["z"][0], f["z"][1], f["h"][0], f["h"][1]]
+    arrays = dict(vehicle_sequences=vseq, vehicle_state=xv[vseq], vehicle_covariance=Pxx[vseq], state_sequences=sseq,
+                  state_size=sizes[sseq], total_state=x, total_covariance=P, covariance_rows=rows, feature_measurements=meas)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BYTES, total
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return total
+
+
+POS_LOG = 1000      # sl2_get_position_log holds xv[0:3] after the last 1000 steps of every sequence (kTrajCapacity)
+
+
+def held_positions(eng, nseq, head, stepped, frames):
+    """[nseq][frames][3]: the engine's position after frame k (1-based) in column k - 1, NaN where the engine no longer holds
+    it.  The log keeps the last POS_LOG steps only, so a run of more frames than that reads it twice: `head` = (the log read
+    at the end of the warm-up, frames stepped by then) holds the first frames, the log now (`stepped` frames) the last."""
+    out = np.full((nseq, frames, 3), np.nan)
+
+    def put(log, last):                  # log[:, i] = position after frame last - count + 1 + i
+        lo = last - log.shape[1]
+        a, b = max(lo, 0), min(last, frames)
+        if b > a:
+            out[:, a:b] = log[:nseq, a - lo:b - lo]
+    if head is not None:
+        put(head[0], head[1])
+    put(eng.position_log(0, nseq, capacity=POS_LOG), stepped)
+    return out
+
+
+def compare_positions(pos, traj):
+    """Engine positions (held_positions) against the oracle's trajectory [nseq][frames][3] over the frames the engine still
+    holds: (RMSE, max-abs, frames compared); (None, None, 0) when it holds none of them."""
+    p = pos[:, :traj.shape[1]]
+    held = np.isfinite(p).all(axis=(0, 2))
+    if not held.any():
+        return None, None, 0
+    d = p[:, held] - traj[:, held]
+    return float(np.sqrt((d ** 2).sum(axis=2).mean())), float(np.abs(d).max()), int(held.sum())
+
+
+def worst(*vals):
+    vals = [v for v in vals if v is not None]
+    return max(vals) if vals else None
+
+
+def per_rank_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render, tdev, world, head, nseq=2,
+                    nframes=8):
     """A rank's leg of the parity check in a multi-GPU run: the first `nseq` sequences of this rank's shard, the first
     `nframes` frames, against the oracle (oracle/liboracle.so), on the same bytes the GPU consumed.  All ranks call this (it ends in two collectives); returns the job-wide summary."""
     from scenelib2_amd import sharding
@@ -147,18 +300,19 @@ def per_rank_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W,
                 s.set_feature_Pyy(i, np.eye(3) * args.feature_sigma ** 2)
         slams.append(s)
     _, traj = oa.run_sequences(slams, [np.ascontiguousarray(allf[1:, b]) for b in range(nseq)], nthreads=nseq)
-    log = eng.position_log(0, nseq, capacity=n_render)[:, :nframes]
-    sq = float(((log - traj) ** 2).sum(axis=2).mean())
-    worst_rmse = sharding.max_over_ranks(float(np.sqrt(sq)), tdev)
-    worst_abs = sharding.max_over_ranks(float(np.abs(log - traj).max()), tdev)
+    rmse, maxabs, compared = compare_positions(held_positions(eng, nseq, head, n_render, nframes), traj)
+    # every rank steps the same number of frames, so either all compared some or none did (-1: none)
+    worst_rmse = sharding.max_over_ranks(-1.0 if rmse is None else rmse, tdev)
+    worst_abs = sharding.max_over_ranks(-1.0 if maxabs is None else maxabs, tdev)
     checked = sharding.sum_over_ranks(1, tdev)
-    return dict(traj_rmse_vs_oracle=worst_rmse, position_maxabs=worst_abs, ranks_checked=int(checked), n_gpus=world,
+    return dict(traj_rmse_vs_oracle=worst_rmse if worst_rmse >= 0 else None, position_maxabs=worst_abs if worst_abs >= 0 else None,
+                ranks_checked=int(checked), n_gpus=world,
                 checker="oracle (CPU restatement; parity unpinned: DESIGN.md section 2)",
-                sequences=nseq, frames=nframes,
+                sequences=nseq, frames=nframes, positions_compared=compared,
                 note="every rank: the first %d sequences of its own shard x %d frames; worst over ranks" % (nseq, nframes))
 
 
-def mapping_cpu_and_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render, sample):
+def mapping_cpu_and_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render, sample, head):
     """--mapping: CPU baseline and parity of the mapping-on workload against the oracle (kind "port"), one worker process
     per usable physical core of the host (oracle/cpu_baseline.py), each stepping its sequences one after the other.
     cpu_baseline = sequence-frames / the slowest worker's time inside GoOneStep; parity = every frame the engine stepped,
@@ -176,10 +330,9 @@ def mapping_cpu_and_parity(eng, specs, templates, d_frames, cam, params, args, B
     cpu["note"] = ("the oracle restatement (oracle/*.hpp, g++ -O3, naive fixed-order products) - a port, not the reference: the "
                    "reference needs Eigen / OpenCV / Pangolin and is unbuildable in this image")
     checker = "oracle (CPU restatement; parity unpinned: DESIGN.md section 2)"
-    log = eng.position_log(0, nseq, capacity=n_render)[:, :frames_n]
-    rmse = float(np.sqrt(((log - traj) ** 2).sum(axis=2).mean()))
+    rmse, maxabs, compared = compare_positions(held_positions(eng, nseq, head, n_render, frames_n), traj)
     parity = dict(traj_rmse_vs_oracle=rmse, checker=checker, sequences=nseq, frames=frames_n, frames_stepped=n_render,
-                  covers_every_timed_frame=True, position_maxabs=float(np.abs(log - traj).max()))
+                  covers_every_timed_frame=compared == frames_n, position_maxabs=maxabs, positions_compared=compared)
     # the maps grew the same way: state size (feature counts and kinds) and the whole state at the end
     dx, same_maps = 0.0, True
     for b in range(nseq):
@@ -245,7 +398,8 @@ def main():
 
     B, N, W, H = args.batch, args.features, args.width, args.height
     K, Wm = args.steps, args.warmup
-    E = 0 if args.no_profile else 4          # extra untimed steps for the full per-kernel breakdown
+    profile = args.full and not args.no_profile
+    E = 4 if profile else 0                  # extra untimed steps for the full per-kernel breakdown
     n_frames = K + Wm
     n_render = n_frames + E
     cam = synth.default_camera(W, H)
@@ -259,7 +413,7 @@ def main():
     # ---- synthetic inputs: specs on the host, frames rendered on the device ----
     t_setup = time.time()
     tex = synth.make_texture()
-    specs = [synth.SequenceSpec(cam, N, n_render, synth.BASE_SEED + int(i), **spec_kw) for i in seq_ids]
+    specs = make_specs(cam, N, n_render, seq_ids, spec_kw, world)
     fb = W * H
     d_tex = _lib.DeviceBuffer(tex.nbytes, dev); d_tex.upload(tex)
     # pose k of every sequence, k-major: frames[k][b]
@@ -299,7 +453,7 @@ def main():
     def step(k):  # frame k (0-based) = pose k+1, resident in HBM
         eng.go_one_step(d_frames.ptr + (k + 1) * B * fb, on_device=True, seq_stride=fb, enable_mapping=args.mapping)
 
-    # ---- warm-up ----  (its last steps, when there are enough, carry a bracket on EVERY launch: they tell which kernel
+    # ---- warm-up ----  (with --full its last steps, when there are enough, carry a bracket on EVERY launch: they tell which kernel
     # dominates, so that the timed region brackets only that one and the search kernel - each bracket is two event markers
     # on the stream, and bracketing the four large kernels cost 1-3 % of the step)
     # profiling scopes carry the kernel symbols (they join with rocprofv3's kernel_stats.csv on the name)
@@ -308,7 +462,7 @@ def main():
         MAJOR = MAJOR + ("k_map_find", "k_map_me_search", "k_me_big", "k_map_particles", "k_map_update", "k_map_finish")
     SEARCH = "k_search_mfma"
     focus = "k_syrk," + SEARCH
-    n_probe = 3 if (not args.no_profile and Wm >= 6) else 0
+    n_probe = 3 if (profile and Wm >= 6) else 0
     for k in range(Wm - n_probe):
         step(k)
     if n_probe:
@@ -324,7 +478,10 @@ def main():
         if cand:
             focus = max(cand, key=cand.get) + "," + SEARCH
     eng.synchronize()
-    if not args.no_profile:
+    # --full: the engine's positions after the warm-up frames - its log keeps the last POS_LOG steps, and the oracle legs
+    # compare the first frames of the run
+    head = (eng.position_log(0, None, capacity=POS_LOG), Wm) if (args.full and Wm > 0) else None
+    if profile:
         eng.set_profile_focus(focus)
         eng.set_profiling(1)          # timed region: only the roofline kernels carry event brackets
         eng.reset_kernel_times()
@@ -342,11 +499,13 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = sharding.max_over_ranks(elapsed, tdev if use_dist else None)
 
-    ktimes = eng.kernel_times() if not args.no_profile else {}
+    ktimes = eng.kernel_times() if profile else {}
     eng.set_profiling(0)
     eng.set_profile_focus("")
     work = eng.step_work()       # algorithmic work of the last timed step, summed over this rank's batch
     xv_final, _ = eng.get_vehicle_state()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     # untimed extra steps with EVERY launch bracketed: the full per-kernel breakdown
     breakdown = {}
     if E > 0:
@@ -369,9 +528,9 @@ def main():
     # ---- N > 1: every rank checks a small sample of ITS OWN sequences against the reference build (values, not shapes);
     # rank 0 reports the worst deviation and how many ranks took part
     rank_parity = None
-    if world > 1 and args.cpu_sample != 0 and not args.mapping:
+    if args.full and world > 1 and args.cpu_sample != 0 and not args.mapping:
         rank_parity = per_rank_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render,
-                                      tdev if use_dist else None, world)
+                                      tdev if use_dist else None, world, head)
 
     out = None
     if rank == 0:
@@ -431,9 +590,9 @@ def main():
 
         # HBM traffic (and the search kernel's instruction count) from the committed PMC passes of this same command
         # (profiles/pmc_traffic.json; rocprofv3 cannot be nested inside this process), corrected as MI355X_MICROARCH.md
-        # prescribes; only when the file was measured on this shape
+        # prescribes; only when the file was measured on this shape, and only for the rooflines of a --full run
         try:
-            pmc_file = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+            pmc_file = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))) if (roof or roof_search) else {"kernels": {}}
             pmc = pmc_file["kernels"]
             pmc_meta = pmc_file.get("meta", {})
             if pmc_meta.get("shape") == [B, W, H, N]:
@@ -462,19 +621,22 @@ def main():
         except Exception:
             pass
 
-        # ---- CPU baseline on the host cores THIS JOB may use, in the same run (rank 0, N = 1 only): a bounded sample of the
+        # ---- CPU baseline (--full) on the host cores THIS JOB may use, in the same run (rank 0, N = 1 only): a bounded sample of the
         # same workload through the oracle (kind "port": the reference itself needs Eigen / OpenCV / Pangolin and is
         # unbuildable in this image), one worker process per usable physical core (oracle/cpu_baseline.py reads the
         # affinity mask and the cgroup quota).  Reported baseline, not the target.
         cpu = None
         parity = None
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import cpu_baseline as cb
-        topo = cb.host_topology()
-        ncores = topo["cores_usable"]
-        sample = args.cpu_sample if args.cpu_sample >= 0 else min(ncores, B)
+        sample = 0
+        if args.full:
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import cpu_baseline as cb
+            topo = cb.host_topology()
+            ncores = topo["cores_usable"]
+            sample = args.cpu_sample if args.cpu_sample >= 0 else min(ncores, B)
         if world == 1 and sample > 0 and args.mapping:
-            cpu, parity = mapping_cpu_and_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render, sample)
+            cpu, parity = mapping_cpu_and_parity(eng, specs, templates, d_frames, cam, params, args, B, N, W, H, fb, n_render, sample,
+                                                 head)
         elif world == 1 and sample > 0:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_api as oa
@@ -535,10 +697,9 @@ def main():
             tt = sum(d["times"].values())
             cpu["stage_split"] = {k: float(v / tt) for k, v in d["times"].items()}
             # parity of the trajectories on the sample (BASELINE metric: traj RMSE vs ref <= 1e-4)
-            log = eng.position_log(0, sample, capacity=n_render)[:, :cpu_frames]
-            rmse = float(np.sqrt(((log - traj) ** 2).sum(axis=2).mean()))
+            rmse, maxabs, compared = compare_positions(held_positions(eng, sample, head, n_render, cpu_frames), traj)
             parity = dict(traj_rmse_vs_oracle=rmse, checker="oracle (CPU restatement; parity unpinned: DESIGN.md section 2)",
-                          sequences=sample, frames=cpu_frames, position_maxabs=float(np.abs(log - traj).max()))
+                          sequences=sample, frames=cpu_frames, position_maxabs=maxabs)
             # ... and over EVERY frame the engine stepped (warm-up, timed region and the bracketed extra steps) on a few
             # sequences: positions after every frame plus the whole state vector / covariance after the last one.  Bounded to
             # about a minute of host time (a sequence-frame of the reference costs ~7 ms x (n / 313)^3).
@@ -549,15 +710,14 @@ def main():
             slams2 = [build(b) for b in range(full_seq)]
             _, traj2 = oa.run_sequences(slams2, [np.ascontiguousarray(allf2[1:, b]) for b in range(full_seq)],
                                         nthreads=min(ncores, full_seq))
-            log2 = eng.position_log(0, full_seq, capacity=n_render)[:, :full_frames]
-            rmse2 = float(np.sqrt(((log2 - traj2) ** 2).sum(axis=2).mean()))
+            rmse2, maxabs2, compared2 = compare_positions(held_positions(eng, full_seq, head, n_render, full_frames), traj2)
             # top level: the worst of the two legs; `sequences` x `frames` = the full-length leg (every frame stepped)
-            parity.update(traj_rmse_vs_oracle=max(rmse, rmse2), sequences=full_seq, frames=full_frames, frames_stepped=n_render,
-                          position_maxabs=max(parity["position_maxabs"], float(np.abs(log2 - traj2).max())),
-                          covers_every_timed_frame=bool(full_frames >= Wm + K))
-            parity["full_length"] = dict(sequences=full_seq, frames=full_frames, traj_rmse=rmse2,
-                                         position_maxabs=float(np.abs(log2 - traj2).max()))
-            parity["wide_sample"] = dict(sequences=sample, frames=cpu_frames, traj_rmse=rmse)
+            parity.update(traj_rmse_vs_oracle=worst(rmse, rmse2), sequences=full_seq, frames=full_frames, frames_stepped=n_render,
+                          position_maxabs=worst(maxabs, maxabs2), positions_compared=compared2,
+                          covers_every_timed_frame=bool(full_frames >= Wm + K and compared2 == full_frames))
+            parity["full_length"] = dict(sequences=full_seq, frames=full_frames, traj_rmse=rmse2, position_maxabs=maxabs2,
+                                         positions_compared=compared2)
+            parity["wide_sample"] = dict(sequences=sample, frames=cpu_frames, traj_rmse=rmse, positions_compared=compared)
             if full_frames == n_render:
                 # the engine stands at frame n_render: whole state and covariance against the reference's
                 dx, dP = 0.0, 0.0
@@ -576,7 +736,7 @@ def main():
         # k + 1 under the step on frame k - what a grabber-fed caller gets.  Outside the timed region, on an engine of its own;
         # the headline stays device-resident.
         host_fed = None
-        if world == 1 and not args.mapping and not args.no_host_fed:
+        if args.full and world == 1 and not args.mapping and not args.no_host_fed:
             try:
                 sys.path.insert(0, os.path.join(ROOT, "scripts"))
                 import pcie_inclusive
@@ -595,7 +755,7 @@ def main():
                       "batched MonoSLAM frames/sec (%dx%d, mapping on, %d known features: the reference's default workload)" % (W, H, N),
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wm,
             "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": (workload_name(B, W, H, N, world) + ", all features selected, map prior sigma %.3g m (%s covariance)"
                                     % (args.feature_sigma, "dense" if args.feature_sigma > 0 else "block-sparse")) if not args.mapping else
                                    ("the reference's default workload (data/SceneLib2.cfg: select 10, keep 12 visible, 100 depth particles, "

@@ -10,7 +10,7 @@ for rep in 1 2; do
 for sw in "$@"; do
   i=$((i+1))
   [ "$sw" = "-" ] && sw=""
-  env $sw timeout 600 python bench.py $FLAGS --cpu-sample 0 2>$OUT/ab_$i.err | tail -1 > $OUT/ab_$i.json
+  env $sw timeout 600 python bench.py $FLAGS --full --cpu-sample 0 2>$OUT/ab_$i.err | tail -1 > $OUT/ab_$i.json
   python - <<PY
 import json
 d=json.load(open("$OUT/ab_$i.json"))

@@ -1,9 +1,11 @@
-"""bench.py prints ONE JSON line with the fields the driver and the judge read; a small run must keep that contract."""
+"""bench.py prints ONE JSON line with the fields the driver and the judge read; a small run must keep that contract.
+Rooflines, the CPU baseline and the parity legs are measured by a --full run only."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "16",
-                          "--cpu-sample", "2", "--cpu-frames", "3"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-sample", "2", "--cpu-frames", "3", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, "exactly one line on stdout"
@@ -52,7 +54,7 @@ def test_bench_mapping_line_is_checked_against_the_oracle():
     oracle, one worker process per usable physical core (oracle/cpu_baseline.py), and the CPU baseline is that same code
     (kind "port")."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mapping", "--steps", "8", "--warmup", "8", "--batch", "16",
-                          "--cpu-sample", "8"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--cpu-sample", "8", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][0])
     p, c = d["parity"], d["cpu_baseline"]
@@ -67,8 +69,8 @@ def test_bench_self_spawns_ranks():
     through the gloo test hook (the code path - rendezvous, barrier, MAX-reduce, gather - is the one RCCL runs on N GPUs)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SL2_BENCH_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "16"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "16",
+                          "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -106,7 +108,7 @@ def test_bench_under_torch_distributed_run():
     env["SL2_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", "29741", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                          "--warmup", "2", "--batch", "16"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--warmup", "2", "--batch", "16", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-1500:]
@@ -114,3 +116,40 @@ def test_bench_under_torch_distributed_run():
     assert d["n_gpus"] == 2 and d["gathered_states"] == 32 and d["steps"] == 3 and d["warmup"] == 2
     assert d["parity"]["ranks_checked"] == 2 and d["parity"]["traj_rmse_vs_oracle"] <= 1e-12
     assert abs(d["value"] - 2 * 16 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+
+
+def _bench_line(args, env=None):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=600,
+                         cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, "exactly one line on stdout"
+    return json.loads(lines[0])
+
+
+def test_plain_bench_is_the_headline_alone_and_dumps_what_it_computed(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes the state of the last
+    timed step as float64 .npy files (at most 64 MB), the same bytes as a --full run of the same arguments computes."""
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "3", "--batch", "16"]
+    d = _bench_line(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert d["steps"] == 4 and d["warmup"] == 3 and d["full"] is False and d["unit"] == "frames/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert d["roofline"] is None and d["roofline_search"] is None and d["cpu_baseline"] is None and d["parity"] is None
+    assert d["host_fed"] is None and d["kernels"] == {}
+    f = _bench_line(args + ["--full", "--cpu-sample", "0", "--no-host-fed", "--dump-outputs", str(tmp_path / "full")])
+    assert f["full"] is True and f["roofline"] is not None
+    plain = {p.name: np.load(p) for p in sorted((tmp_path / "plain").iterdir())}
+    full = {p.name: np.load(p) for p in sorted((tmp_path / "full").iterdir())}
+    assert set(plain) == set(full) and "total_covariance.npy" in plain and "vehicle_state.npy" in plain
+    assert sum(a.nbytes for a in plain.values()) <= 64 << 20
+    for name, a in plain.items():
+        assert a.dtype == np.float64, name
+        assert np.array_equal(a, full[name]), name
+    assert plain["vehicle_state.npy"].shape == (16, 13) and np.isfinite(plain["vehicle_state.npy"]).all()
+    seqs = plain["state_sequences.npy"].astype(int)
+    assert np.array_equal(plain["total_state.npy"][:, :13], plain["vehicle_state.npy"][seqs])
+    assert plain["total_covariance.npy"].shape == (seqs.size, 313, 313)
+    # the search found the features it was asked for: measurements of the last step
+    m = plain["feature_measurements.npy"]
+    assert m.shape == (seqs.size, 100, 8) and (m[:, :, 3] == 1).sum() > 0
