@@ -156,8 +156,10 @@ int sl2_set_feature_covariances(sl2_engine* e, int seq0, int nseq, int nfeat, co
  * 0.2 m/s speed gate, MatchPartiallyInitialisedFeatures) with up to params.max_features_to_init_at_once <= 4 partially
  * initialised features in flight per sequence (the shipped value is 1; the six state columns of each are reserved at
  * sl2_create) and up to 1024 depth particles (params.number_of_particles; the shipped value is 100); other settings are
- * rejected with SL2_ERR_INVALID.  With more than one feature in flight the reference's own arithmetic is kept, including the
- * position it records for later features after a conversion (feature.cpp:254).  SL2_STATUS_LABELS_EXHAUSTED = a sequence could
+ * rejected with SL2_ERR_INVALID.  The reference's own arithmetic is kept for the position it records for later features
+ * after a conversion (feature.cpp:254, Q28): it is misplaced whenever a feature converts in front of one that joined the map
+ * after it - a second partially initialised feature, or a known feature added while one was in flight - and that feature's
+ * dh_by_dy block then lands where the reference puts it.  SL2_STATUS_LABELS_EXHAUSTED = a sequence could
  * not take a new feature because all max_features slots hold live features. */
 int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int frames_on_device,
                     int save_trajectory, int enable_mapping);
@@ -439,11 +441,16 @@ int sl2_delete_features(sl2_engine* e, int seq0, int nseq, const int32_t* labels
  * raise when the bit RISES). */
 #define SL2_STATUS_NONFINITE 1
 #define SL2_STATUS_LABELS_EXHAUSTED 2
-/* SL2_STATUS_REFERENCE_OUT_OF_BOUNDS (sticky; only with max_features_to_init_at_once > 1): the position the reference records
- * for a feature after several conversions and deletions (feature.cpp:254, Q28) has gone NEGATIVE; the reference then writes
- * its dh_by_dy block outside dh_by_dx_tot (monoslam.cpp:564, undefined behaviour).  The engine holds the block at column 0
- * and flags the sequence: from here on its filter is not the reference's. */
+/* SL2_STATUS_REFERENCE_OUT_OF_BOUNDS (sticky): the position the reference records for a feature after several conversions in
+ * front of it and deletions (feature.cpp:254, Q28; see sl2_go_one_step for how a position becomes misplaced) has gone
+ * NEGATIVE; the reference then writes its dh_by_dy block outside dh_by_dx_tot (monoslam.cpp:564, undefined behaviour).  The
+ * engine holds the block at column 0 and flags the sequence: from here on its filter is not the reference's. */
 #define SL2_STATUS_REFERENCE_OUT_OF_BOUNDS 4
+/* SL2_STATUS_SMALL_STEP_REFUSED (sticky): the fused small-map update was launched for a sequence it cannot take (a live map
+ * wider than its LDS panel, or a dh_by_dy block outside the live state) and skipped that sequence's Kalman update instead of
+ * reaching outside its memory.  Never expected: the engine chooses the fused step only for maps it fits, so the bit means an
+ * engine bug, and the sequence's filter is no longer the reference's. */
+#define SL2_STATUS_SMALL_STEP_REFUSED 8
 int sl2_get_status_flags(sl2_engine* e, int seq0, int nseq, int32_t* flags);
 
 /* ------------------------------------------------------------------- profiling */

@@ -312,6 +312,7 @@ int launch_search_kernel(sl2_engine* e);     // the search kernel alone (the fus
 int launch_search_score(sl2_engine* e);
 int small_step_mode(const sl2_engine* e, int slots_bound);       // sl2_small.hip: 0 = ten launches, 1 = three (both sides of the search fused), 2 = the back side only
 int launch_small_front(sl2_engine* e, int n);                 // predict + feature prediction + selection in one launch
+int small_panel_w(const sl2_engine* e, int slots_bound);         // sl2_small.hip: columns of k_small_back's LDS panel (64 or 128)
 int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound);   // scoring + EKF update + normalise / delete / symmetrise in one launch
 int launch_update(sl2_engine* e);
 int launch_syrk_on(sl2_engine* e, const double* Vt, double* P);

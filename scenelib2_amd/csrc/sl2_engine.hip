@@ -962,7 +962,7 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
   const bool tail = e->mapping_used;
   const int slots_bound = slots_upper_bound(e);
   const int parts_state = tail ? parts_state_for_step(e) : 0;
-  const int small_any = [&]() { int m = ((slots_bound + 1 > e->N) ? 1 : 0) + 2 * parts_state; for (const sl2_engine* g : e->groups) m = (m * 5 + small_step_mode(g, slots_bound)) % 1000003; return m; }();   // (which launches the step consists of: part of a captured step's key)
+  const int small_any = [&]() { int m = ((slots_bound + 1 > e->N) ? 1 : 0) + 2 * parts_state; for (const sl2_engine* g : e->groups) { const int md = small_step_mode(g, slots_bound); m = (m * 7 + (md == 0 ? 0 : md + (small_panel_w(g, slots_bound) == 64 ? 3 : 0))) % 1000003; } return m; }();   // (which launches the step consists of, and the LDS panel k_small_back is launched with: part of a captured step's key)
   auto issue = [=]() -> int {
     int r = for_each_group(e, [=](sl2_engine* g) {
       int q;

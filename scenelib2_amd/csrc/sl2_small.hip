@@ -61,9 +61,13 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
 // what the update touches is the LIVE part of the state: columns [0, 13 + 3 n_slots), the six states of a partially
 // initialised feature at ppos (if one is in flight), and the innovation.  Those are gathered into a compact column index
 // c < W (W = 64 or 128, cmap below) for everything that lives in LDS; P and x are addressed in place, at stride ld.
-// sAt: [32][W] doubles of dynamic LDS.  H row a = 2 j + r of the j-th successful feature in SLOT order (succ_idx): the seven
-// pose coefficients of dh_by_dxv and the three of dh_by_dy at column 13 + 3 slot (monoslam.cpp:548-572; with one partially
-// initialised feature per sequence - the only case this kernel is launched for - no recorded position is misplaced, Q28).
+// sAt: [32][W] doubles of dynamic LDS (lds_bytes: what the launch provided).  H row a = 2 j + r of the j-th successful
+// feature in SLOT order (succ_idx): the seven pose coefficients of dh_by_dxv and the three of dh_by_dy at column 13 + 3 slot
+// (monoslam.cpp:548-572) - unless the sequence carries a misplaced recorded position (Q28, feature.cpp:254: a known feature
+// added behind a partially initialised one is three columns off once that one converts, even with one feature in flight).
+// Then the block sits at the engine column search_score_body<true> put in f_hcol, exactly as in k_build_AS: a column inside
+// the partial feature's six states is compact column nlive + (column - ppos), and a column below 7 OVERWRITES the dh_by_dxv
+// coefficients it lands on (monoslam.cpp:562-565).
 constexpr int kSmallW = 128;         // compact columns at most: 13 + 3 * 36 + 6 + 1
 constexpr int kSmallBatchMax = 256;  // sequences per group up to which the fused step is the faster one at ANY capacity (scripts/small_latency.py)
 __device__ __forceinline__ void small_update_body(const int b, double* __restrict__ x, double* __restrict__ P,
@@ -71,7 +75,8 @@ __device__ __forceinline__ void small_update_body(const int b, double* __restric
                                                   const double* __restrict__ f_nu, const double* __restrict__ f_R,
                                                   const int* __restrict__ succ_idx, const int* __restrict__ m_count,
                                                   const int* __restrict__ n_slots, const int* __restrict__ part_i, int ppos, int pend,
-                                                  int N, int ld, int* __restrict__ status, double* sAt) {
+                                                  const int* __restrict__ pos_err_any, const int* __restrict__ f_hcol,
+                                                  int N, int ld, unsigned lds_bytes, int* __restrict__ status, double* sAt) {
   __shared__ double sH[kSmallM][10];
   __shared__ double sR[kSmallM];
   __shared__ int sPos[kSmallM];
@@ -86,22 +91,27 @@ __device__ __forceinline__ void small_update_body(const int b, double* __restric
   double* Pb = P + (size_t)b * ld * ld;
   const int nlive = 13 + 3 * n_slots[b];
   const int n_c = nlive + (part_i[(size_t)b * kPartInts + kPartCount] ? pend - ppos : 0);      // compact columns that hold state
-  if (n_c + 1 > kSmallW || m > kSmallM) {             // cannot happen: the host launches this kernel only under its bound on n_slots
-    if (tid == 0) status[b] |= 8;                     // ... and if it ever did, the sequence says so instead of corrupting memory
+  const int W = (n_c + 1 <= 64) ? 64 : kSmallW;       // row pitch of the LDS panel; column W - 1 carries the innovation
+  // cannot happen: the host launches this kernel only under its bound on n_slots, with a panel of at least W columns (a captured
+  // step's key holds the panel width) - and if it ever did, the sequence says so instead of reaching outside the allocation
+  if (n_c + 1 > kSmallW || m > kSmallM || sizeof(double) * kSmallM * W > lds_bytes) {
+    if (tid == 0) status[b] |= SL2_STATUS_SMALL_STEP_REFUSED;
     return;
   }
-  const int W = (n_c + 1 <= 64) ? 64 : kSmallW;       // row pitch of the LDS panel; column W - 1 carries the innovation
   auto cmap = [&](int c) { return c < nlive ? c : ppos + (c - nlive); };
+  auto ccol = [&](int g) { return g < nlive ? g : nlive + (g - ppos); };     // (engine column -> compact column)
+  const bool q28 = pos_err_any[b] != 0;               // (uniform)
   if (tid < kSmallM) {
     if (tid < m) {
       const int f = succ_idx[(size_t)b * N + (tid >> 1)];
       const size_t fi = (size_t)b * N + f;
+      const int pos = q28 ? f_hcol[fi] : 13 + 3 * f;
 #pragma unroll
-      for (int c = 0; c < 7; ++c) sH[tid][c] = f_Hx[fi * 14 + (tid & 1) * 7 + c];
+      for (int c = 0; c < 7; ++c) sH[tid][c] = (q28 && (unsigned)(c - pos) < 3u) ? 0.0 : f_Hx[fi * 14 + (tid & 1) * 7 + c];
 #pragma unroll
       for (int c = 0; c < 3; ++c) sH[tid][7 + c] = f_Hy[fi * 6 + (tid & 1) * 3 + c];
       sR[tid] = f_R[fi];
-      sPos[tid] = 13 + 3 * f;
+      sPos[tid] = pos;                                // the ENGINE column (the row of P that A^T reads)
       sAt[tid * W + W - 1] = f_nu[fi * 2 + (tid & 1)];         // the innovation rides along as the last column
     } else {
       sAt[tid * W + W - 1] = 0.0;
@@ -115,6 +125,14 @@ __device__ __forceinline__ void small_update_body(const int b, double* __restric
 #pragma unroll
   for (int c = 0; c < 7; ++c) pc[c] = (i < n_c) ? ((i < 13) ? Pb[(size_t)i * ld + c] : Pb[(size_t)c * ld + gi]) : 0.0;
   __syncthreads();
+  if (q28) {                                          // every misplaced block must still land on columns that hold state
+    bool ok = true;
+    for (int a = 0; a < m; ++a) { const int cp = ccol(sPos[a]); ok = ok && sPos[a] >= 0 && cp >= 0 && cp + 3 <= n_c; }
+    if (!ok) {                                        // (the same verdict in every thread)
+      if (tid == 0) status[b] |= SL2_STATUS_SMALL_STEP_REFUSED;
+      return;
+    }
+  }
   if (i < W - 1) {
     for (int a = a0; a < kSmallM; a += astep) {
       double acc = 0.0;
@@ -139,7 +157,7 @@ __device__ __forceinline__ void small_update_body(const int b, double* __restric
     double v = (a == bb) ? 1.0 : 0.0;
     if (a < m && bb < m) {
       const double* arow = sAt + bb * W;
-      const int pos = sPos[a];                        // (13 + 3 slot < nlive: the compact index of a feature column is the column)
+      const int pos = ccol(sPos[a]);                  // (13 + 3 slot < nlive: the compact index of a feature column is the column)
       double acc = 0.0;
 #pragma unroll
       for (int c = 0; c < 7; ++c) acc = __builtin_fma(sH[a][c], arow[c], acc);
@@ -247,7 +265,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
     const double* __restrict__ f_R, const int* __restrict__ part_i, int pend, int ld,
     double* __restrict__ traj, int* __restrict__ traj_count, const double* __restrict__ last_r, double* __restrict__ pos_log,
     int* __restrict__ pos_count, int min_attempts, double match_fraction, int save_trajectory, int* __restrict__ slots_max,
-    unsigned long long* __restrict__ slots_mail, int publish) {
+    unsigned long long* __restrict__ slots_mail, int publish, unsigned lds_bytes) {
   extern __shared__ double s_dynd[];                  // phase by phase: [N + 8] ints, [32][128] doubles, [2 N] ints
   const int b = blockIdx.x;
   SST(3, 0);
@@ -260,7 +278,8 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
                           (int*)s_dynd, s_ext_score);
   __syncthreads();
   SST(3, 1);
-  small_update_body(b, x, P, f_Hx, f_Hy, f_nu, f_R, succ_idx, m_count, n_slots, part_i, ppos0, pend, N, ld, status, s_dynd);
+  small_update_body(b, x, P, f_Hx, f_Hy, f_nu, f_R, succ_idx, m_count, n_slots, part_i, ppos0, pend, pos_err_any, f_hcol, N, ld, lds_bytes,
+                    status, s_dynd);
   __syncthreads();
   SST(3, 2);
   finalize_body<true>(b, x, P, f_flags, n_slots, attempted, successful, m_count, n_sel, traj, traj_count, last_r, status, pos_log,
@@ -271,8 +290,9 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
 
 // Which stages of a sequence group's step are fused: 0 = none (ten launches), 1 = both sides of the search (three launches),
 // 2 = the back side only (scoring + update + finalize in one launch, the front-end stages on their own: six launches).
-// Static conditions: at most 16 features measured per frame - the innovation system is one 32 x 32 block - and no recorded
-// feature position can be misplaced (Q28 needs two partially initialised features in flight).  Dynamic: the LIVE maps fit
+// Static conditions: at most 16 features measured per frame - the innovation system is one 32 x 32 block - and one partially
+// initialised feature in flight at most (a misplaced recorded position, Q28, is taken from f_hcol like the ten-launch step
+// does; the host cannot know of one without a synchronisation, so it is not a condition).  Dynamic: the LIVE maps fit
 // kSmallW columns - `slots_bound` = the host's upper bound on n_slots of any sequence (sl2_engine.hip: slots_upper_bound, exact
 // at synchronised points, from the device's mailbox in between).  Then: everything fused when the group is small enough to be
 // latency-bound or the capacity is large (the one-stage kernels work on all ld columns, the fused ones on the live ones:
@@ -283,6 +303,13 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
 int small_step_mode(const sl2_engine* e, int slots_bound) {
   if (!e->root->step_fusion || e->mld != kSmallM || e->kpart != 1 || 13 + 3 * slots_bound + 6 * e->kpart + 1 > kSmallW) return 0;
   return (e->B <= kSmallBatchMax || e->ld >= 256 || e->root->step_fusion == 2) ? 1 : 2;
+}
+
+// Columns of k_small_back's LDS panel for a group whose live maps are at most `slots_bound` slots: 64 while every map fits
+// them (a third workgroup per CU at large batches), else kSmallW.  The kernel picks its own W from each sequence's size, which
+// the bound bounds; a captured step bakes this choice in, so it is part of the step's key (sl2_go_one_step).
+int small_panel_w(const sl2_engine* e, int slots_bound) {
+  return (13 + 3 * slots_bound + 6 * e->kpart + 1 <= 64) ? 64 : kSmallW;
 }
 
 int launch_small_front(sl2_engine* e, int n) {
@@ -299,9 +326,8 @@ int launch_small_front(sl2_engine* e, int n) {
 
 int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound) {
   LaunchScope ls(e, "k_small_back", true);
-  // the LDS panel is [32][W], W = 64 while every live map of the group fits it (the kernel picks W from the sequence's own size,
-  // which the bound bounds): a third workgroup per CU at large batches
-  size_t shm = sizeof(double) * kSmallM * ((13 + 3 * slots_bound + 6 * e->kpart + 1 <= 64) ? 64 : kSmallW);
+  // the LDS panel is [32][W] (small_panel_w)
+  size_t shm = sizeof(double) * kSmallM * small_panel_w(e, slots_bound);
   // (the bookkeeping phases: [N + 8] ints + 16 x kWorkDoubles doubles, then [2 N] ints + 354 doubles)
   const size_t ints = sizeof(int) * (2 * (size_t)e->N + 10) + sizeof(double) * (16 + 169 + 169 + 16 * kWorkDoubles);
   if (ints > shm) shm = ints;
@@ -311,7 +337,7 @@ int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound) {
                      e->N, e->srch_big, e->status, e->x, e->P, e->f_Hx, e->f_Hy, e->f_R, e->part_i, e->ppos + 6 * e->kpart, e->ld,
                      e->traj, e->traj_count, e->last_r, e->pos_log, e->pos_count, e->prm.minimum_attempted_measurements_of_feature,
                      e->prm.successful_match_fraction, save_trajectory, e->root->slots_max_dev, e->root->slots_mail_dev,
-                     e->group_first == 0 ? 1 : 0);
+                     e->group_first == 0 ? 1 : 0, (unsigned)shm);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }

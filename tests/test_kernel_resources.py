@@ -63,3 +63,36 @@ def test_hot_kernels_stay_inside_their_register_budgets(tmp_path):
         assert sspills <= max_sspill, "%s spills %d scalar registers (allowed %d)" % (frag, sspills, max_sspill)
         assert vg <= max_regs, "%s uses %d registers, budget %d (= %d wavefronts per SIMD)" % (frag, vg, max_regs, waves)
         assert 512 // ((vg + 7) // 8 * 8) >= waves
+
+
+def _descriptor(text, frag):
+    m = re.search(r"\.name:\s+(\S*%s\S*)\n" % re.escape(frag), text)
+    assert m, "kernel %s not found" % frag
+    start = text.rfind("- .agpr_count", 0, m.start())
+    end = text.find("- .agpr_count", m.end())
+    return text[start:end if end > 0 else len(text)]
+
+
+def _constexpr(src, name):
+    m = re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(CSRC, src)).read())
+    assert m, "%s not found in %s" % (name, src)
+    return int(m.group(1))
+
+
+LDS_PER_CU = 160 * 1024          # gfx950
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+def test_small_back_leaves_room_for_three_workgroups_per_cu(tmp_path):
+    """k_small_back's LDS: its static arrays (the update's sH, sR, sPos, sS, sLinv, sCol and the bookkeeping bodies' own) plus the
+    largest dynamic region launch_small_back asks for - the [32][kSmallW] panel of doubles, or the bookkeeping phases' scratch at
+    the largest capacity sl2_create accepts (ld <= 2048) if that were bigger - must fit a third of the CU's LDS: three workgroups
+    per CU at large batches (sl2_small.hip).  A static array added to the kernel fails no parity test; it fails this one."""
+    block = _descriptor(_assembly("sl2_small.hip", ["-ffp-contract=off"], tmp_path), "k_small_back")
+    static = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
+    panel = 8 * _constexpr("sl2_small.hip", "kSmallM") * _constexpr("sl2_small.hip", "kSmallW")
+    n_max = (2048 - 13 - 6 - 1) // 3                       # ld = roundup(13 + 3 N + 6 kpart + 1, 64) <= 2048, kpart >= 1
+    scratch = 4 * (2 * n_max + 10) + 8 * (16 + 169 + 169 + 16 * _constexpr("sl2_common.hpp", "kWorkDoubles"))
+    dyn = max(panel, scratch)
+    assert static + dyn <= LDS_PER_CU // 3, "k_small_back: %d B static + %d B dynamic > %d B (a third of the CU's LDS)" % (
+        static, dyn, LDS_PER_CU // 3)
