@@ -36,7 +36,9 @@ extern "C" {
  * sequence (max_features_to_init_at_once > 1), sl2_get_partial_feature takes the index of the partial feature; 5 = sl2_ingest_next
  * uploads on a stream of its own, one frame ahead (or hands a small batch out in place): its `stream` argument is the stream the
  * frames are CONSUMED on, not the one the copy is queued on; sl2_set_update_variant no longer takes chol_variant 2; new:
- * sl2_set_step_fusion, sl2_get_stream, sl2_ingest_set_zero_copy; scenelib2_amd_comm.h. */
+ * sl2_set_step_fusion, sl2_get_stream, sl2_ingest_set_zero_copy; scenelib2_amd_comm.h.  Additions within 5: sl2_save_sequences,
+ * sl2_load_sequences, sl2_copy_sequences, sl2_reset_sequences, sl2_sequence_blob_capacity, sl2_sequence_blob_layout;
+ * sl2_snapshot_header.sequence_steps (taken from reserved[]). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -400,7 +402,9 @@ typedef struct sl2_snapshot_header {
   int32_t init_feature_search_region[4];       /* ustart, vstart, ufinish, vfinish */
   int32_t off_xv, off_Pxx, off_features, off_cov, off_selection, off_traj, off_partial, off_patches;
   int32_t steps_done;                          /* GoOneStep calls so far (low 31 bits) */
-  int32_t reserved[31];
+  int32_t sequence_steps;                      /* steps this SEQUENCE has taken (low 31 bits): differs from steps_done once the
+                                                  sequence was loaded, copied in or reset (sl2_load_sequences below) */
+  int32_t reserved[30];
 } sl2_snapshot_header;                         /* 256 bytes */
 typedef struct sl2_partial_info {              /* FeatureInitInfo, feature_init_info.h:77-118 */
   int32_t label;                               /* fp_->label_ */
@@ -452,6 +456,92 @@ int sl2_delete_features(sl2_engine* e, int seq0, int nseq, const int32_t* labels
  * engine bug, and the sequence's filter is no longer the reference's. */
 #define SL2_STATUS_SMALL_STEP_REFUSED 8
 int sl2_get_status_flags(sl2_engine* e, int seq0, int nseq, int32_t* flags);
+
+/* ------------------------------------------------- save / restore / copy / reset of sequences */
+
+/* The COMPLETE state of one sequence as a self-describing, position-independent blob (additions within SL2_API_VERSION 5): not
+ * the public view of sl2_snapshot but everything a later step reads - x and P, templates in their packed form, retired slots,
+ * counters, the recorded-position offsets (Q28), the partially initialised features with their particles, the drand48 state,
+ * both trajectory stores.  k_seq_pack / k_seq_unpack (sl2_checkpoint.hip) write and read it on the device.  A blob can be loaded
+ * into any sequence of any engine that FITS: the same sl2_camera and sl2_params (bytewise, except max_features_to_init_at_once
+ * and number_of_features_to_select, which must be at least what the blob uses: its partial slots, its selected features),
+ * max_features >= n_slots, partial slots >= n_partial_slots, particle capacity >= n_particles.  Same-shape engines continue a
+ * loaded sequence bit for bit; another shape keeps every integer result and agrees to rounding (the partial features' columns
+ * sit elsewhere, so sums run in another order).
+ *
+ * Layout: every section starts on a 64-byte boundary at the offset the header gives.  n = 13 + 3 n_slots + 6 n_partial_slots.
+ *   header        sl2_sequence_blob_header (256 bytes), written LAST by the device
+ *   off_x         double[row_pitch]            canonical order: vehicle (13), slots 0 .. n_slots - 1 (3 each, retired slots
+ *                                              included: they are zero), partial slots 0 .. n_partial_slots - 1 (6 each); zero padded
+ *   off_P         double[n][row_pitch]         the leading n x n square in the same order (the full square, not a triangle: P is
+ *                                              symmetric only after sl2_finish_step); row_pitch = n rounded up to 8 doubles
+ *   off_slots     SL2_BLOB_SLOT_ARRAYS arrays of [n_slots] records, each array on a 64-byte boundary, in this order (bytes per
+ *                 record): template 288, patch_sums 8, xp_org 64, flags 4, label 4, attempted 4, successful 4, pos_err 4,
+ *                 h column 4 (canonical column), h 16, Hx 112, Hy 48, R 8, S 32, score 8, z 16, nu 16, selection order 4,
+ *                 meas_ok 4, meas_score 8, successes 4, first row in S 4   (sl2_sequence_blob_layout reports each offset)
+ *   off_seq       448 bytes: int32 n_slots, next_label, status, pos_err_any, n_selected, n_visible, m_count, traj_count;
+ *                 uint64 drand48 state; double prev_r[3], last_r[3], part_d[4]; at 128: int32 part_i[16]; at 192: int32
+ *                 ps_i[4][8]; at 320: double ps_d[4][4]
+ *   off_particles double[n_partial_slots][n_particles][12]
+ *   off_traj      double[1000][3]  trajectory_store_ ring (entry k of the sequence's life at k % 1000)
+ *   off_pos_log   double[1000][3]  the position log, oldest first, the newest entry LAST; entries from before the sequence
+ *                                  existed are zero
+ * Not in the blob: what a step rewrites before it reads it (search windows, A^T, V^T, S, L, the particles' search ellipses, the
+ * score cache, the work counters).  A blob is therefore taken between steps, or between the seams from sl2_make_measurements on.
+ *
+ * The step clock: an engine counts steps, not its sequences.  A loaded or reset sequence takes the DESTINATION engine's step
+ * index; its position log is placed so that its newest entry is the destination's newest, and sl2_get_position_log shows of it
+ * what is not older than the destination engine (count = min(capacity, destination steps done, 1000)).  The sequence's own age
+ * travels in the header and is reported by sl2_snapshot_header.sequence_steps. */
+#define SL2_BLOB_MAGIC 0x51324c53u /* "SL2Q" */
+#define SL2_BLOB_LAYOUT_VERSION 1
+#define SL2_BLOB_SLOT_ARRAYS 22
+typedef struct sl2_sequence_blob_header {
+  uint32_t magic;                              /* SL2_BLOB_MAGIC */
+  uint32_t layout_version;                     /* SL2_BLOB_LAYOUT_VERSION */
+  uint64_t bytes;                              /* size of the whole blob, a multiple of 64 */
+  int64_t sequence_steps;                      /* steps the sequence has taken */
+  int32_t src_max_features, src_partial_slots, src_particle_capacity;   /* shape of the engine that wrote it */
+  int32_t width, height;
+  int32_t n_slots;                             /* feature slots in use (live, reserved or retired) */
+  int32_t n_partial_slots;                     /* highest partial slot in use + 1 */
+  int32_t n_particles;                         /* particles stored per partial slot (the largest count in use) */
+  int32_t mapping_in_use;                      /* the source engine had feature initialisation in use */
+  uint32_t off_x, off_P, off_slots, off_seq, off_particles, off_traj, off_pos_log;
+  int32_t row_pitch;                           /* doubles per row of x / P in the blob */
+  int32_t state_size;                          /* n */
+  sl2_camera camera;
+  sl2_params params;
+  int32_t n_selected;                          /* features selected in the sequence's last selection (rows of the innovation system) */
+  int32_t reserved[3];
+} sl2_sequence_blob_header;                    /* 256 bytes */
+/* The layout arithmetic, host only (no device needed): offsets [capacity] receives off_x, off_P, off_slots, the
+ * SL2_BLOB_SLOT_ARRAYS array offsets, off_seq, off_particles, off_traj, off_pos_log (SL2_BLOB_LAYOUT_OFFSETS values, as many as
+ * fit); returns the blob's size in bytes, 0 for a negative argument. */
+#define SL2_BLOB_LAYOUT_OFFSETS (7 + SL2_BLOB_SLOT_ARRAYS)
+size_t sl2_sequence_blob_layout(int n_slots, int n_partial_slots, int n_particles, uint64_t* offsets, int capacity);
+/* Upper bound of one blob of this engine (every slot, partial slot and particle in use), a multiple of 64. */
+size_t sl2_sequence_blob_capacity(const sl2_engine* e);
+/* One blob per sequence of [seq0, seq0 + nseq) at blobs + i * blob_stride (blob_stride >= sl2_sequence_blob_capacity, a multiple
+ * of 64).  blobs_on_device != 0: one launch on the engine's stream, asynchronous, nothing else; `bytes` must be NULL (the size
+ * is in each header).  Otherwise packed on the device into engine-owned staging of bounded size and copied out chunk by chunk,
+ * one synchronisation per chunk; bytes [nseq] (may be NULL) receives each blob's size.  The engine is not changed. */
+int sl2_save_sequences(sl2_engine* e, int seq0, int nseq, void* blobs, size_t blob_stride, int blobs_on_device, uint64_t* bytes);
+/* The inverse, into sequences [seq0, seq0 + nseq).  blob_stride = distance between blobs AND the bytes available of each (any
+ * multiple of 64 that holds the blob).  Every header is checked BEFORE anything is written (device blobs: the 256-byte headers
+ * are fetched first): SL2_ERR_INVALID (magic, version, sizes, offsets, camera, params) or SL2_ERR_CAPACITY (the blob does not
+ * fit this engine) with sl2_last_error() naming the field, and the engine untouched.  A blob with mapping in use switches
+ * feature initialisation on (MatchPartiallyInitialisedFeatures goes on running, monoslam.cpp:167) and is refused with more
+ * than one sequence group, like mapping itself.  Rows, columns and slots the blob does not cover are zeroed.  Synchronises;
+ * captured step graphs are dropped. */
+int sl2_load_sequences(sl2_engine* e, int seq0, int nseq, const void* blobs, size_t blob_stride, int blobs_on_device);
+/* Save + load without the host, between two engines on one device or inside one engine (overlapping ranges: SL2_ERR_INVALID).
+ * Engines on different streams are ordered by an event.  The destination is treated as by sl2_load_sequences. */
+int sl2_copy_sequences(sl2_engine* dst, int dst_seq0, sl2_engine* src, int src_seq0, int nseq);
+/* The sequences become what sl2_create left: empty map, next_free_label_ 0, counters, status, trajectory store, position log
+ * and partial features cleared, drand48 as after srand48(0) (monoslam.cpp:1968), x and P zero.  The caller then sets the
+ * vehicle state and adds features as for a fresh engine.  Synchronises; captured step graphs are dropped. */
+int sl2_reset_sequences(sl2_engine* e, int seq0, int nseq);
 
 /* ------------------------------------------------------------------- profiling */
 

@@ -289,6 +289,38 @@ class MonoSLAM {
     }
   }
 
+  // The filter as a file (not in the reference, which cannot stop and resume): the sequence blob of sl2_save_sequences -
+  // state, covariance, templates, counters, partially initialised features with their particles, the drand48 state, both
+  // trajectory stores.  LoadState wants an object initialised with the same camera and parameters (Init); its map is replaced
+  // and the run continues as if it had never stopped.
+  void SaveState(const std::string& path) {
+    std::vector<unsigned char> blob(sl2_sequence_blob_capacity(eng_));
+    uint64_t bytes = 0;
+    check(sl2_save_sequences(eng_, 0, 1, blob.data(), blob.size(), 0, &bytes), "sl2_save_sequences");
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("MonoSLAM::SaveState: cannot write " + path);
+    const size_t done = std::fwrite(blob.data(), 1, (size_t)bytes, f);
+    if (std::fclose(f) != 0 || done != (size_t)bytes) throw std::runtime_error("MonoSLAM::SaveState: short write to " + path);
+  }
+  void LoadState(const std::string& path) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("MonoSLAM::LoadState: cannot read " + path);
+    std::vector<unsigned char> blob;
+    unsigned char buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;) blob.insert(blob.end(), buf, buf + n);
+    std::fclose(f);
+    if (blob.size() < sizeof(sl2_sequence_blob_header)) throw std::runtime_error("MonoSLAM::LoadState: " + path + " is not a sequence blob");
+    if (reinterpret_cast<const sl2_sequence_blob_header*>(blob.data())->bytes > blob.size())
+      throw std::runtime_error("MonoSLAM::LoadState: " + path + " is truncated");
+    blob.resize((blob.size() + 63) / 64 * 64);
+    check(sl2_load_sequences(eng_, 0, 1, blob.data(), blob.size(), 0), "sl2_load_sequences");
+    // nothing this object cached belongs to the loaded sequence
+    feature_list_.clear(); selected_feature_list_.clear(); trajectory_store_.clear(); patch_cache_.clear();
+    traj_seen_ = 0; patch_seen_ = 0;
+    refresh_public_members();
+    map_full_ = (status_flags_ & SL2_STATUS_LABELS_EXHAUSTED) != 0;
+  }
+
   sl2_engine* engine() { return eng_; }
   // Wall time of the last GoOneStep: the sl2_go_one_step call and the read-back of the public members (one sl2_snapshot).
   // The step is asynchronous, so without measure_timing_ the first figure is its enqueue time and the second one holds the

@@ -67,7 +67,7 @@ class sl2_snapshot_header(C.Structure):
         "n_partial", "n_patches", "uu", "vv", "location_selected_flag", "init_feature_search_region_defined_flag")] + \
         [("init_feature_search_region", C.c_int32 * 4)] + \
         [(n, C.c_int32) for n in ("off_xv", "off_Pxx", "off_features", "off_cov", "off_selection", "off_traj", "off_partial",
-                                  "off_patches", "steps_done")] + [("reserved", C.c_int32 * 31)]
+                                  "off_patches", "steps_done", "sequence_steps")] + [("reserved", C.c_int32 * 30)]
 
 
 class sl2_partial_info(C.Structure):
@@ -75,7 +75,21 @@ class sl2_partial_info(C.Structure):
                 ("making_measurement_on_this_step_flag", C.c_int32), ("mean", C.c_double), ("covariance", C.c_double)]
 
 
-assert C.sizeof(sl2_snapshot_header) == 256 and C.sizeof(sl2_partial_info) == 32
+class sl2_sequence_blob_header(C.Structure):
+    """Header of a sequence blob (Engine.save_sequences / load_sequences)."""
+    _fields_ = [("magic", C.c_uint32), ("layout_version", C.c_uint32), ("bytes", C.c_uint64), ("sequence_steps", C.c_int64)] + \
+        [(n, C.c_int32) for n in ("src_max_features", "src_partial_slots", "src_particle_capacity", "width", "height", "n_slots",
+                                  "n_partial_slots", "n_particles", "mapping_in_use")] + \
+        [(n, C.c_uint32) for n in ("off_x", "off_P", "off_slots", "off_seq", "off_particles", "off_traj", "off_pos_log")] + \
+        [("row_pitch", C.c_int32), ("state_size", C.c_int32), ("camera", sl2_camera), ("params", sl2_params),
+         ("n_selected", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+SL2_BLOB_MAGIC = 0x51324C53
+SL2_BLOB_SLOT_ARRAYS = 22
+SL2_BLOB_LAYOUT_OFFSETS = 7 + SL2_BLOB_SLOT_ARRAYS
+
+assert C.sizeof(sl2_snapshot_header) == 256 and C.sizeof(sl2_partial_info) == 32 and C.sizeof(sl2_sequence_blob_header) == 256
 
 # every symbol include/scenelib2_amd.h declares (tests check the .so exports all of them)
 EXPORTED_SYMBOLS = [
@@ -90,6 +104,8 @@ EXPORTED_SYMBOLS = [
     "sl2_reset_kernel_times", "sl2_kernel_count", "sl2_get_kernel_time", "sl2_get_step_work", "sl2_get_placement",
     "sl2_synth_render_host", "sl2_synth_render_device", "sl2_dev_malloc", "sl2_dev_free", "sl2_dev_upload",
     "sl2_dev_download",
+    "sl2_sequence_blob_layout", "sl2_sequence_blob_capacity", "sl2_save_sequences", "sl2_load_sequences", "sl2_copy_sequences",
+    "sl2_reset_sequences",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench"]
@@ -191,6 +207,15 @@ def _bind(L):
     L.sl2_dev_free.argtypes = [C.c_int, vp]
     L.sl2_dev_upload.argtypes = [C.c_int, vp, vp, C.c_size_t]
     L.sl2_dev_download.argtypes = [C.c_int, vp, vp, C.c_size_t]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_save_sequences"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_sequence_blob_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int]
+        L.sl2_sequence_blob_layout.restype = C.c_size_t
+        L.sl2_sequence_blob_capacity.argtypes = [vp]
+        L.sl2_sequence_blob_capacity.restype = C.c_size_t
+        L.sl2_save_sequences.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
+        L.sl2_load_sequences.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int]
+        L.sl2_copy_sequences.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+        L.sl2_reset_sequences.argtypes = [vp, C.c_int, C.c_int]
     return L
 
 

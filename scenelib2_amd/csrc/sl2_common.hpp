@@ -148,6 +148,7 @@ struct sl2_engine {
   double* pos_log = nullptr;  // [B][kTrajCapacity][3] xv[0:3] after every step (the true trajectory, cf. Q12)
   int* pos_count = nullptr;   // [B] steps logged so far (device-side, so that a captured step needs no per-step argument)
   long long steps_done = 0;
+  int* seq_age = nullptr;     // [B] a sequence's own step count minus pos_count (0 until it is loaded, copied in or reset: sl2_checkpoint.hip)
   int chol_variant = 1;       // 1 = one-launch left-looking Cholesky (k_chol_left; the product's only path); TEST build: 0 = launch-per-block kernels
   void* chol_trace = nullptr; // development only (SL2_CHOL_TRACE builds): per-wave cycle stamps of k_chol_fused4
   int build_variant = 1;      // 1 = k_build_AS (A and S in one pass over the measured features' rows of P; the product's only path); TEST build: 0 = k_build_A then k_build_S
@@ -251,6 +252,9 @@ struct sl2_engine {
   size_t acc_dev_bytes = 0;
   void* acc_host = nullptr;       // pinned host scratch of the same calls
   size_t acc_host_bytes = 0;
+  void* ckpt_stage = nullptr;     // device: the blobs of one chunk of sl2_save_sequences / sl2_load_sequences / sl2_copy_sequences (grown on demand, bounded)
+  size_t ckpt_stage_bytes = 0;
+  hipEvent_t ckpt_event = nullptr;   // orders two engines' streams in sl2_copy_sequences
 
   uint8_t* frames_buf = nullptr;  // [B][W*H] staging for host frames
   const uint8_t* cur_frames = nullptr;
@@ -321,6 +325,11 @@ int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int s
 int launch_manual_init(sl2_engine* e, const int* d_uv);
 int launch_auto_init(sl2_engine* e);
 int launch_compact_slots(sl2_engine* e, int need);   // sl2_mapping.hip: retired slots squeezed out when a sequence lacks room for `need` more features
+// sl2_engine.hip, for sl2_checkpoint.hip: what a call owes the engine when it replaces sequences under it
+int checkpoint_refresh_slots(sl2_engine* e);         // refresh_slots_exact
+int checkpoint_drop_graphs(sl2_engine* e);           // drop_step_graphs
+int checkpoint_enable_mapping(sl2_engine* e);        // enable_feature_initialisation
+void release_checkpoint_staging(sl2_engine* e);      // sl2_checkpoint.hip (sl2_destroy)
 int write_grey_image(const char* path, const uint8_t* px, int w, int h);   // sl2_ingest.hip (PGM / PNG)
 
 }  // namespace sl2

@@ -489,6 +489,7 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
   A(dmalloc(&e->status, B));
   A(dmalloc(&e->pos_log, B * kTrajCapacity * 3));
   A(dmalloc(&e->pos_count, B));
+  A(dmalloc(&e->seq_age, B));
   A(dmalloc(&e->f_h, B * N * 2));
   A(dmalloc(&e->f_Hx, B * N * 14));
   A(dmalloc(&e->f_Hy, B * N * 6));
@@ -603,8 +604,9 @@ void sl2_destroy(sl2_engine* e) {
                   e->traj, e->traj_count, e->last_r, e->status, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score,
                   e->f_z, e->f_nu, e->sel_idx, e->n_sel, e->n_vis, e->meas_ok, e->meas_score, e->succ_idx, e->f_arow, e->m_count,
                   e->work, e->At, e->Vt, e->St, e->LinvT, e->frames_buf, e->pos_log, e->srch_i, e->srch_d, e->srch_res, e->srch_sel,
-                  e->part_i, e->part_d, e->particles, e->rand48, e->prev_r, e->me_desc, e->score_map, e->me_big_list, e->ps_i, e->ps_d, e->pos_err, e->pos_err_any, e->f_hcol, e->pos_count, e->init_uv, e->f_label, e->next_label};
+                  e->part_i, e->part_d, e->particles, e->rand48, e->prev_r, e->me_desc, e->score_map, e->me_big_list, e->ps_i, e->ps_d, e->pos_err, e->pos_err_any, e->f_hcol, e->pos_count, e->init_uv, e->f_label, e->next_label, e->seq_age};
   for (void* p : ptrs) if (p) hipFree(p);
+  release_checkpoint_staging(e);
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
   if (e->slots_mail) hipHostFree(e->slots_mail);
   if (e->snap_stage) hipFree(e->snap_stage);
@@ -1538,3 +1540,9 @@ int sl2_debug_ncc_score(int device, const int32_t* sums5, int count, double* sco
 #endif  // SL2_TESTING
 
 }  // extern "C"
+
+namespace sl2 {
+int checkpoint_refresh_slots(sl2_engine* e) { return refresh_slots_exact(e); }
+int checkpoint_drop_graphs(sl2_engine* e) { return drop_step_graphs(e); }
+int checkpoint_enable_mapping(sl2_engine* e) { return enable_feature_initialisation(e); }
+}  // namespace sl2

@@ -16,7 +16,7 @@ namespace sl2 {
 struct SnapArrays {
   const double *x, *P, *xp_org, *f_h, *f_z, *f_nu, *f_R, *f_S, *f_Hx, *f_Hy, *traj, *ps_d, *particles;
   const int *f_flags, *f_label, *n_slots, *next_label, *attempted, *successful, *sel_idx, *n_sel, *n_vis, *m_count, *traj_count,
-      *status, *part_i, *ps_i, *pos_err;
+      *status, *part_i, *ps_i, *pos_err, *pos_count, *seq_age;
   const uint8_t* patch;
 };
 
@@ -119,6 +119,7 @@ __global__ void __launch_bounds__(kSnapThreads) k_snapshot(SnapArrays a, int seq
     hd.init_feature_search_region_defined_flag = pi[kPartRegionValid];
     for (int k = 0; k < 4; ++k) hd.init_feature_search_region[k] = pi[kPartRegion + k];
     hd.steps_done = (int)(steps_done & 0x7fffffff);
+    hd.sequence_steps = (a.pos_count[seq] + a.seq_age[seq]) & 0x7fffffff;
     int off = (int)sizeof(sl2_snapshot_header);
     hd.off_xv = off; off += 13 * 8;
     hd.off_Pxx = off; off += 169 * 8;
@@ -269,6 +270,7 @@ extern "C" int sl2_snapshot(sl2_engine* e, int seq, int traj_cursor, int patch_f
   a.f_flags = e->f_flags; a.f_label = e->f_label; a.n_slots = e->n_slots; a.next_label = e->next_label; a.attempted = e->attempted;
   a.successful = e->successful; a.sel_idx = e->sel_idx; a.n_sel = e->n_sel; a.n_vis = e->n_vis; a.m_count = e->m_count;
   a.traj_count = e->traj_count; a.status = e->status; a.part_i = e->part_i; a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.patch = e->patch;
+  a.pos_count = e->pos_count; a.seq_age = e->seq_age;
   hipLaunchKernelGGL(k_snapshot, dim3(1), dim3(kSnapThreads), sizeof(int) * 8 * e->N, e->stream, a, seq, e->N, e->ld, e->ppos, e->pcap, e->kpart,
                      traj_cursor, patch_from_label, e->steps_done, (unsigned char*)e->snap_stage, (uint4*)e->snap_host_dev,
                      (unsigned long long*)((char*)e->snap_host_dev + e->snap_cap), ++e->snap_ticket);

@@ -304,6 +304,56 @@ class Engine:
         self._ck(self.L.sl2_get_status_flags(self.h, 0, self.batch, _lib.ip(out)))
         return out
 
+    # ---- save / restore / copy / reset of sequences (sl2_save_sequences ...) -------
+    def sequence_blob_capacity(self):
+        """Upper bound in bytes of one sequence blob of this engine (a multiple of 64)."""
+        return int(self.L.sl2_sequence_blob_capacity(self.h))
+
+    def save_sequences(self, seq0=0, nseq=None):
+        """The complete state of sequences [seq0, seq0 + nseq) as one `bytes` blob each (self-describing: see
+        sl2_sequence_blob_header).  The engine is not changed."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        cap = self.sequence_blob_capacity()
+        buf = np.zeros((max(nseq, 1), cap), dtype=np.uint8)
+        sizes = np.zeros(max(nseq, 1), dtype=np.uint64)
+        self._ck(self.L.sl2_save_sequences(self.h, int(seq0), nseq, buf.ctypes.data_as(_lib.vp), cap, 0,
+                                           sizes.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [buf[i, :int(sizes[i])].tobytes() for i in range(nseq)]
+
+    def load_sequences(self, blobs, seq0=0):
+        """Blobs of save_sequences (of this or any engine they fit) into sequences seq0, seq0 + 1, ...  Every header is checked
+        before anything is written: a blob that is malformed or does not fit raises Sl2Error and leaves the engine untouched."""
+        blobs = [blobs] if isinstance(blobs, (bytes, bytearray, memoryview)) else list(blobs)
+        stride = max(256, max((len(b) for b in blobs), default=0))
+        stride = (stride + 63) // 64 * 64
+        buf = np.zeros((max(len(blobs), 1), stride), dtype=np.uint8)
+        for i, b in enumerate(blobs):
+            a = np.frombuffer(bytes(b), dtype=np.uint8)
+            if a.size >= 256 and _lib.sl2_sequence_blob_header.from_buffer_copy(a[:256].tobytes()).bytes > a.size:
+                raise _lib.Sl2Error(_lib.SL2_ERR_INVALID, "sequence blob %d: bytes: the blob is truncated (%d bytes given)" % (i, a.size))
+            buf[i, :a.size] = a
+        self._ck(self.L.sl2_load_sequences(self.h, int(seq0), len(blobs), buf.ctypes.data_as(_lib.vp), stride, 0))
+
+    def save_sequences_device(self, dev_ptr, blob_stride, seq0=0, nseq=None):
+        """Blobs into device memory (dev_ptr: 64-byte aligned, blob_stride >= sequence_blob_capacity()): one launch on the
+        engine's stream, asynchronous."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        self._ck(self.L.sl2_save_sequences(self.h, int(seq0), nseq, _lib.vp(int(dev_ptr)), int(blob_stride), 1, None))
+
+    def load_sequences_device(self, dev_ptr, blob_stride, seq0=0, nseq=None):
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        self._ck(self.L.sl2_load_sequences(self.h, int(seq0), nseq, _lib.vp(int(dev_ptr)), int(blob_stride), 1))
+
+    def copy_sequences(self, src, src_seq0, nseq, dst_seq0):
+        """Sequences [src_seq0, src_seq0 + nseq) of engine `src` (may be this engine) into [dst_seq0, ...) of this one, on
+        the device."""
+        self._ck(self.L.sl2_copy_sequences(self.h, int(dst_seq0), src.h, int(src_seq0), int(nseq)))
+
+    def reset_sequences(self, seq0=0, nseq=None):
+        """The sequences become what a fresh engine holds; set the vehicle state and add features next."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        self._ck(self.L.sl2_reset_sequences(self.h, int(seq0), nseq))
+
     # ---- profiling -----------------------------------------------------------
     def set_profile_focus(self, names=""):
         self._ck(self.L.sl2_set_profile_focus(self.h, names.encode() if names else None))
@@ -468,6 +518,18 @@ class MonoSLAM:
             return False
         self._engine.save_patch(0, self.marked_feature_label_, path)
         return True
+
+    # The filter as a file: the sequence blob of sl2_save_sequences (not in the reference, which cannot stop and resume).
+    def SaveState(self, path):
+        with open(path, "wb") as f:
+            f.write(self._engine.save_sequences(0, 1)[0])
+
+    # Into an object that was initialised with the same camera and parameters (InitFromValues / Init); its map is replaced.
+    def LoadState(self, path):
+        with open(path, "rb") as f:
+            self._engine.load_sequences([f.read()], 0)
+        self._patches = {d["label"]: self._engine.feature_patch(0, d["label"]) for d in self._engine.features(0)}
+        self._map_full = bool(int(self._engine.status_flags()[0]) & 2)
 
     @property
     def xv_(self):
