@@ -38,7 +38,8 @@ extern "C" {
  * frames are CONSUMED on, not the one the copy is queued on; sl2_set_update_variant no longer takes chol_variant 2; new:
  * sl2_set_step_fusion, sl2_get_stream, sl2_ingest_set_zero_copy; scenelib2_amd_comm.h.  Additions within 5: sl2_save_sequences,
  * sl2_load_sequences, sl2_copy_sequences, sl2_reset_sequences, sl2_sequence_blob_capacity, sl2_sequence_blob_layout;
- * sl2_snapshot_header.sequence_steps (taken from reserved[]). */
+ * sl2_snapshot_header.sequence_steps (taken from reserved[]); sl2_set_active_sequences, sl2_get_active_sequences,
+ * sl2_ingest_frame_counts, sl2_ingest_next_ragged. */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -165,6 +166,32 @@ int sl2_set_feature_covariances(sl2_engine* e, int seq0, int nseq, int nfeat, co
  * not take a new feature because all max_features slots hold live features. */
 int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int frames_on_device,
                     int save_trajectory, int enable_mapping);
+
+/* Stepping a subset of the batch.  Every sequence has one byte of engine state, `active`, on the device: all ones after
+ * sl2_create.  A step issued while active[b] == 0 - sl2_go_one_step in every form it takes (fused or not, graph replay, sequence
+ * groups, large maps, the feature-initialisation tail) and each of the five seams below - leaves sequence b exactly as it
+ * was, bit for bit: state and covariance, templates, flags, counters, the per-frame values the accessors read, partially
+ * initialised features and their particles, the drand48 stream, the trajectory store and the status bits.  The engine's step
+ * clock is shared, so three things do move: the position log gets one more entry that repeats the unchanged camera position
+ * (it stays aligned with the engine's steps), the sequence's own step count (sl2_sequence_blob_header.sequence_steps,
+ * sl2_snapshot_header.sequence_steps) stands still while the engine's advances, and the sequence's map size still counts
+ * towards the engine's choice of step kernels.  A sequence that is resumed predicts over one delta_t, as the reference does
+ * when it is handed the next frame.  The bytes of a paused sequence's frame are not read.
+ * The mask is not part of a sequence blob (it belongs to the engine that steps, not to the sequence) and is left alone by
+ * sl2_load_sequences / sl2_copy_sequences / sl2_reset_sequences.  It is consulted by STEPS only: sl2_add_known_features,
+ * sl2_set_vehicle_state, sl2_set_feature_covariances, sl2_delete_features, sl2_initialise_feature,
+ * sl2_initialise_auto_feature and checkpoint load / copy / reset act on the sequences they are given whatever the mask says.
+ * Change it between steps; changing it between the seams of one step is undefined.
+ *
+ * sl2_set_active_sequences: active[i] != 0 = sequence seq0 + i takes part in the steps issued after this call.  on_device == 0:
+ * `active` is host memory of any kind (pageable, pinned, registered) and is consumed before the call returns; on_device != 0:
+ * a device pointer, read by a copy kernel on the engine's stream (keep it alive and unchanged until the stream has passed
+ * this point).  Either way the change is ordered on the engine's stream: after every step already queued, before the next one.
+ * The call never waits for the device and drops no captured step (the mask is data a replayed graph reads, not part of
+ * its key).  SL2_ERR_INVALID: a range outside the batch or a null pointer. */
+int sl2_set_active_sequences(sl2_engine* e, int seq0, int nseq, const uint8_t* active, int on_device);
+/* sl2_get_active_sequences: the mask as the steps queued so far leave it (1 / 0 per sequence), to host memory.  Synchronises. */
+int sl2_get_active_sequences(sl2_engine* e, int seq0, int nseq, uint8_t* active);
 
 /* The seams of GoOneStep, individually callable (same order as the reference):
  *   Kalman::KalmanFilterPredict(monoslam,u=0)            kalman.cpp:50-69
@@ -327,6 +354,17 @@ int sl2_ingest_next(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_
  * back to the decoder once the caller's stream is past the point it had reached at the NEXT call).  A single 320 x 240 sequence
  * saves the ~10 us per frame that queueing a copy costs the host.  Before the first sl2_ingest_next only. */
 int sl2_ingest_set_zero_copy(sl2_ingest* g, size_t max_batch_bytes);
+/* Sequences of unequal length (opt-in; sl2_ingest_next and sl2_ingest_frame_count keep their meaning).
+ * sl2_ingest_frame_counts: counts[s] = frames in dirs[s], for the first min(capacity, nseq) sequences; returns nseq (< 0: bad
+ * argument).
+ * sl2_ingest_next_ragged: like sl2_ingest_next, but goes on until the LONGEST sequence is exhausted: call k hands out frame k
+ * of every sequence that still has one and sets have[s] = 1 for those, 0 for the others (have: host [nseq]).  The part of the
+ * batch that belongs to a sequence with have[s] == 0 is unspecified - nothing is decoded into it - so step with
+ * sl2_set_active_sequences(e, 0, nseq, have, 0) in front of sl2_go_one_step.  Same stream contract, one-frame-ahead upload
+ * and zero-copy rule as sl2_ingest_next.  SL2_ERR_CAPACITY = every sequence is exhausted.  A grabber serves ONE of the two
+ * calls: the other one returns SL2_ERR_INVALID once the first has been used. */
+int sl2_ingest_frame_counts(const sl2_ingest* g, int32_t* counts, int capacity);
+int sl2_ingest_next_ragged(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_t* seq_stride, uint8_t* have);
 void sl2_ingest_close(sl2_ingest* g);
 
 /* ----------------------------------------------------------------- state access */
@@ -563,7 +601,8 @@ int sl2_get_kernel_time(sl2_engine* e, int idx, const char** name, double* total
  * out[10] = searches that took the exact fallback kernel path,
  * out[11] = 16 x 16 candidate tiles of the search windows, sum_f ceil(nu / 16) ceil(nv / 16): the matrix-core work of
  * k_search_mfma (24 v_mfma_i32_16x16x64_i8 per tile),
- * out[12] = search windows that were shared out over the wavefronts of the launch (sl2_set_search_split) */
+ * out[12] = search windows that were shared out over the wavefronts of the launch (sl2_set_search_split).
+ * Sequences that are paused (sl2_set_active_sequences) when the call is made are left out of every sum. */
 #define SL2_STEP_WORK_COUNT 13
 /* capacity = length of the caller's array: min(capacity, SL2_STEP_WORK_COUNT) values are written (a caller built against a
  * header with fewer entries is never overrun; one built against more sees the extra entries untouched). */

@@ -106,6 +106,7 @@ EXPORTED_SYMBOLS = [
     "sl2_dev_download",
     "sl2_sequence_blob_layout", "sl2_sequence_blob_capacity", "sl2_save_sequences", "sl2_load_sequences", "sl2_copy_sequences",
     "sl2_reset_sequences",
+    "sl2_set_active_sequences", "sl2_get_active_sequences", "sl2_ingest_frame_counts", "sl2_ingest_next_ragged",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench"]
@@ -216,6 +217,11 @@ def _bind(L):
         L.sl2_load_sequences.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int]
         L.sl2_copy_sequences.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
         L.sl2_reset_sequences.argtypes = [vp, C.c_int, C.c_int]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_set_active_sequences"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_set_active_sequences.argtypes = [vp, C.c_int, C.c_int, c_u8p, C.c_int]
+        L.sl2_get_active_sequences.argtypes = [vp, C.c_int, C.c_int, c_u8p]
+        L.sl2_ingest_frame_counts.argtypes = [vp, c_ip, C.c_int]
+        L.sl2_ingest_next_ragged.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), c_u8p]
     return L
 
 

@@ -149,6 +149,10 @@ struct sl2_engine {
   int* pos_count = nullptr;   // [B] steps logged so far (device-side, so that a captured step needs no per-step argument)
   long long steps_done = 0;
   int* seq_age = nullptr;     // [B] a sequence's own step count minus pos_count (0 until it is loaded, copied in or reset: sl2_checkpoint.hip)
+  // ---- stepping a subset of the batch (sl2_set_active_sequences) ----
+  uint8_t* active = nullptr;  // [B] 1 = the sequence takes part in the steps issued from now on (all ones after sl2_create); engine-global, in no blob
+  int* sel_gate = nullptr;    // [B] per step: n_sel of an active sequence, 0 of a paused one (k_select) - what the search kernels take for n_sel
+  int* m_gate = nullptr;      // [B] per step: m_count of an active sequence, 0 of a paused one (k_search_score) - what the update chain takes for m_count
   int chol_variant = 1;       // 1 = one-launch left-looking Cholesky (k_chol_left; the product's only path); TEST build: 0 = launch-per-block kernels
   void* chol_trace = nullptr; // development only (SL2_CHOL_TRACE builds): per-wave cycle stamps of k_chol_fused4
   int build_variant = 1;      // 1 = k_build_AS (A and S in one pass over the measured features' rows of P; the product's only path); TEST build: 0 = k_build_A then k_build_S
@@ -324,7 +328,7 @@ int launch_finalize(sl2_engine* e, int save_trajectory);
 int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int slots_bound, int parts_state);
 int launch_manual_init(sl2_engine* e, const int* d_uv);
 int launch_auto_init(sl2_engine* e);
-int launch_compact_slots(sl2_engine* e, int need);   // sl2_mapping.hip: retired slots squeezed out when a sequence lacks room for `need` more features
+int launch_compact_slots(sl2_engine* e, int need, bool honour_mask = false);   // sl2_mapping.hip: retired slots squeezed out when a sequence lacks room for `need` more features (honour_mask: the launch of a step, which leaves paused sequences alone)
 // sl2_engine.hip, for sl2_checkpoint.hip: what a call owes the engine when it replaces sequences under it
 int checkpoint_refresh_slots(sl2_engine* e);         // refresh_slots_exact
 int checkpoint_drop_graphs(sl2_engine* e);           // drop_step_graphs

@@ -797,7 +797,7 @@ static int launch_fwdsub_lds(sl2_engine* e, int B, bool* done) {
   if (e->nblk_max <= kKsMaxBlocks && (long long)B * (e->ld / 16) <= 160 && !e->root->no_ksplit) {
     LaunchScope ls(e, "k_fwdsub_ksplit", true);
     hipLaunchKernelGGL(k_fwdsub_ksplit, dim3(xcd_grid(e->ld / 16, B)), dim3(256), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
-                       e->m_count, e->ld, e->mld, e->nblk_max, B);
+                       e->m_gate, e->ld, e->mld, e->nblk_max, B);
     SL2_HIP(hipGetLastError());
     return SL2_OK;
   }
@@ -806,7 +806,7 @@ static int launch_fwdsub_lds(sl2_engine* e, int B, bool* done) {
   LaunchScope ls(e, "k_fwdsub_lds", true);
 #define SL2_FWD_CASE(NBV)                                                                                           \
   case NBV:                                                                                                         \
-    hipLaunchKernelGGL((k_fwdsub_lds<NBV>), grid, block, 0, e->stream, e->At, e->Vt, e->St, e->LinvT, e->m_count, \
+    hipLaunchKernelGGL((k_fwdsub_lds<NBV>), grid, block, 0, e->stream, e->At, e->Vt, e->St, e->LinvT, e->m_gate, \
                        e->ld, e->mld, e->nblk_max, B, 0, 0, e->ld / 64, NBV);                                       \
     break;
   switch (e->nblk_max) {
@@ -980,7 +980,7 @@ static int launch_chol_panels(sl2_engine* e, int B) {
     const int nb = e->nblk_max - p0 < pb ? e->nblk_max - p0 : pb;
     {
       LaunchScope ls(e, "k_chol_left", true);
-      hipLaunchKernelGGL(k_chol_left, dim3(B), dim3(256), 0, e->stream, e->St, e->LinvT, e->m_count, e->mld, e->nblk_max, p0, nb,
+      hipLaunchKernelGGL(k_chol_left, dim3(B), dim3(256), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, p0, nb,
                          (long long*)nullptr);
       SL2_HIP(hipGetLastError());
     }
@@ -991,15 +991,15 @@ static int launch_chol_panels(sl2_engine* e, int B) {
       LaunchScope ls(e, "k_fwdsub_lds@chol", true);
       if (pb == 8)
         hipLaunchKernelGGL((k_fwdsub_lds<8>), dim3(xcd_grid(ntile, B)), dim3(256), 0, e->stream, e->St, e->St, e->St,
-                           e->LinvT, e->m_count, e->mld, e->mld, e->nblk_max, B, p0, c0, ntile, nb);
+                           e->LinvT, e->m_gate, e->mld, e->mld, e->nblk_max, B, p0, c0, ntile, nb);
       else
         hipLaunchKernelGGL((k_fwdsub_lds<kCholPanelBlocks>), dim3(xcd_grid(ntile, B)), dim3(256), 0, e->stream, e->St, e->St, e->St,
-                           e->LinvT, e->m_count, e->mld, e->mld, e->nblk_max, B, p0, c0, ntile, nb);
+                           e->LinvT, e->m_gate, e->mld, e->mld, e->nblk_max, B, p0, c0, ntile, nb);
       SL2_HIP(hipGetLastError());
     }
     {
       LaunchScope ls(e, "k_chol_syrk", true);
-      hipLaunchKernelGGL(k_chol_syrk, dim3(xcd_grid(ntile * (ntile + 1) / 2, B)), dim3(256), 0, e->stream, e->St, e->m_count, e->mld,
+      hipLaunchKernelGGL(k_chol_syrk, dim3(xcd_grid(ntile * (ntile + 1) / 2, B)), dim3(256), 0, e->stream, e->St, e->m_gate, e->mld,
                          B, p0 * 32, nb * 32, c0);
       SL2_HIP(hipGetLastError());
     }
@@ -1014,16 +1014,16 @@ static int launch_fwdsub_grouped(sl2_engine* e, int B) {
     if (J0 > 0) {
       LaunchScope ls(e, "k_fwd_gemm", true);
       hipLaunchKernelGGL(k_fwd_gemm, dim3(xcd_grid((g / 2) * (e->ld / 64), B)), dim3(256), 0, e->stream, e->At, e->Vt, e->St,
-                         e->m_count, e->ld, e->mld, B, J0, g / 2);
+                         e->m_gate, e->ld, e->mld, B, J0, g / 2);
       SL2_HIP(hipGetLastError());
     }
     LaunchScope ls(e, "k_fwdsub_lds", true);
     if (g == 4)
       hipLaunchKernelGGL((k_fwdsub_lds<4>), dim3(xcd_grid(e->ld / 64, B)), dim3(256), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
-                         e->m_count, e->ld, e->mld, e->nblk_max, B, J0, 0, e->ld / 64, 4);
+                         e->m_gate, e->ld, e->mld, e->nblk_max, B, J0, 0, e->ld / 64, 4);
     else
       hipLaunchKernelGGL((k_fwdsub_lds<8>), dim3(xcd_grid(e->ld / 64, B)), dim3(256), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
-                         e->m_count, e->ld, e->mld, e->nblk_max, B, J0, 0, e->ld / 64, 8);
+                         e->m_gate, e->ld, e->mld, e->nblk_max, B, J0, 0, e->ld / 64, 8);
     SL2_HIP(hipGetLastError());
   }
   return SL2_OK;
@@ -1258,6 +1258,9 @@ __global__ void __launch_bounds__(256, 4) k_syrk(const double* __restrict__ Vt, 
 // the large-map Cholesky).
 static int launch_update_range(sl2_engine* e) {
   const int B = e->B;     // (succ_idx / m_count, the successful measurements in slot order, come from k_search_score)
+  // Every kernel of the update takes its row count from a pointer and leaves at once on 0 - before it writes anything to x or P
+  // (At / Vt / St / LinvT are rebuilt by every update).  What they are handed is m_gate: m_count for a sequence that takes part in
+  // the step, 0 for a paused one (k_search_score; sl2_set_active_sequences), so a paused sequence costs these kernels one load.
 #ifdef SL2_TESTING
   const int build_variant = e->root->build_variant, chol_variant = e->root->chol_variant, fwd_variant = e->root->fwd_variant;
 #else
@@ -1269,13 +1272,13 @@ static int launch_update_range(sl2_engine* e) {
       LaunchScope ls(e, "k_build_A", true);
       const int threads = e->ld <= 512 ? e->ld : 512;
       hipLaunchKernelGGL(k_build_A, dim3(B), dim3(threads), 0, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->succ_idx,
-                         e->m_count, e->At, e->N, e->ld, e->mld);
+                         e->m_gate, e->At, e->N, e->ld, e->mld);
       SL2_HIP(hipGetLastError());
     }
     {
       LaunchScope ls(e, "k_build_S");
       dim3 grid(e->mld / 32, (e->mld + 255) / 256, B);
-      hipLaunchKernelGGL(k_build_S, grid, dim3(256), 0, e->stream, e->At, e->f_Hx, e->f_Hy, e->f_R, e->succ_idx, e->m_count,
+      hipLaunchKernelGGL(k_build_S, grid, dim3(256), 0, e->stream, e->At, e->f_Hx, e->f_Hy, e->f_R, e->succ_idx, e->m_gate,
                          e->St, e->N, e->ld, e->mld);
       SL2_HIP(hipGetLastError());
     }
@@ -1296,11 +1299,11 @@ static int launch_update_range(sl2_engine* e) {
       size_t shm = sizeof(double) * 2 * kASBatch * e->ld;
       if ((size_t)e->root->build_lds_min > shm) shm = (size_t)e->root->build_lds_min;
       hipLaunchKernelGGL((k_build_AS<1, kASBatch>), dim3(B, nsplit), dim3(e->ld), shm, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->f_R,
-                         e->succ_idx, e->m_count, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld);
+                         e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld);
     } else {
       const size_t shm = sizeof(double) * 2 * 2 * e->ld;      // <= 64 KB
       hipLaunchKernelGGL((k_build_AS<2, 2>), dim3(B, nsplit), dim3(1024), shm, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->f_R,
-                         e->succ_idx, e->m_count, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld);
+                         e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld);
     }
     SL2_HIP(hipGetLastError());
   }
@@ -1311,7 +1314,7 @@ static int launch_update_range(sl2_engine* e) {
     if (rc != SL2_OK) return rc;
   } else if (e->nblk_max <= e->root->panel_from && chol_variant == 1) {
     LaunchScope ls(e, "k_chol_left", true);
-    hipLaunchKernelGGL(k_chol_left, dim3(B), dim3(256), 0, e->stream, e->St, e->LinvT, e->m_count, e->mld, e->nblk_max, 0,
+    hipLaunchKernelGGL(k_chol_left, dim3(B), dim3(256), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, 0,
                        e->nblk_max, (long long*)e->root->chol_trace);
     SL2_HIP(hipGetLastError());
   } else {
@@ -1320,20 +1323,20 @@ static int launch_update_range(sl2_engine* e) {
       for (int J = 0; J < e->nblk_max; ++J) {
         {
           LaunchScope ls(e, "k_chol_diag");
-          hipLaunchKernelGGL(k_chol_diag, dim3(B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_count, e->mld, e->nblk_max, J);
+          hipLaunchKernelGGL(k_chol_diag, dim3(B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, J);
           SL2_HIP(hipGetLastError());
         }
         const int rem = e->nblk_max - 1 - J;
         if (rem > 0) {
           {
             LaunchScope ls(e, "k_chol_panel");
-            hipLaunchKernelGGL(k_chol_panel, dim3(rem, B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_count, e->mld,
+            hipLaunchKernelGGL(k_chol_panel, dim3(rem, B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld,
                                e->nblk_max, J);
             SL2_HIP(hipGetLastError());
           }
           {
             LaunchScope ls(e, "k_chol_trail");
-            hipLaunchKernelGGL(k_chol_trail, dim3(rem * (rem + 1) / 2, B), dim3(64), 0, e->stream, e->St, e->m_count, e->mld, J);
+            hipLaunchKernelGGL(k_chol_trail, dim3(rem * (rem + 1) / 2, B), dim3(64), 0, e->stream, e->St, e->m_gate, e->mld, J);
             SL2_HIP(hipGetLastError());
           }
         }
@@ -1361,7 +1364,7 @@ static int launch_update_range(sl2_engine* e) {
 #ifdef SL2_TESTING
       LaunchScope ls(e, "k_fwdsub", true);
       hipLaunchKernelGGL(k_fwdsub, dim3(xcd_grid(e->ld / 64, B)), dim3(128), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
-                         e->m_count, e->ld, e->mld, e->nblk_max, B);
+                         e->m_gate, e->ld, e->mld, e->nblk_max, B);
       SL2_HIP(hipGetLastError());
 #else
       set_error("launch_update: no substitution kernel for this system size (sl2_create should have padded it)");
@@ -1374,10 +1377,10 @@ static int launch_update_range(sl2_engine* e) {
     const int nt = e->ld / 64;
 #ifdef SL2_CHOL_TRACE   // the stamp buffer is the Cholesky's unless SL2_TRACE_SYRK is set (scripts/syrk_clock.py sets it)
     static const bool trace_syrk = getenv("SL2_TRACE_SYRK") != nullptr;
-    hipLaunchKernelGGL(k_syrk, dim3(xcd_grid(nt * (nt + 1) / 2, B)), dim3(256), 0, e->stream, e->Vt, e->P, e->x, e->m_count,
+    hipLaunchKernelGGL(k_syrk, dim3(xcd_grid(nt * (nt + 1) / 2, B)), dim3(256), 0, e->stream, e->Vt, e->P, e->x, e->m_gate,
                        e->ld, e->mld, B, e->n_slots, e->ppos, trace_syrk ? (long long*)e->root->chol_trace : nullptr);
 #else
-    hipLaunchKernelGGL(k_syrk, dim3(xcd_grid(nt * (nt + 1) / 2, B)), dim3(256), 0, e->stream, e->Vt, e->P, e->x, e->m_count,
+    hipLaunchKernelGGL(k_syrk, dim3(xcd_grid(nt * (nt + 1) / 2, B)), dim3(256), 0, e->stream, e->Vt, e->P, e->x, e->m_gate,
                        e->ld, e->mld, B, e->n_slots, e->ppos);
 #endif
     SL2_HIP(hipGetLastError());

@@ -185,6 +185,7 @@ static int build_groups(sl2_engine* e, int G) {
     g->particles = e->particles + f * e->kpart * e->pcap * kParticleDoubles; g->rand48 = e->rand48 + f; g->prev_r = e->prev_r + f * 3;
     g->me_desc = e->me_desc + f * e->kpart * e->pcap * 8;
     g->pos_err = e->pos_err + f * N; g->pos_err_any = e->pos_err_any + f; g->f_hcol = e->f_hcol + f * N;
+    g->seq_age = e->seq_age + f; g->active = e->active + f; g->sel_gate = e->sel_gate + f; g->m_gate = e->m_gate + f;
     // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
     SL2_HIP(hipMalloc((void**)&g->srch_big, sizeof(int) * kSrchBigInts));
     SL2_HIP(hipMemsetAsync(g->srch_big, 0, sizeof(int) * kSrchBigParts, e->stream));      // (everything but the partial results)
@@ -490,6 +491,9 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
   A(dmalloc(&e->pos_log, B * kTrajCapacity * 3));
   A(dmalloc(&e->pos_count, B));
   A(dmalloc(&e->seq_age, B));
+  A(dmalloc(&e->active, B));
+  A(dmalloc(&e->sel_gate, B));
+  A(dmalloc(&e->m_gate, B));
   A(dmalloc(&e->f_h, B * N * 2));
   A(dmalloc(&e->f_Hx, B * N * 14));
   A(dmalloc(&e->f_Hy, B * N * 6));
@@ -527,6 +531,7 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
   A(dmalloc(&e->prev_r, B * 3));
   A(dmalloc(&e->me_desc, B * (size_t)e->kpart * e->pcap * 8));
 #undef A
+  SL2_HIP(hipMemset(e->active, 1, B));                               // every sequence takes part until sl2_set_active_sequences says otherwise
   SL2_HIP(hipMalloc((void**)&e->slots_max_dev, sizeof(int) * 2));
   SL2_HIP(hipMemset(e->slots_max_dev, 0, sizeof(int) * 2));
   SL2_HIP(hipHostMalloc((void**)&e->slots_mail, 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
@@ -604,7 +609,7 @@ void sl2_destroy(sl2_engine* e) {
                   e->traj, e->traj_count, e->last_r, e->status, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score,
                   e->f_z, e->f_nu, e->sel_idx, e->n_sel, e->n_vis, e->meas_ok, e->meas_score, e->succ_idx, e->f_arow, e->m_count,
                   e->work, e->At, e->Vt, e->St, e->LinvT, e->frames_buf, e->pos_log, e->srch_i, e->srch_d, e->srch_res, e->srch_sel,
-                  e->part_i, e->part_d, e->particles, e->rand48, e->prev_r, e->me_desc, e->score_map, e->me_big_list, e->ps_i, e->ps_d, e->pos_err, e->pos_err_any, e->f_hcol, e->pos_count, e->init_uv, e->f_label, e->next_label, e->seq_age};
+                  e->part_i, e->part_d, e->particles, e->rand48, e->prev_r, e->me_desc, e->score_map, e->me_big_list, e->ps_i, e->ps_d, e->pos_err, e->pos_err_any, e->f_hcol, e->pos_count, e->init_uv, e->f_label, e->next_label, e->seq_age, e->active, e->sel_gate, e->m_gate};
   for (void* p : ptrs) if (p) hipFree(p);
   release_checkpoint_staging(e);
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
@@ -751,6 +756,51 @@ int sl2_add_known_features(sl2_engine* e, int seq0, int nseq, int nfeat, const d
   SL2_HIP(hipGetLastError());
   { int _rc = e->sync_all(); if (_rc != SL2_OK) return _rc; }
   return refresh_slots_exact(e);
+}
+
+// ------------------------------------------------------------------- stepping a subset of the batch
+
+// The host form travels in the launch's own arguments (kActiveChunk sequences a launch, a bit each): the caller's array is read
+// before the call returns whatever kind of memory it is, nothing is staged in a buffer a later call could overwrite while steps
+// are still queued ahead of this one, and nothing waits for the device.
+constexpr int kActiveChunk = 2048;
+struct ActiveBits { unsigned w[kActiveChunk / 32]; };
+__global__ void __launch_bounds__(256) k_set_active_bits(uint8_t* __restrict__ active, ActiveBits bits, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) active[i] = (uint8_t)((bits.w[i >> 5] >> (i & 31)) & 1u);
+}
+__global__ void __launch_bounds__(256) k_set_active_dev(uint8_t* __restrict__ active, const uint8_t* __restrict__ src, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) active[i] = src[i] ? 1 : 0;
+}
+
+int sl2_set_active_sequences(sl2_engine* e, int seq0, int nseq, const uint8_t* active, int on_device) {
+  if (!range_ok(e, seq0, nseq) || !active) return SL2_ERR_INVALID;
+  SL2_HIP(hipSetDevice(e->device));
+  // on the engine's stream: behind the steps already queued (every stepping call joins the groups' streams back into it), in
+  // front of the next one (which forks from it); outside any captured step - the mask is data a replayed graph reads
+  if (on_device) {
+    hipLaunchKernelGGL(k_set_active_dev, dim3((nseq + 255) / 256), dim3(256), 0, e->stream, e->active + seq0, active, nseq);
+    SL2_HIP(hipGetLastError());
+    return SL2_OK;
+  }
+  for (int c0 = 0; c0 < nseq; c0 += kActiveChunk) {
+    const int cnt = nseq - c0 < kActiveChunk ? nseq - c0 : kActiveChunk;
+    ActiveBits bits;
+    memset(&bits, 0, sizeof(bits));
+    for (int i = 0; i < cnt; ++i) if (active[c0 + i]) bits.w[i >> 5] |= 1u << (i & 31);
+    hipLaunchKernelGGL(k_set_active_bits, dim3((cnt + 255) / 256), dim3(256), 0, e->stream, e->active + seq0 + c0, bits, cnt);
+    SL2_HIP(hipGetLastError());
+  }
+  return SL2_OK;
+}
+
+int sl2_get_active_sequences(sl2_engine* e, int seq0, int nseq, uint8_t* active) {
+  if (!range_ok(e, seq0, nseq) || !active) return SL2_ERR_INVALID;
+  SL2_HIP(hipSetDevice(e->device));
+  { int _rc = e->sync_all(); if (_rc != SL2_OK) return _rc; }
+  SL2_HIP(hipMemcpy(active, e->active + seq0, (size_t)nseq, hipMemcpyDeviceToHost));
+  return SL2_OK;
 }
 
 // ------------------------------------------------------------------- stepping
@@ -1461,6 +1511,8 @@ int sl2_get_step_work(sl2_engine* e, double* out_caller, int capacity) {
   { int _rc = e->sync_all(); if (_rc != SL2_OK) return _rc; }
   std::vector<double> w((size_t)e->B * kWorkDoubles);
   std::vector<int> mc(e->B), flags((size_t)e->B * e->N), slots(e->B);
+  std::vector<uint8_t> act(e->B);
+  SL2_HIP(hipMemcpy(act.data(), e->active, (size_t)e->B, hipMemcpyDeviceToHost));
   SL2_HIP(hipMemcpy(w.data(), e->work, sizeof(double) * w.size(), hipMemcpyDeviceToHost));
   SL2_HIP(hipMemcpy(mc.data(), e->m_count, sizeof(int) * e->B, hipMemcpyDeviceToHost));
   SL2_HIP(hipMemcpy(flags.data(), e->f_flags, sizeof(int) * flags.size(), hipMemcpyDeviceToHost));
@@ -1468,6 +1520,7 @@ int sl2_get_step_work(sl2_engine* e, double* out_caller, int capacity) {
   for (int k = 0; k < SL2_STEP_WORK_COUNT; ++k) out[k] = 0.0;
   const double frame_bytes = (double)e->cam.width * e->cam.height;
   for (int b = 0; b < e->B; ++b) {
+    if (!act[b]) continue;                  // a paused sequence did no work in the step (its counters are those of the last frame it saw)
     const double win = w[(size_t)b * kWorkDoubles + 0];
     out[0] += win < frame_bytes ? win : frame_bytes;
     out[1] += w[(size_t)b * kWorkDoubles + 1];

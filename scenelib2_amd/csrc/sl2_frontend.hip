@@ -13,7 +13,8 @@ namespace sl2 {
 
 __global__ void __launch_bounds__(256) k_predict(double* __restrict__ x, double* __restrict__ P, const int* __restrict__ n_slots,
                                                  double* __restrict__ prev_r, const int* __restrict__ part_i, int pend, int ld,
-                                                 double dt) {
+                                                 double dt, const uint8_t* __restrict__ active) {
+  if (!active[blockIdx.x]) return;           // a paused sequence (uniform)
   predict_body(blockIdx.x, x, P, n_slots, prev_r, part_i, pend, ld, dt);
 }
 
@@ -23,7 +24,8 @@ __global__ void __launch_bounds__(64) k_feature_prediction(const double* __restr
                                                            double* __restrict__ f_Hx, double* __restrict__ f_Hy,
                                                            double* __restrict__ f_R, double* __restrict__ f_S,
                                                            double* __restrict__ f_score, int* __restrict__ srch_i, double* __restrict__ srch_d,
-                                                           CameraParams cam, int N, int ld) {
+                                                           CameraParams cam, int N, int ld, const uint8_t* __restrict__ active) {
+  if (!active[blockIdx.y]) return;           // a paused sequence (uniform)
   feature_prediction_body(blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, x, P, xp_org, f_flags, n_slots, f_h, f_Hx, f_Hy, f_R, f_S,
                           f_score, srch_i, srch_d, cam, N, ld);
 }
@@ -33,10 +35,12 @@ __global__ void __launch_bounds__(256) k_select(const double* __restrict__ f_sco
                                                 int* __restrict__ sel_idx, int* __restrict__ n_sel, int* __restrict__ n_vis,
                                                 double* __restrict__ last_r, const int* __restrict__ srch_i,
                                                 const double* __restrict__ srch_d, int* __restrict__ srch_sel, int N,
-                                                int n_want, int* __restrict__ srch_big, int split_bands) {
+                                                int n_want, int* __restrict__ srch_big, int split_bands,
+                                                const uint8_t* __restrict__ active, int* __restrict__ sel_gate) {
   extern __shared__ double s_dyn[];
+  if (!active[blockIdx.x]) { select_paused(blockIdx.x, sel_gate); return; }
   select_body(blockIdx.x, f_score, f_flags, n_slots, xp_org, sel_idx, n_sel, n_vis, last_r, srch_i, srch_d, srch_sel, N, n_want,
-              srch_big, split_bands, s_dyn);
+              srch_big, split_bands, s_dyn, sel_gate);
 }
 
 __global__ void __launch_bounds__(128) k_finalize(double* __restrict__ x, double* __restrict__ P, int* __restrict__ f_flags,
@@ -47,8 +51,10 @@ __global__ void __launch_bounds__(128) k_finalize(double* __restrict__ x, double
                                                   int* __restrict__ status, double* __restrict__ pos_log, int* __restrict__ pos_count, int N, int ld,
                                                   int min_attempts, double match_fraction, int save_trajectory,
                                                   const int* __restrict__ part_i, int pend, int* __restrict__ slots_max,
-                                                  unsigned long long* __restrict__ slots_mail, int publish) {
+                                                  unsigned long long* __restrict__ slots_mail, int publish,
+                                                  const uint8_t* __restrict__ active, int* __restrict__ seq_age) {
   extern __shared__ int s_del[];
+  if (!active[blockIdx.x]) { finalize_paused(blockIdx.x, x, n_slots, pos_log, pos_count, seq_age, ld, slots_max, slots_mail, publish); return; }
   finalize_body(blockIdx.x, x, P, f_flags, n_slots, attempted, successful, m_count, n_sel, traj, traj_count, last_r, status, pos_log,
                 pos_count, N, ld, min_attempts, match_fraction, save_trajectory, part_i, pend, s_del, slots_max, slots_mail, publish);
 }
@@ -64,7 +70,7 @@ namespace sl2 {
 int launch_predict(sl2_engine* e) {
   LaunchScope ls(e, "k_predict");
   hipLaunchKernelGGL(k_predict, dim3(e->B), dim3(256), 0, e->stream, e->x, e->P, e->n_slots, e->prev_r, e->part_i, e->ppos + 6 * e->kpart, e->ld,
-                     e->prm.delta_t);
+                     e->prm.delta_t, e->active);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -73,7 +79,7 @@ int launch_feature_prediction(sl2_engine* e) {
   LaunchScope ls(e, "k_feature_prediction");
   dim3 grid((e->N + 63) / 64, e->B);
   hipLaunchKernelGGL(k_feature_prediction, grid, dim3(64), 0, e->stream, e->x, e->P, e->xp_org, e->f_flags, e->n_slots,
-                     e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score, e->srch_i, e->srch_d, e->cam, e->N, e->ld);
+                     e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score, e->srch_i, e->srch_d, e->cam, e->N, e->ld, e->active);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -84,7 +90,7 @@ int launch_select(sl2_engine* e, int n) {
   const size_t shm = (size_t)e->N * (sizeof(double) + 3 * sizeof(int));
   hipLaunchKernelGGL(k_select, dim3(e->B), dim3(256), shm, e->stream, e->f_score, e->f_flags, e->n_slots, e->xp_org,
                      e->sel_idx, e->n_sel, e->n_vis, e->last_r, e->srch_i, e->srch_d, e->srch_sel, e->N, n, e->srch_big,
-                     (e->srch_big && e->root->search_variant == 1) ? e->root->search_split : 0);
+                     (e->srch_big && e->root->search_variant == 1) ? e->root->search_split : 0, e->active, e->sel_gate);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -96,7 +102,7 @@ int launch_finalize(sl2_engine* e, int save_trajectory) {
                      e->successful, e->m_count, e->n_sel, e->traj, e->traj_count, e->last_r, e->status, e->pos_log,
                      e->pos_count, e->N, e->ld, e->prm.minimum_attempted_measurements_of_feature,
                      e->prm.successful_match_fraction, save_trajectory, e->part_i, e->ppos + 6 * e->kpart, e->root->slots_max_dev,
-                     e->root->slots_mail_dev, e->group_first == 0 ? 1 : 0);
+                     e->root->slots_mail_dev, e->group_first == 0 ? 1 : 0, e->active, e->seq_age);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }

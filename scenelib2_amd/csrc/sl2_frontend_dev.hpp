@@ -158,7 +158,8 @@ __device__ __forceinline__ void select_body(const int b, const double* __restric
                                                 int* __restrict__ sel_idx, int* __restrict__ n_sel, int* __restrict__ n_vis,
                                                 double* __restrict__ last_r, const int* __restrict__ srch_i,
                                                 const double* __restrict__ srch_d, int* __restrict__ srch_sel, int N,
-                                                int n_want, int* __restrict__ srch_big, int split_bands, double* s_dyn) {
+                                                int n_want, int* __restrict__ srch_big, int split_bands, double* s_dyn,
+                                                int* __restrict__ sel_gate) {
   double* s_score = s_dyn;                 // [N]
   int* s_vis = (int*)(s_dyn + N);          // [N]
   int* s_nu = s_vis + N;                   // [N] rank accumulator
@@ -285,9 +286,41 @@ __device__ __forceinline__ void select_body(const int b, const double* __restric
   FTR(1, 3);
   if (tid == 0) {
     n_sel[b] = limit;
+    sel_gate[b] = limit;                     // what the search kernels take for n_sel (0 for a paused sequence: select_paused)
     n_vis[b] = s_nvis;
     if (s_last >= 0)
       for (int k = 0; k < 3; ++k) last_r[b * 3 + k] = xp_org[((size_t)b * N + s_last) * 8 + k];
+  }
+}
+
+// A PAUSED sequence (sl2_set_active_sequences: active[b] == 0) is left exactly as it was by every stage of a step.  The
+// workgroup that owns it tests the byte - b is uniform, so the test is a scalar one - before any barrier or LDS use and
+// leaves; what little a paused sequence still owes the step is in the two bodies below (one thread each).
+//   select_paused     the per-step gate of the search kernels: no position of this sequence is searched, nothing goes on
+//                     the list of large windows, the stale records of its last frame are not looked at
+//   finalize_paused   the engine's step clock is shared: pos_count advances (the mailboxes and the host compare it with
+//                     steps_done), seq_age drops by one so that the sequence's own step count stands still, the position log
+//                     repeats the unchanged xv(0..2), and the map-size mailbox works as for any other sequence
+__device__ __forceinline__ void select_paused(const int b, int* __restrict__ sel_gate) {
+  if (threadIdx.x == 0) sel_gate[b] = 0;
+}
+__device__ __forceinline__ void finalize_paused(const int b, const double* __restrict__ x, const int* __restrict__ n_slots,
+                                                double* __restrict__ pos_log, int* __restrict__ pos_count, int* __restrict__ seq_age,
+                                                int ld, int* __restrict__ slots_max, unsigned long long* __restrict__ slots_mail,
+                                                int publish) {
+  if (threadIdx.x != 0) return;
+  const int pc = pos_count[b], ns = n_slots[b];
+  pos_count[b] = pc + 1;
+  seq_age[b] -= 1;
+  const int log_slot = pc % kTrajCapacity;
+  for (int k = 0; k < 3; ++k) pos_log[((size_t)b * kTrajCapacity + log_slot) * 3 + k] = x[(size_t)b * ld + k];
+  if (slots_max) {                           // (as in finalize_body)
+    if (ns > __hip_atomic_load(&slots_max[pc & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&slots_max[pc & 1], ns);
+    if (publish && b == 0) {
+      const int prev = __hip_atomic_load(&slots_max[(pc + 1) & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&slots_max[(pc + 1) & 1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(slots_mail, ((unsigned long long)(unsigned)pc << 32) | (unsigned)prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
 }
 

@@ -260,6 +260,11 @@ struct sl2_ingest {
   int device = 0, nseq = 0, width = 0, height = 0, depth = 0;
   std::vector<std::vector<std::string>> files;   // per sequence, sorted
   int n_frames = 0;                               // min over sequences
+  // Sequences of unequal length (sl2_ingest_next_ragged): the grabber serves ONE of the two next-calls, decided by the first one
+  // made.  Up to the end of the shortest sequence both hand out the same batches, so the producer runs ahead as always; beyond
+  // it, it goes on only once the ragged call has been made, and decodes the sequences that still have a frame.
+  int n_longest = 0;                              // max over sequences
+  int mode = 0;                                   // 0 = not decided, 1 = sl2_ingest_next, 2 = sl2_ingest_next_ragged (guarded by mu)
   // ring of `depth` pinned host batches [nseq][W*H]
   std::vector<uint8_t*> host;
   std::vector<int> state;        // 0 free, 1 decoded, 2 in flight (uploaded, waiting for its event)
@@ -293,14 +298,15 @@ struct sl2_ingest {
   void run() {
     const size_t fb = (size_t)width * height;
     std::vector<uint8_t> px;
-    for (int k = 0; k < n_frames; ++k) {
+    for (int k = 0; k < n_longest; ++k) {
       const int slot = k % depth;
       {
         std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || state[slot] == 0; });
-        if (stop) return;
+        cv.wait(lk, [&] { return stop || (state[slot] == 0 && (k < n_frames || mode != 0)); });
+        if (stop || (k >= n_frames && mode != 2)) return;
       }
       for (int s = 0; s < nseq; ++s) {
+        if (k >= (int)files[s].size()) continue;           // (ragged: this sequence has ended; its part of the batch is unspecified)
         int w = 0, h = 0;
         bool ok = false;
         try { ok = sl2::read_image(files[s][k], px, &w, &h); } catch (const std::exception&) { ok = false; }
@@ -438,6 +444,7 @@ int sl2_ingest_open(const char* const* dirs, int nseq, int width, int height, in
     }
     const int n = (int)g->files[s].size();
     nmin = (nmin < 0 || n < nmin) ? n : nmin;
+    g->n_longest = n > g->n_longest ? n : g->n_longest;
   }
   g->n_frames = nmin;
   const size_t batch = (size_t)nseq * width * height;
@@ -556,10 +563,15 @@ static int next_zero_copy(sl2_ingest* g, hipStream_t st, const uint8_t** d_frame
   return SL2_OK;
 }
 
-int sl2_ingest_next(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_t* seq_stride) {
+// Both next-calls: `mode` = which one (1 / 2), `limit` = the frames it hands out in all.
+static int ingest_next(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_t* seq_stride, int mode, int limit) {
   using namespace sl2;
-  if (!g || !d_frames || !seq_stride) return SL2_ERR_INVALID;
-  if (g->consumed >= g->n_frames) return SL2_ERR_CAPACITY;     // end of the shortest sequence
+  {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (g->mode != 0 && g->mode != mode) { set_error("sl2_ingest_next and sl2_ingest_next_ragged cannot be mixed on one grabber"); return SL2_ERR_INVALID; }
+    if (g->mode == 0) { g->mode = mode; g->cv.notify_all(); }
+  }
+  if (g->consumed >= limit) return SL2_ERR_CAPACITY;           // end of the shortest sequence (ragged: of the longest)
   hipStream_t st = (hipStream_t)stream;
   if ((size_t)g->nseq * g->width * g->height <= g->zc_max && g->depth >= 4) {
     *seq_stride = (size_t)g->width * g->height;
@@ -577,7 +589,7 @@ int sl2_ingest_next(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_
   // ONE AHEAD: frame k + 1 goes to the other buffer, which the caller's work on frame k - 1 read - everything queued on the
   // caller's stream so far.  Behind that point the buffer may be overwritten; the caller's work on frame k, queued after this
   // call returns, runs beside the copy.
-  if (k + 1 < g->n_frames) {
+  if (k + 1 < limit) {
     if (g->handed_out[b ^ 1]) SL2_HIP(hipEventRecord(g->reusable[b ^ 1], st));
     const int rc = issue_copy(g, k + 1, false);
     if (rc < 0) { /* reported by the call whose frame it is */ (void)hipGetLastError(); }
@@ -596,6 +608,26 @@ int sl2_ingest_next(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_
   }
   *d_frames = g->dev[b];
   *seq_stride = (size_t)g->width * g->height;
+  return SL2_OK;
+}
+
+int sl2_ingest_next(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_t* seq_stride) {
+  if (!g || !d_frames || !seq_stride) return SL2_ERR_INVALID;
+  return ingest_next(g, stream, d_frames, seq_stride, 1, g->n_frames);
+}
+
+int sl2_ingest_frame_counts(const sl2_ingest* g, int32_t* counts, int capacity) {
+  if (!g || !counts || capacity < 0) return -1;
+  for (int s = 0; s < g->nseq && s < capacity; ++s) counts[s] = (int32_t)g->files[s].size();
+  return g->nseq;
+}
+
+int sl2_ingest_next_ragged(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_t* seq_stride, uint8_t* have) {
+  if (!g || !d_frames || !seq_stride || !have) return SL2_ERR_INVALID;
+  const int k = g->consumed;                        // (the frame this call hands out, if it hands one out)
+  const int rc = ingest_next(g, stream, d_frames, seq_stride, 2, g->n_longest);
+  if (rc != SL2_OK) return rc;
+  for (int s = 0; s < g->nseq; ++s) have[s] = k < (int)g->files[s].size() ? 1 : 0;
   return SL2_OK;
 }
 

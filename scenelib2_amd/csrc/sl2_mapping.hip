@@ -149,8 +149,9 @@ __global__ void __launch_bounds__(kDetThreads) k_map_find(const double* __restri
                                                           double* __restrict__ part_d, unsigned long long* __restrict__ rand48,
                                                           double* __restrict__ last_r, int* __restrict__ status,
                                                           const uint8_t* __restrict__ frames, size_t seq_stride, CameraParams cam,
-                                                          MapParams mp, int N, int ld) {
+                                                          MapParams mp, int N, int ld, const uint8_t* __restrict__ active) {
   extern __shared__ double s_uv[];
+  if (active && !active[blockIdx.x]) return;          // a paused sequence of a step (uniform; the "initialise feature" calls pass no mask)
   region_body(x, f_flags, n_slots, n_vis, prev_r, part_i, rand48, last_r, status, cam, mp, N, ld, s_uv);
   const int b = blockIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
@@ -171,6 +172,7 @@ struct MapArrays {
   double* part_d; int* ps_i; double* ps_d; int *pos_err, *pos_err_any;
   double *particles, *last_r, *traj; int* traj_count; const int* pos_count; unsigned long long* parts_mail;
   int N, ld, ppos0;
+  const uint8_t* active;      // the step's mask (sl2_set_active_sequences); nullptr: the caller's explicit act on every sequence
 };
 
 __device__ __forceinline__ void create_body(const MapArrays& a, const CameraParams& cam, const MapParams& mp) {
@@ -186,6 +188,7 @@ __device__ __forceinline__ void create_body(const MapArrays& a, const CameraPara
   const int b = blockIdx.x, lane = threadIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
   double* pd = part_d + (size_t)b * kPartDoubles;
+  if (a.active && !a.active[b]) return;        // a paused sequence (uniform): its flags of the last frame it saw are not acted on again
   if (!pi[kPartRegionValid]) return;
   if (!(pd[2] > 20000)) return;        // SUITABLE_PATCH_SCORE_THRESHOLD (:837, 850-858)
   // the partial slot this feature takes: the first free one (k_map_find / k_map_manual checked that there is one)
@@ -337,10 +340,12 @@ __global__ void __launch_bounds__(THREADS) k_map_particles(const double* __restr
                                                                  int* __restrict__ ps_i, double* __restrict__ particles,
                                                                  int* __restrict__ me_desc, double* __restrict__ last_r,
                                                                  int* __restrict__ me_big_count, int* __restrict__ part_i, int clear_region,
-                                                                 CameraParams cam, int ld, int ppos0, int pcap, int kpart) {
+                                                                 CameraParams cam, int ld, int ppos0, int pcap, int kpart,
+                                                                 const uint8_t* __restrict__ active) {
   const int b = blockIdx.x, ks = blockIdx.y, tid = threadIdx.x;       // one workgroup per (sequence, partial slot)
   int* ps = ps_i + ((size_t)b * kpart + ks) * kPsInts;
   if (b == 0 && ks == 0 && tid == 0) *me_big_count = 0;     // the step's list of oversized multi-ellipse searches starts empty
+  if (!active[b]) return;                                   // a paused sequence (uniform): no attempt counted, no particle touched
   if (clear_region && ks == 0 && tid == 0) {                // this step runs without k_map_find (launch_mapping: parts_state 2): its two per-step flags
     part_i[(size_t)b * kPartInts + kPartRegionValid] = 0;
     part_i[(size_t)b * kPartInts + kPartCreated] = 0;
@@ -392,6 +397,7 @@ __global__ void __launch_bounds__(THREADS) k_map_particles(const double* __restr
 struct MeJobsEngine {      // job = sequence * kpart + partial slot
   const uint8_t* frames; size_t seq_stride; const uint8_t* patch_base; const int* ps_i; const int* me_desc; double* particles;
   double* map_base; int N, pcap, width, height, kpart;
+  const uint8_t* active;     // the step's mask: a paused sequence's jobs are not searched and go on no list
   __device__ const int* ps(int j) const { return ps_i + (size_t)j * kPsInts; }
   __device__ const uint8_t* img(int j) const { return frames + (size_t)(j / kpart) * seq_stride; }
   __device__ const uint8_t* patch(int j) const { return patch_base + ((size_t)(j / kpart) * N + ps(j)[kPsLabel]) * kPatchStride; }
@@ -413,6 +419,7 @@ struct MeJobsEngine {      // job = sequence * kpart + partial slot
 __global__ void __launch_bounds__(1024) k_map_me_search(MeJobsEngine J, int* __restrict__ big_list, int* __restrict__ big_count) {
   const int j = blockIdx.x;
   const int* ps = J.ps(j);
+  if (!J.active[j / J.kpart]) return;               // (uniform)
   if (!ps[kPsActive] || !ps[kPsMaking]) return;
   const bool done = me_search_fused_wg(J.img(j), J.width, J.patch(j), J.desc(j), J.n_ell(j), [&](int e) { return J.pu(j, e); },
                                        [&](int e, int flag, int u, int v, double best) { J.emit(j, e, flag, u, v, best); });
@@ -442,6 +449,14 @@ __device__ __forceinline__ void update_body(const MapArrays& a, const MapParams&
   const int N = a.N, ld = a.ld, ppos0 = a.ppos0;
   const int b = blockIdx.x, lane = threadIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
+  if (a.active && !a.active[b]) {
+    // a paused sequence (uniform): nothing of it changes, no trajectory push.  A one-sequence engine still reports - the count its
+    // partial features stand at, under the step index k_finalize has just counted - so that the host's next step takes the same
+    // shortcuts it would have taken (sl2_engine.hip: parts_state_for_step)
+    if (lane == 0 && mp.publish_parts)
+      __hip_atomic_store(parts_mail, ((unsigned long long)(unsigned)pos_count[b] << 32) | (unsigned)pi[kPartCount], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return;
+  }
   double* xb = x + (size_t)b * ld;
   double* Pb = P + (size_t)b * ld * ld;
   const int ns = n_slots[b];
@@ -723,6 +738,7 @@ struct SlotArrays {
   uint8_t* patch;
   int *patch_sums, *f_flags, *attempted, *successful, *f_label, *srch_i, *sel_idx, *succ_idx, *f_arow, *n_sel, *m_count, *n_slots, *ps_i, *pos_err;
   int kpart;
+  const uint8_t* active;     // the mask of a step's launch (nullptr: sl2_add_known_features and the "initialise feature" calls, which ignore it)
 };
 __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, int ld, int ppos, int need) {
   extern __shared__ int s_map[];        // [N] new slot -> old slot, then [N] old slot -> new slot (-1: retired)
@@ -730,6 +746,7 @@ __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, 
   int* s_new = s_map + N;
   __shared__ int s_live;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  if (a.active && !a.active[b]) return;                          // a paused sequence of a step (uniform)
   const int ns = a.n_slots[b];
   if (ns + need <= N) return;                                    // room for what is about to be added: nothing to do
   int* flags = a.f_flags + (size_t)b * N;
@@ -869,7 +886,7 @@ __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, 
   if (tid == 0) a.n_slots[b] = nl;
 }
 
-int launch_compact_slots(sl2_engine* e, int need) {
+int launch_compact_slots(sl2_engine* e, int need, bool honour_mask) {
   if ((size_t)e->ld > 8 * 256) return SL2_OK;                     // (maps beyond 2048 states: slots are not squeezed)
   LaunchScope ls(e, "k_map_compact_slots");
   SlotArrays a;
@@ -877,7 +894,7 @@ int launch_compact_slots(sl2_engine* e, int need) {
   a.f_score = e->f_score; a.f_z = e->f_z; a.f_nu = e->f_nu; a.srch_d = e->srch_d; a.patch = e->patch; a.patch_sums = e->patch_sums;
   a.f_flags = e->f_flags; a.attempted = e->attempted; a.successful = e->successful; a.f_label = e->f_label; a.srch_i = e->srch_i;
   a.sel_idx = e->sel_idx; a.succ_idx = e->succ_idx; a.f_arow = e->f_arow; a.n_sel = e->n_sel; a.m_count = e->m_count; a.n_slots = e->n_slots;
-  a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.kpart = e->kpart;
+  a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.kpart = e->kpart; a.active = honour_mask ? e->active : nullptr;
   hipLaunchKernelGGL(k_map_compact_slots, dim3(e->B), dim3(256), sizeof(int) * 2 * e->N, e->stream, a, e->N, e->ld, e->ppos, need);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
@@ -919,7 +936,7 @@ static MapParams map_params(const sl2_engine* e, int enable_mapping, int save_tr
   return mp;
 }
 
-static MapArrays map_arrays(const sl2_engine* e) {
+static MapArrays map_arrays(const sl2_engine* e, bool honour_mask) {
   MapArrays a;
   a.x = e->x; a.P = e->P; a.frames = e->cur_frames; a.seq_stride = e->cur_stride; a.patch = e->patch; a.patch_sums = e->patch_sums;
   a.xp_org = e->xp_org; a.f_flags = e->f_flags; a.n_slots = e->n_slots; a.attempted = e->attempted; a.successful = e->successful;
@@ -927,20 +944,22 @@ static MapArrays map_arrays(const sl2_engine* e) {
   a.pos_err = e->pos_err; a.pos_err_any = e->pos_err_any; a.particles = e->particles; a.last_r = e->last_r; a.traj = e->traj;
   a.traj_count = e->traj_count; a.pos_count = e->pos_count; a.parts_mail = e->root->parts_mail_dev;
   a.N = e->N; a.ld = e->ld; a.ppos0 = e->ppos;
+  a.active = honour_mask ? e->active : nullptr;
   return a;
 }
 
-static int launch_create(sl2_engine* e, const MapParams& mp) {
+static int launch_create(sl2_engine* e, const MapParams& mp, bool honour_mask) {
   LaunchScope ls(e, "k_map_create");
-  hipLaunchKernelGGL(k_map_create, dim3(e->B), dim3(64), 0, e->stream, map_arrays(e), e->cam, mp);
+  hipLaunchKernelGGL(k_map_create, dim3(e->B), dim3(64), 0, e->stream, map_arrays(e, honour_mask), e->cam, mp);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 
-static int launch_find(sl2_engine* e, const MapParams& mp) {
+static int launch_find(sl2_engine* e, const MapParams& mp, bool honour_mask) {
   LaunchScope ls(e, "k_map_find");
   hipLaunchKernelGGL(k_map_find, dim3(e->B), dim3(kDetThreads), sizeof(double) * 2 * e->N, e->stream, e->x, e->f_flags, e->n_slots, e->n_vis,
-                     e->prev_r, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride, e->cam, mp, e->N, e->ld);
+                     e->prev_r, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride, e->cam, mp, e->N, e->ld,
+                     honour_mask ? e->active : nullptr);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -952,15 +971,15 @@ int launch_manual_init(sl2_engine* e, const int* d_uv) {
   hipLaunchKernelGGL(k_map_manual, dim3((e->B + 63) / 64), dim3(64), 0, e->stream, d_uv, e->n_slots, e->part_i, e->part_d, e->status,
                      e->N, e->cam.width, e->cam.height, e->B, e->kpart);
   SL2_HIP(hipGetLastError());
-  return launch_create(e, mp);
+  return launch_create(e, mp, false);       // (the caller's explicit act: the mask is not consulted)
 }
 
 // InitialiseAutoFeature(frame) = AutoInitialiseFeature(frame, 0) (monoslam.cpp:1535-1541, 823-865): region, detector, creation
 int launch_auto_init(sl2_engine* e) {
   const MapParams mp = map_params(e, 1, 0, 1);
   { int rc = launch_compact_slots(e, 1); if (rc != SL2_OK) return rc; }
-  { int rc = launch_find(e, mp); if (rc != SL2_OK) return rc; }
-  return launch_create(e, mp);
+  { int rc = launch_find(e, mp, false); if (rc != SL2_OK) return rc; }
+  return launch_create(e, mp, false);
 }
 
 int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int slots_bound, int parts_state) {
@@ -991,21 +1010,21 @@ int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int s
   // Retired slots are squeezed out only when a sequence is about to run out of slots; the host's upper bound on the slots in use
   // (sl2_engine.hip: slots_upper_bound) says when none can be: the launch - one of the step's dependent chain, 7 us at one
   // sequence, 0.03 ms at 1024 - is then left out altogether.
-  if (enable_mapping && slots_bound + 1 > e->N) { int rc = launch_compact_slots(e, 1); if (rc != SL2_OK) return rc; }
-  if (!parts_full) { int rc = launch_find(e, mp); if (rc != SL2_OK) return rc; }
+  if (enable_mapping && slots_bound + 1 > e->N) { int rc = launch_compact_slots(e, 1, true); if (rc != SL2_OK) return rc; }
+  if (!parts_full) { int rc = launch_find(e, mp, true); if (rc != SL2_OK) return rc; }
   const size_t shm_particles = sizeof(double) * kParticleDoubles * (size_t)mp.n_particles;
   if (parts_none) {
     LaunchScope ls(e, "k_map_finish");
-    hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e), e->cam, mp);
+    hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), e->cam, mp);
     SL2_HIP(hipGetLastError());
     return SL2_OK;
   }
-  if (!parts_full) { int rc = launch_create(e, mp); if (rc != SL2_OK) return rc; }
+  if (!parts_full) { int rc = launch_create(e, mp, true); if (rc != SL2_OK) return rc; }
   {
     LaunchScope ls(e, "k_map_particles");
     const int pc = e->root->pcap;
 #define SL2_PARTICLES(T) hipLaunchKernelGGL(k_map_particles<T>, dim3(B, mp.kpart), dim3(pc), 0, e->stream, e->x, e->P, e->ps_i, e->particles, \
-                                            e->me_desc, e->last_r, e->me_big_count, e->part_i, parts_full, e->cam, e->ld, e->ppos, pc, mp.kpart)
+                                            e->me_desc, e->last_r, e->me_big_count, e->part_i, parts_full, e->cam, e->ld, e->ppos, pc, mp.kpart, e->active)
     if (pc <= 128) SL2_PARTICLES(128);
     else if (pc <= 256) SL2_PARTICLES(256);
     else if (pc <= 512) SL2_PARTICLES(512);
@@ -1017,7 +1036,7 @@ int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int s
     MeJobsEngine J;
     J.frames = e->cur_frames; J.seq_stride = e->cur_stride; J.patch_base = e->patch; J.ps_i = e->ps_i; J.me_desc = e->me_desc;
     J.particles = e->particles; J.map_base = e->score_map; J.N = e->N; J.pcap = e->root->pcap;
-    J.width = W; J.height = H; J.kpart = mp.kpart;
+    J.width = W; J.height = H; J.kpart = mp.kpart; J.active = e->active;
     {
       LaunchScope ls(e, "k_map_me_search");
       hipLaunchKernelGGL(k_map_me_search, dim3(B * mp.kpart), dim3(1024), 0, e->stream, J, e->me_big_list, e->me_big_count);
@@ -1031,7 +1050,7 @@ int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int s
   }
   {
     LaunchScope ls(e, "k_map_update");
-    hipLaunchKernelGGL(k_map_update, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e), mp);
+    hipLaunchKernelGGL(k_map_update, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), mp);
     SL2_HIP(hipGetLastError());
   }
   return SL2_OK;

@@ -6,6 +6,21 @@
 
 namespace sl2 {
 
+// What the scoring stage still does for a PAUSED sequence (sl2_set_active_sequences): the update chain's gate is shut - every
+// kernel of the update takes its row count from m_gate and leaves on 0, so x and P of the sequence are not touched while
+// m_count keeps last frame's value for the accessors - and the first sequence of a group returns the step's list of large
+// windows to zero as it always does (the list belongs to the group, not to the sequence).
+__device__ __forceinline__ void search_score_paused(const int b, int* __restrict__ srch_big, int* __restrict__ m_gate) {
+  const int tid = threadIdx.x;
+  if (b == 0 && srch_big) {
+    const int nunits_done = min(srch_big[0], kSrchBigUnits), nshared_done = srch_big[3];
+    for (int i = tid; i < nunits_done; i += (int)blockDim.x) srch_big[kSrchBigDone + i] = 0;
+    __syncthreads();                                              // (every thread has read the counters)
+    if (tid == 0) { srch_big[1] = nshared_done; srch_big[0] = 0; srch_big[2] = 0; srch_big[3] = 0; }
+  }
+  if (tid == 0) m_gate[b] = 0;
+}
+
 // One workgroup per sequence, one thread per selected position.  Besides the deferred FP64 scores and the reference's
 // bookkeeping it compacts the successful measurements (succ_idx / m_count, what the EKF update reads: see the comment at
 // the compaction) and leaves the step's work counters - a launch
@@ -23,7 +38,7 @@ __device__ __forceinline__ void search_score_body(const int b, const int* __rest
                                                        const int* __restrict__ pos_err, const int* __restrict__ pos_err_any,
                                                        int* __restrict__ f_hcol, const int* __restrict__ ps_i, int kpart, int ppos0,
                                                        int N, int* __restrict__ srch_big, int* __restrict__ status, int* s_flag,
-                                                       double* s_ext = nullptr) {
+                                                       int* __restrict__ m_gate, double* s_ext = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = (int)blockDim.x >> 6;
   // s_flag: [N + 8] successful measurement of slot i in this frame (dynamic LDS of the caller)
   __shared__ int s_wcnt[16];
@@ -108,7 +123,7 @@ __device__ __forceinline__ void search_score_body(const int b, const int* __rest
     base += total;
     __syncthreads();
   }
-  if (tid == 0) m_count[b] = base;
+  if (tid == 0) { m_count[b] = base; m_gate[b] = base; }        // m_gate: what the update chain takes for m_count (search_score_paused)
   for (int off = 32; off > 0; off >>= 1) {
     w_win += __shfl_xor(w_win, off, 64); w_n += __shfl_xor(w_n, off, 64);
     w_cand += __shfl_xor(w_cand, off, 64); w_fb += __shfl_xor(w_fb, off, 64); w_tiles += __shfl_xor(w_tiles, off, 64);

@@ -1023,11 +1023,13 @@ __global__ void __launch_bounds__(1024) k_search_score(const int* __restrict__ s
                                                        int* __restrict__ m_count, const int* __restrict__ n_slots,
                                                        const int* __restrict__ pos_err, const int* __restrict__ pos_err_any,
                                                        int* __restrict__ f_hcol, const int* __restrict__ ps_i, int kpart, int ppos0,
-                                                       int N, int* __restrict__ srch_big, int* __restrict__ status) {
+                                                       int N, int* __restrict__ srch_big, int* __restrict__ status,
+                                                       const uint8_t* __restrict__ active, int* __restrict__ m_gate) {
   extern __shared__ int s_flag[];
+  if (!active[blockIdx.x]) { search_score_paused(blockIdx.x, srch_big, m_gate); return; }      // a paused sequence (uniform)
   search_score_body(blockIdx.x, srch_res, srch_i, patch, f_h, sel_idx, n_sel, f_flags, f_z, f_nu, attempted, successful, meas_ok,
                     meas_score, work, succ_idx, f_arow, m_count, n_slots, pos_err, pos_err_any, f_hcol, ps_i, kpart, ppos0, N,
-                    srch_big, status, s_flag);
+                    srch_big, status, s_flag, m_gate);
 }
 
 // Stateless batch kernel (C-ABI seam S1): grid (count), one wave per search.  VARIANT 0 = exact, 1 = matrix-core walk.
@@ -1073,7 +1075,7 @@ int launch_search_kernel(sl2_engine* e) {
     if (e->root->search_variant == 0) {
       LaunchScope ls(e, "k_search_exact", true);
       hipLaunchKernelGGL(k_search_exact, dim3(xcd_grid(e->nsel_max, e->B)), dim3(64), 0, e->stream, e->cur_frames, e->cur_stride,
-                         e->cam.width, e->patch, e->srch_i, e->srch_d, e->sel_idx, e->n_sel, e->srch_res, e->meas_score, e->N,
+                         e->cam.width, e->patch, e->srch_i, e->srch_d, e->sel_idx, e->sel_gate, e->srch_res, e->meas_score, e->N,
                          e->nsel_max, e->B);
     } else {
       LaunchScope ls(e, "k_search_mfma", true);
@@ -1094,7 +1096,7 @@ int launch_search_kernel(sl2_engine* e) {
       int helpers = xcd_grid(nchunks, e->B) / 4;
       helpers = helpers < 128 ? 128 : (helpers > kSearchBigWaves ? kSearchBigWaves : helpers);
       hipLaunchKernelGGL(k_search_mfma, dim3(xcd_grid(nchunks, e->B) + (shared ? helpers : 0)), dim3(64), (size_t)e->root->search_lds_pad, e->stream, e->cur_frames, e->cur_stride,
-                         e->cam.width, e->cam.width * e->cam.height, e->patch, e->srch_sel, e->n_sel, e->srch_res, e->meas_score,
+                         e->cam.width, e->cam.width * e->cam.height, e->patch, e->srch_sel, e->sel_gate, e->srch_res, e->meas_score,
                          e->N, nchunks, e->B, chunk, shared ? e->srch_big : nullptr);
     }
     SL2_HIP(hipGetLastError());
@@ -1116,7 +1118,7 @@ int launch_search_score(sl2_engine* e) {
     if (e->root->score_threads > 0) threads = e->root->score_threads;     // experiments (SL2_SCORE_THREADS)
     hipLaunchKernelGGL(k_search_score, dim3(e->B), dim3(threads), sizeof(int) * (e->N + 8), e->stream, e->srch_res, e->srch_i, e->patch, e->f_h, e->sel_idx,
                        e->n_sel, e->f_flags, e->f_z, e->f_nu, e->attempted, e->successful, e->meas_ok, e->meas_score, e->work,
-                       e->succ_idx, e->f_arow, e->m_count, e->n_slots, e->pos_err, e->pos_err_any, e->f_hcol, e->ps_i, e->kpart, e->ppos, e->N, e->srch_big, e->status);
+                       e->succ_idx, e->f_arow, e->m_count, e->n_slots, e->pos_err, e->pos_err_any, e->f_hcol, e->ps_i, e->kpart, e->ppos, e->N, e->srch_big, e->status, e->active, e->m_gate);
     SL2_HIP(hipGetLastError());
   }
   return SL2_OK;

@@ -40,9 +40,11 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
     double* __restrict__ f_Hy, double* __restrict__ f_R, double* __restrict__ f_S, double* __restrict__ f_score,
     int* __restrict__ srch_i, double* __restrict__ srch_d, CameraParams cam, int N,
     int* __restrict__ sel_idx, int* __restrict__ n_sel, int* __restrict__ n_vis, double* __restrict__ last_r,
-    int* __restrict__ srch_sel, int n_want, int* __restrict__ srch_big, int split_bands) {
+    int* __restrict__ srch_sel, int n_want, int* __restrict__ srch_big, int split_bands,
+    const uint8_t* __restrict__ active, int* __restrict__ sel_gate) {
   extern __shared__ double s_dyn[];
   const int b = blockIdx.x;
+  if (!active[b]) { select_paused(b, sel_gate); return; }      // a paused sequence (uniform): nothing predicted, nothing selected
   SST(2, 0);
   predict_body(b, x, P, n_slots, prev_r, part_i, pend, ld, dt);
   __syncthreads();                                    // x and P of this sequence: written above, read below (same workgroup)
@@ -52,7 +54,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
   __syncthreads();
   SST(2, 2);
   select_body(b, f_score, f_flags, n_slots, xp_org, sel_idx, n_sel, n_vis, last_r, srch_i, srch_d, srch_sel, N, n_want, srch_big,
-              split_bands, s_dyn);
+              split_bands, s_dyn, sel_gate);
   SST(2, 3);
 }
 
@@ -265,9 +267,15 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
     const double* __restrict__ f_R, const int* __restrict__ part_i, int pend, int ld,
     double* __restrict__ traj, int* __restrict__ traj_count, const double* __restrict__ last_r, double* __restrict__ pos_log,
     int* __restrict__ pos_count, int min_attempts, double match_fraction, int save_trajectory, int* __restrict__ slots_max,
-    unsigned long long* __restrict__ slots_mail, int publish, unsigned lds_bytes) {
+    unsigned long long* __restrict__ slots_mail, int publish, unsigned lds_bytes,
+    const uint8_t* __restrict__ active, int* __restrict__ m_gate, int* __restrict__ seq_age) {
   extern __shared__ double s_dynd[];                  // phase by phase: [N + 8] ints, [32][128] doubles, [2 N] ints
   const int b = blockIdx.x;
+  if (!active[b]) {                                   // a paused sequence (uniform): the group's list of large windows and the step clock only
+    search_score_paused(b, srch_big, m_gate);
+    finalize_paused(b, x, n_slots, pos_log, pos_count, seq_age, ld, slots_max, slots_mail, publish);
+    return;
+  }
   SST(3, 0);
   // the bookkeeping stages' scratch sits behind their index arrays in the dynamic region (launch_small_back sizes it): with it
   // among the statics the kernel needed 56.4 KB at W = 128 - two workgroups per CU; 53.0 KB: three
@@ -275,7 +283,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
   double* const s_ext_final = s_dynd + (size_t)N;
   search_score_body<true>(b, srch_res, srch_i, patch, f_h, sel_idx, n_sel, f_flags, f_z, f_nu, attempted, successful, meas_ok, meas_score,
                           work, succ_idx, f_arow, m_count, n_slots, pos_err, pos_err_any, f_hcol, ps_i, kpart, ppos0, N, srch_big, status,
-                          (int*)s_dynd, s_ext_score);
+                          (int*)s_dynd, m_gate, s_ext_score);
   __syncthreads();
   SST(3, 1);
   small_update_body(b, x, P, f_Hx, f_Hy, f_nu, f_R, succ_idx, m_count, n_slots, part_i, ppos0, pend, pos_err_any, f_hcol, N, ld, lds_bytes,
@@ -319,7 +327,7 @@ int launch_small_front(sl2_engine* e, int n) {
   hipLaunchKernelGGL(k_small_front, dim3(e->B), dim3(kSmallThreads), shm, e->stream, e->x, e->P, e->n_slots, e->prev_r, e->part_i,
                      e->ppos + 6 * e->kpart, e->ld, e->prm.delta_t, e->xp_org, e->f_flags, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S,
                      e->f_score, e->srch_i, e->srch_d, e->cam, e->N, e->sel_idx, e->n_sel, e->n_vis, e->last_r, e->srch_sel, n,
-                     e->srch_big, (e->srch_big && e->root->search_variant == 1) ? e->root->search_split : 0);
+                     e->srch_big, (e->srch_big && e->root->search_variant == 1) ? e->root->search_split : 0, e->active, e->sel_gate);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -337,7 +345,7 @@ int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound) {
                      e->N, e->srch_big, e->status, e->x, e->P, e->f_Hx, e->f_Hy, e->f_R, e->part_i, e->ppos + 6 * e->kpart, e->ld,
                      e->traj, e->traj_count, e->last_r, e->pos_log, e->pos_count, e->prm.minimum_attempted_measurements_of_feature,
                      e->prm.successful_match_fraction, save_trajectory, e->root->slots_max_dev, e->root->slots_mail_dev,
-                     e->group_first == 0 ? 1 : 0, (unsigned)shm);
+                     e->group_first == 0 ? 1 : 0, (unsigned)shm, e->active, e->m_gate, e->seq_age);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }

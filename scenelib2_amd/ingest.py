@@ -119,6 +119,10 @@ class FrameIngest:
         self.h = _lib.vp()
         _lib.check(self.L.sl2_ingest_open(arr, len(directories), width, height, device, depth, C.byref(self.h)))
         self.frame_count = self.L.sl2_ingest_frame_count(self.h)
+        self.nseq = len(directories)
+        counts = np.zeros(self.nseq, dtype=np.int32)
+        self.L.sl2_ingest_frame_counts(self.h, _lib.ip(counts), self.nseq)
+        self.frame_counts = counts            # frames per sequence (frame_count is their minimum)
 
     def set_zero_copy(self, max_batch_bytes):
         """Batches of at most this many bytes are handed out in place (pinned host memory read by the device); 0 = never."""
@@ -129,6 +133,16 @@ class FrameIngest:
         stride = C.c_size_t(0)
         _lib.check(self.L.sl2_ingest_next(self.h, _lib.vp(stream) if stream else None, C.byref(ptr), C.byref(stride)))
         return ptr.value, stride.value
+
+    def next_ragged(self, stream=None):
+        """Sequences of unequal length: (device pointer, stride, have) until the LONGEST sequence ends; have[s] = 1 where
+        sequence s still had a frame - feed it to Engine.set_active before the step.  Not to be mixed with next()."""
+        ptr = _lib.vp()
+        stride = C.c_size_t(0)
+        have = np.zeros(self.nseq, dtype=np.uint8)
+        _lib.check(self.L.sl2_ingest_next_ragged(self.h, _lib.vp(stream) if stream else None, C.byref(ptr), C.byref(stride),
+                                                 _lib.u8p(have)))
+        return ptr.value, stride.value, have
 
     def close(self):
         if self.h:

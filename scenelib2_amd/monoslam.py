@@ -93,6 +93,24 @@ class Engine:
         if keep is not None:
             self.synchronize()  # host buffer must outlive the async H2D copy
 
+    def set_active(self, mask, seq0=0, on_device=False):
+        """Which sequences take part in the steps issued from now on (sl2_set_active_sequences): mask[i] != 0 = sequence
+        seq0 + i does.  A paused sequence is left exactly as it was by every step.  mask: array-like of len <= batch - seq0
+        (consumed before the call returns), or with on_device=True a (device pointer, count) pair.  Never synchronises."""
+        if on_device:
+            ptr, n = mask
+            self._ck(self.L.sl2_set_active_sequences(self.h, int(seq0), int(n), C.cast(_lib.vp(int(ptr)), _lib.c_u8p), 1))
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        self._ck(self.L.sl2_set_active_sequences(self.h, int(seq0), int(m.size), _lib.u8p(m), 0))
+
+    def active(self, seq0=0, nseq=None):
+        """The mask as the steps queued so far leave it: uint8 [nseq] (sl2_get_active_sequences; synchronises)."""
+        nseq = self.batch - seq0 if nseq is None else nseq
+        out = np.zeros(nseq, dtype=np.uint8)
+        self._ck(self.L.sl2_get_active_sequences(self.h, int(seq0), int(nseq), _lib.u8p(out)))
+        return out
+
     def set_groups(self, groups):
         self._ck(self.L.sl2_set_groups(self.h, int(groups)))
 
