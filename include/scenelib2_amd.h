@@ -139,7 +139,14 @@ int sl2_get_vehicle_state(sl2_engine* e, int seq0, int nseq, double* xv, double*
  * patches [nseq][nfeat][121] = the 11x11 8-bit template the reference would
  * cv::imread from `identifier`.  Labels continue from next_free_label_; a sequence that lacks free slots first gets the slots
  * of its deleted features back (see SL2_STATUS_LABELS_EXHAUSTED below); SL2_ERR_CAPACITY if it still holds more than
- * max_features - nfeat live features. */
+ * max_features - nfeat live features.  The call is all or nothing as far as features go: when ANY sequence of the range
+ * lacks room, no sequence gets a feature and no label is used up.  What a failing call may have done is give other
+ * sequences their deleted features' slots back - a renumbering no accessor shows (slots are not part of the interface;
+ * sl2_get_features(include_deleted) merely stops listing the deleted features).  A sequence with room is not touched.
+ * The call may come between the seams of a step (sl2_kalman_filter_predict ... sl2_finish_step): the selection, the search
+ * records, the measurements and the recorded positions (Q28) of the frame in progress follow their features to the new
+ * slots.  A feature added behind sl2_auto_select_n_features joins the selection with the next frame, like the
+ * reference's AddNewKnownFeature at that point. */
 int sl2_add_known_features(sl2_engine* e, int seq0, int nseq, int nfeat, const double* y, const double* xp_org,
                            const uint8_t* patches);
 

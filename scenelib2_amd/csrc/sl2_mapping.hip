@@ -731,12 +731,17 @@ __global__ void __launch_bounds__(64) k_map_finish(MapArrays a, CameraParams cam
 // (so every "in feature_list_ order" rule - selection ties, the deletion walk, the total state layout - is untouched) and
 // the freed slots at the end take the next initialisations.  Labels live in f_label and are never reused.  Everything
 // indexed by slot moves: the feature's entries of x, its rows and columns of P, template, counters, flags, the per-frame
-// scratch the accessors read, and the slot numbers held by the selection lists and the partial feature's record.
+// scratch the accessors read, and the slot numbers held by the selection lists, by the selected positions' search records
+// (srch_sel: the search kernel fetches the template by that slot) and by the partial feature's record.  f_hcol - per slot,
+// the state column a feature's dh_by_dy block lands on under a position error (Q28) - moves with its slot AND has its value
+// re-based through the map P's columns go through: a squeeze may come between the seams of a step (sl2_add_known_features
+// after sl2_auto_select_n_features or sl2_make_measurements), when those records are live.
 // ---------------------------------------------------------------------------
 struct SlotArrays {
   double *x, *P, *xp_org, *f_h, *f_Hx, *f_Hy, *f_R, *f_S, *f_score, *f_z, *f_nu, *srch_d;
   uint8_t* patch;
   int *patch_sums, *f_flags, *attempted, *successful, *f_label, *srch_i, *sel_idx, *succ_idx, *f_arow, *n_sel, *m_count, *n_slots, *ps_i, *pos_err;
+  int *f_hcol, *srch_sel;
   int kpart;
   const uint8_t* active;     // the mask of a step's launch (nullptr: sl2_add_known_features and the "initialise feature" calls, which ignore it)
 };
@@ -831,11 +836,29 @@ __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, 
       // (a round's last slot may be half written: the next round reads the other half of it, or slots above it)
     }
   }
+  // f_hcol moves with its slot like the records above, in rounds of its own (the record loop has no register to spare), and
+  // its VALUE is re-based like the columns of P: the column of a live feature's block follows that feature; pose columns (and
+  // the 0 a negative column is held at), the partial features' columns behind the slots and a column whose feature has been
+  // retired meanwhile stay as they are.  Same order argument: a round's sources are slots >= its own first slot.
+  for (int d0 = 0; d0 < nl; d0 += nt) {
+    const int d = d0 + tid;
+    int col = 0;
+    if (d < nl) {
+      col = a.f_hcol[o + s_src[d]];
+      if (col >= 13 && col < 13 + 3 * ns) {
+        const int t = s_new[(col - 13) / 3];
+        if (t >= 0) col = 13 + 3 * t + (col - 13) % 3;
+      }
+    }
+    __syncthreads();
+    if (d < nl) a.f_hcol[o + d] = col;
+  }
   __syncthreads();
   for (int f = nl + tid; f < ns; f += nt) {                      // the freed slots: unused again
     flags[f] = 0;
     a.f_arow[o + f] = -1;
     a.pos_err[o + f] = 0;
+    a.f_hcol[o + f] = 0;
     a.attempted[o + f] = 0; a.successful[o + f] = 0;
     for (int k = 0; k < 3; ++k) a.x[(size_t)b * ld + 13 + 3 * f + k] = 0.0;
   }
@@ -883,6 +906,12 @@ __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, 
     }
     // (no second barrier: the next block reads rows >= its own first row, none of which this block wrote)
   }
+  // word 0 of selected position k's search record (k_select) is its slot: the one sel_idx[k] now names (each thread reads back
+  // what it wrote above; done down here, where nothing else is live - next to the sel_idx loop it cost three scalar spills)
+  for (int k = tid; k < a.n_sel[b]; k += nt) {
+    const int t = a.sel_idx[o + k];
+    if (t >= 0) a.srch_sel[(o + k) * 16] = t;
+  }
   if (tid == 0) a.n_slots[b] = nl;
 }
 
@@ -894,7 +923,7 @@ int launch_compact_slots(sl2_engine* e, int need, bool honour_mask) {
   a.f_score = e->f_score; a.f_z = e->f_z; a.f_nu = e->f_nu; a.srch_d = e->srch_d; a.patch = e->patch; a.patch_sums = e->patch_sums;
   a.f_flags = e->f_flags; a.attempted = e->attempted; a.successful = e->successful; a.f_label = e->f_label; a.srch_i = e->srch_i;
   a.sel_idx = e->sel_idx; a.succ_idx = e->succ_idx; a.f_arow = e->f_arow; a.n_sel = e->n_sel; a.m_count = e->m_count; a.n_slots = e->n_slots;
-  a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.kpart = e->kpart; a.active = honour_mask ? e->active : nullptr;
+  a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.f_hcol = e->f_hcol; a.srch_sel = e->srch_sel; a.kpart = e->kpart; a.active = honour_mask ? e->active : nullptr;
   hipLaunchKernelGGL(k_map_compact_slots, dim3(e->B), dim3(256), sizeof(int) * 2 * e->N, e->stream, a, e->N, e->ld, e->ppos, need);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
