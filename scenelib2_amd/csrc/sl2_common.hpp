@@ -10,6 +10,7 @@
 
 #include "../../include/scenelib2_amd.h"
 #include "sl2_math.hpp"
+#include "sl2_seq_arrays.hpp"
 
 namespace sl2 {
 
@@ -40,10 +41,8 @@ enum : int {
   FF_PARTIAL = 64,    // label reserved by a partially initialised feature (its 6 states live at ppos + 6 k, k = its partial slot)
 };
 
-constexpr int kTrajCapacity = 1000;  // monoslam.cpp:174
 // feature initialisation (one partially initialised feature per sequence)
 constexpr int kMaxParticles = 1024;      // upper bound of params.number_of_particles (k_map_particles: one thread per particle)
-constexpr int kParticleDoubles = 12;     // lambda, probability, cumulative, h[2], z[2], SInv(00,01,11), detS, success
 // Large search windows are cut into UNITS of a few bands (32 x 16 candidate positions each) that any wavefront of the search
 // launch may take (sl2_search.hip: m4_big_windows).  sl2_engine::srch_big, ints: [0] units allocated this step (k_select),
 // [1] windows shared out in the last completed step (sl2_get_step_work), [2] next unit to hand out, [3] windows shared out this
@@ -71,20 +70,14 @@ __host__ __device__ inline int srch_unit_bands(int bands) { const int g = (bands
 // Partially initialised features: up to kMaxPartial per sequence (params.max_features_to_init_at_once, monoslam.cpp:163-167).
 // part_i / part_d = the per-SEQUENCE record: feature_init_info_vector_.size(), the partial slots in the vector's order (a
 // conversion or deletion erases an entry, the later ones move up), the image selection and the counters; ps_i / ps_d = one
-// record per PARTIAL SLOT k (FeatureInitInfo): its six states live in columns ppos + 6 k of x / P.
+// record per PARTIAL SLOT k (FeatureInitInfo): its six states live in columns ppos + 6 k of x / P.  (Their sizes, kPartInts /
+// kPartDoubles and kPsInts / kPsDoubles, are in sl2_seq_arrays.hpp.)
 constexpr int kMaxPartial = 4;
-constexpr int kPartInts = 16, kPartDoubles = 4;
 enum : int { kPartCount = 0, kPartOrder /* kMaxPartial ints */, kPartUU = 5, kPartVV, kPartRegionValid,
              kPartRegion /* 4 ints */, kPartInitialised = 12, kPartConverted, kPartDeleted, kPartCreated };
-constexpr int kPsInts = 8, kPsDoubles = 4;          // ps_d: mean, covariance of lambda
 enum : int { kPsActive = 0, kPsLabel /* the feature SLOT that holds its label */, kPsAttempts, kPsNp, kPsMaking };
-constexpr int kWorkDoubles = 5;     // per-sequence work counters of a step (work[]): window bytes, searches, candidates, exact
-                                    // fallbacks, 16 x 16 candidate tiles of the matrix-core search
 constexpr int kCholBlock = 32;       // block size of the blocked Cholesky / forward substitution
-constexpr int kPatchStride = 288;    // bytes per stored template: 121 raw bytes (+7 pad), then at byte
-                                     // 128 the packed form: 33 dwords (11 rows x 12 bytes, byte 11 = 0),
-                                     // sum g0, sum g0^2, flag (patch sigma >= 10), pad
-constexpr int kPatchPackedOffset = 128;
+constexpr int kPatchPackedOffset = 128;   // where the packed form of a stored template starts (kPatchStride, sl2_seq_arrays.hpp)
 
 // XCD-aware block -> (sequence, tile) mapping.  MI355X dispatches workgroup L to XCD L % 8 and
 // every XCD has its own 4 MB L2; all tiles of one sequence share that sequence's operands
@@ -115,8 +108,9 @@ struct PendingEvent {
 
 }  // namespace sl2
 
-// The opaque engine object of the C ABI.
-struct sl2_engine {
+// The opaque engine object of the C ABI.  Its per-sequence device arrays (x, P, patch ... me_desc) are the members of
+// sl2::SeqArrays, listed and documented in sl2_seq_arrays.hpp.
+struct sl2_engine : sl2::SeqArrays {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -128,31 +122,7 @@ struct sl2_engine {
   int nsel_max = 0;  // max features measured per frame
   int mld = 0;       // leading dimension of the innovation system (>= 2 nsel_max, multiple of 32)
   int nblk_max = 0;  // mld / 32
-
-  // ---- persistent SLAM state (device) ----
-  double* x = nullptr;        // [B][ld]        total state: xv(13), y_0(3), y_1(3) ... ; x[ld-1] unused
-  double* P = nullptr;        // [B][ld][ld]    total covariance, dense; row/col ld-1 always zero
-  uint8_t* patch = nullptr;   // [B][N][128]    11x11 templates
-  int* patch_sums = nullptr;  // [B][N][2]      (sum g0, sum g0^2) of each template
-  double* xp_org = nullptr;   // [B][N][8]      xp_org_ (7 used)
-  int* f_flags = nullptr;     // [B][N]
-  int* n_slots = nullptr;     // [B]            slots in use (live, reserved or retired features), list order = slot order
-  int* f_label = nullptr;     // [B][N]         Feature::label_ of the slot (slots are compacted when they run out, labels never reused)
-  int* next_label = nullptr;  // [B]            next_free_label_
-  int* attempted = nullptr;   // [B][N]
-  int* successful = nullptr;  // [B][N]
-  double* traj = nullptr;     // [B][kTrajCapacity][3]
-  int* traj_count = nullptr;  // [B]  total pushes
-  double* last_r = nullptr;   // [B][3] scratch motion_model_->rRES_ (Q12)
-  int* status = nullptr;      // [B]
-  double* pos_log = nullptr;  // [B][kTrajCapacity][3] xv[0:3] after every step (the true trajectory, cf. Q12)
-  int* pos_count = nullptr;   // [B] steps logged so far (device-side, so that a captured step needs no per-step argument)
   long long steps_done = 0;
-  int* seq_age = nullptr;     // [B] a sequence's own step count minus pos_count (0 until it is loaded, copied in or reset: sl2_checkpoint.hip)
-  // ---- stepping a subset of the batch (sl2_set_active_sequences) ----
-  uint8_t* active = nullptr;  // [B] 1 = the sequence takes part in the steps issued from now on (all ones after sl2_create); engine-global, in no blob
-  int* sel_gate = nullptr;    // [B] per step: n_sel of an active sequence, 0 of a paused one (k_select) - what the search kernels take for n_sel
-  int* m_gate = nullptr;      // [B] per step: m_count of an active sequence, 0 of a paused one (k_search_score) - what the update chain takes for m_count
   int chol_variant = 1;       // 1 = one-launch left-looking Cholesky (k_chol_left; the product's only path); TEST build: 0 = launch-per-block kernels
   void* chol_trace = nullptr; // development only (SL2_CHOL_TRACE builds): per-wave cycle stamps of k_chol_fused4
   int build_variant = 1;      // 1 = k_build_AS (A and S in one pass over the measured features' rows of P; the product's only path); TEST build: 0 = k_build_A then k_build_S
@@ -160,22 +130,7 @@ struct sl2_engine {
   // ---- feature initialisation ----
   int ppos = 0;                          // first column of the partial features' states (13 + 3N); slot k at ppos + 6 k
   int kpart = 1;                         // partial slots per sequence: params.max_features_to_init_at_once, 1 .. kMaxPartial
-  int* part_i = nullptr;                 // [B][kPartInts]
-  double* part_d = nullptr;              // [B][kPartDoubles]  [2] = evbest of the last detection
-  int* ps_i = nullptr;                   // [B][kpart][kPsInts]
-  double* ps_d = nullptr;                // [B][kpart][kPsDoubles]
   int pcap = 128;                        // particle slots per partial feature: roundup(params.number_of_particles, 64)
-  double* particles = nullptr;           // [B][kpart][pcap][kParticleDoubles]
-  // Q28 (feature.cpp:254): a conversion moves the LATER features' position_in_total_state_vector_ by 6 instead of 3, and the
-  // reference then places their dh_by_dy blocks three columns early in H (monoslam.cpp:564).  pos_err = how far a slot's
-  // recorded position lies below its true one; f_hcol = the engine column its H block therefore lands on (k_search_score
-  // recomputes it for sequences that carry such an error; every other sequence uses 13 + 3 slot).
-  int* pos_err = nullptr;                // [B][N]
-  int* pos_err_any = nullptr;            // [B]
-  int* f_hcol = nullptr;                 // [B][N]
-  unsigned long long* rand48 = nullptr;  // [B]  drand48 state (srand48(0) at Init, monoslam.cpp:1968)
-  double* prev_r = nullptr;              // [B][3] camera position before the prediction (speed estimate, :121-124)
-  int* me_desc = nullptr;                // [B][kpart][pcap][8] search ellipses of the particles
   double* score_map = nullptr;           // [B][kpart][H][W] score cache of an OVERSIZED multi-ellipse search (allocated on first use)
   int* me_big_list = nullptr;            // [B * kpart] (sequence, partial slot) jobs too large for the one-workgroup form, this step
   int* me_big_count = nullptr;           // [1]
@@ -217,35 +172,6 @@ struct sl2_engine {
   // ---- large search windows (round 4): the step's units of work for every wavefront of k_search_mfma (layout: kSrchBig* above) ----
   int* srch_big = nullptr;    // per sequence GROUP (allocated by build_groups)
 
-  // ---- per-frame feature scratch (device), indexed [B][N] ----
-  double* f_h = nullptr;      // [..][2]
-  double* f_Hx = nullptr;     // [..][14]
-  double* f_Hy = nullptr;     // [..][6]
-  double* f_R = nullptr;      // [..]
-  double* f_S = nullptr;      // [..][4]
-  double* f_score = nullptr;  // [..]
-  double* f_z = nullptr;      // [..][2]  (persistent: untouched on failure, Q4)
-  double* f_nu = nullptr;     // [..][2]
-  int* sel_idx = nullptr;     // [B][N]   selected feature slots in selection order
-  int* n_sel = nullptr;       // [B]
-  int* n_vis = nullptr;       // [B]
-  int* meas_ok = nullptr;     // [B][N]   per selected position k
-  double* meas_score = nullptr;  // [B][N]
-  int* succ_idx = nullptr;    // [B][N]   successful feature slots, ascending (slot order)
-  int* f_arow = nullptr;      // [B][N]   per slot: first row of A^T / S of its measurement (2 x rank among the successes), -1 = none this frame
-  int* m_count = nullptr;     // [B]      number of successful features (m = 2 * m_count)
-  double* work = nullptr;     // [B][kWorkDoubles]   window bytes, searched, candidates, exact-fallback searches, candidate tiles
-  int* srch_i = nullptr;      // [B][N][8]  per-feature search window: ucentre, vcentre, urelstart, nu, vrelstart, nv, hw, hh
-  double* srch_d = nullptr;   // [B][N][4]  PuInv (a, b, c), pad
-  int* srch_res = nullptr;    // [B][N][8]  per selected position: code, u, v, S1, S2, X, ncand, pad
-  int* srch_sel = nullptr;    // [B][N][16] per selected position k (written by k_select): slot f, the 7 window ints of srch_i, then PuInv (a, b, c) as 3 doubles, pad - one 64-byte line, so that the search kernel needs ONE round trip for it
-
-  // ---- EKF update workspaces (device) ----
-  double* At = nullptr;    // [B][mld][ld]   (P H^T)^T, k-major; column ld-1 carries nu
-  double* Vt = nullptr;    // [B][mld][ld]   L^-1 (P H^T)^T
-  double* St = nullptr;    // [B][mld][mld]  St[c][r] = S[r][c]; overwritten by L (same layout)
-  double* LinvT = nullptr; // [B][nblk_max][32][32]  LinvT[p][k] = (L_JJ^-1)[k][p]
-
   // ---- engine-owned staging of the state accessors (no allocation per call; released by sl2_destroy) ----
   void* snap_stage = nullptr;     // device: the packed blob of sl2_snapshot
   void* snap_host = nullptr;      // pinned + mapped host memory the blob is streamed into (what sl2_snapshot returns)
@@ -275,7 +201,7 @@ struct sl2_engine {
   // ---- sequence groups: the batch is split into G contiguous groups, each stepped on its own
   // HIP stream, so that the latency-bound kernels of one group (blocked Cholesky, selection,
   // bookkeeping) overlap with the throughput-bound kernels of another (SYRK, substitution, search).
-  // A group is a shallow copy of the root engine whose per-sequence pointers are offset.
+  // A group is a shallow copy of the root engine whose per-sequence pointers are offset (sl2_seq_arrays.hpp: seq_arrays_view).
   sl2_engine* root = nullptr;           // self for the root object
   std::vector<sl2_engine*> groups;      // root only
   int group_first = 0;                  // first sequence of this group

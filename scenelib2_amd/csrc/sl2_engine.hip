@@ -145,50 +145,51 @@ static int acc_scratch(sl2_engine* e, size_t dev_bytes, size_t host_bytes) {
 #endif
 using namespace sl2;
 
+// Captured steps bake kernel choices, arguments and the groups' pointers in: every setter that changes one of them drops the
+// graphs through here - after the device has finished with them (a replay may still be in flight on the engine's streams).
+static int drop_step_graphs(sl2_engine* e) {
+  if (e->step_graphs.empty()) return SL2_OK;
+  SL2_HIP(hipSetDevice(e->device));
+  { int rc = e->sync_all(); if (rc != SL2_OK) return rc; }
+  for (auto& sg : e->step_graphs) hipGraphExecDestroy(sg.exec);
+  e->step_graphs.clear();
+  return SL2_OK;
+}
+
+// Release a group object and what it owns: its stream (unless it steps on the root's), its join event and its list of
+// large search windows.  Also right for a half-built group.
+static void free_group(sl2_engine* root, sl2_engine* g) {
+  if (g->stream && g->stream != root->stream) hipStreamDestroy(g->stream);
+  if (g->fork_event) hipEventDestroy(g->fork_event);
+  if (g->srch_big) hipFree(g->srch_big);
+  delete g;
+}
+
 // Build the group objects: shallow copies of the root whose per-sequence pointers start at
-// `first` and whose B is the group's sequence count.  G == 1 -> a single group on the root stream.
+// `first` (seq_arrays_view) and whose B is the group's sequence count.  G == 1 -> a single group on the root stream.
 static int build_groups(sl2_engine* e, int G) {
-  for (sl2_engine* g : e->groups) {
-    if (g->stream != e->stream) hipStreamDestroy(g->stream);
-    if (g->srch_big) hipFree(g->srch_big);
-    delete g;
-  }
+  for (sl2_engine* g : e->groups) free_group(e, g);
   e->groups.clear();
   if (G < 1) G = 1;
   if (G > e->B) G = e->B;
-  const size_t N = e->N, ld = e->ld, mld = e->mld;
+  const SeqDims dims = {(size_t)e->N, (size_t)e->ld, (size_t)e->mld, (size_t)e->nblk_max, (size_t)e->kpart, (size_t)e->pcap};
   for (int k = 0; k < G; ++k) {
-    const int base = e->B / G, rem = e->B % G;
-    const int first = k * base + (k < rem ? k : rem), count = base + (k < rem ? 1 : 0);
+    int first, count;
+    group_range(e->B, G, k, &first, &count);
     sl2_engine* g = new sl2_engine();
     g->device = e->device; g->cam = e->cam; g->prm = e->prm;
     g->B = count; g->N = e->N; g->ld = e->ld; g->nsel_max = e->nsel_max; g->mld = e->mld; g->nblk_max = e->nblk_max;
     g->ppos = e->ppos; g->pcap = e->pcap; g->kpart = e->kpart;
     g->root = e; g->group_first = first;
-    if (G == 1) g->stream = e->stream; else SL2_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    const size_t f = first;
-    g->x = e->x + f * ld; g->P = e->P + f * ld * ld; g->patch = e->patch + f * N * kPatchStride;
-    g->patch_sums = e->patch_sums + f * N * 2; g->xp_org = e->xp_org + f * N * 8; g->f_flags = e->f_flags + f * N;
-    g->f_label = e->f_label + f * N; g->next_label = e->next_label + f;
-    g->n_slots = e->n_slots + f; g->attempted = e->attempted + f * N; g->successful = e->successful + f * N;
-    g->traj = e->traj + f * kTrajCapacity * 3; g->traj_count = e->traj_count + f; g->last_r = e->last_r + f * 3;
-    g->status = e->status + f; g->pos_log = e->pos_log + f * kTrajCapacity * 3; g->pos_count = e->pos_count + f;
-    g->f_h = e->f_h + f * N * 2; g->f_Hx = e->f_Hx + f * N * 14; g->f_Hy = e->f_Hy + f * N * 6; g->f_R = e->f_R + f * N;
-    g->f_S = e->f_S + f * N * 4; g->f_score = e->f_score + f * N; g->f_z = e->f_z + f * N * 2; g->f_nu = e->f_nu + f * N * 2;
-    g->sel_idx = e->sel_idx + f * N; g->n_sel = e->n_sel + f; g->n_vis = e->n_vis + f; g->meas_ok = e->meas_ok + f * N;
-    g->meas_score = e->meas_score + f * N; g->succ_idx = e->succ_idx + f * N; g->f_arow = e->f_arow + f * N; g->m_count = e->m_count + f;
-    g->srch_i = e->srch_i + f * N * 8; g->srch_d = e->srch_d + f * N * 4; g->srch_res = e->srch_res + f * N * 8; g->srch_sel = e->srch_sel + f * N * 16;
-    g->work = e->work + f * kWorkDoubles; g->At = e->At + f * mld * ld; g->Vt = e->Vt + f * mld * ld; g->St = e->St + f * mld * mld;
-    g->LinvT = e->LinvT + f * (size_t)e->nblk_max * 1024;
-    g->part_i = e->part_i + f * kPartInts; g->part_d = e->part_d + f * kPartDoubles;
-    g->ps_i = e->ps_i + f * e->kpart * kPsInts; g->ps_d = e->ps_d + f * e->kpart * kPsDoubles;
-    g->particles = e->particles + f * e->kpart * e->pcap * kParticleDoubles; g->rand48 = e->rand48 + f; g->prev_r = e->prev_r + f * 3;
-    g->me_desc = e->me_desc + f * e->kpart * e->pcap * 8;
-    g->pos_err = e->pos_err + f * N; g->pos_err_any = e->pos_err_any + f; g->f_hcol = e->f_hcol + f * N;
-    g->seq_age = e->seq_age + f; g->active = e->active + f; g->sel_gate = e->sel_gate + f; g->m_gate = e->m_gate + f;
-    // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
-    SL2_HIP(hipMalloc((void**)&g->srch_big, sizeof(int) * kSrchBigInts));
-    SL2_HIP(hipMemsetAsync(g->srch_big, 0, sizeof(int) * kSrchBigParts, e->stream));      // (everything but the partial results)
+    static_cast<SeqArrays&>(*g) = seq_arrays_view(*e, dims, first);
+    const int rc = [&]() -> int {
+      if (G == 1) g->stream = e->stream; else SL2_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+      // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
+      SL2_HIP(hipMalloc((void**)&g->srch_big, sizeof(int) * kSrchBigInts));
+      SL2_HIP(hipMemsetAsync(g->srch_big, 0, sizeof(int) * kSrchBigParts, e->stream));      // (everything but the partial results)
+      return SL2_OK;
+    }();
+    if (rc != SL2_OK) { free_group(e, g); return rc; }
     e->groups.push_back(g);
   }
   return SL2_OK;
@@ -470,67 +471,13 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
     return SL2_ERR_CAPACITY;
   }
 #endif
-  const size_t B = batch, N = max_features, ld = e->ld, mld = e->mld;
-  int r = SL2_OK;
-#define A(call) do { r = (call); if (r != SL2_OK) { return r; } } while (0)
-  A(dmalloc(&e->x, B * ld));
-  A(dmalloc(&e->P, B * ld * ld));
-  A(dmalloc(&e->patch, B * N * kPatchStride));
-  A(dmalloc(&e->patch_sums, B * N * 2));
-  A(dmalloc(&e->xp_org, B * N * 8));
-  A(dmalloc(&e->f_flags, B * N));
-  A(dmalloc(&e->n_slots, B));
-  A(dmalloc(&e->f_label, B * N));
-  A(dmalloc(&e->next_label, B));
-  A(dmalloc(&e->attempted, B * N));
-  A(dmalloc(&e->successful, B * N));
-  A(dmalloc(&e->traj, B * kTrajCapacity * 3));
-  A(dmalloc(&e->traj_count, B));
-  A(dmalloc(&e->last_r, B * 3));
-  A(dmalloc(&e->status, B));
-  A(dmalloc(&e->pos_log, B * kTrajCapacity * 3));
-  A(dmalloc(&e->pos_count, B));
-  A(dmalloc(&e->seq_age, B));
-  A(dmalloc(&e->active, B));
-  A(dmalloc(&e->sel_gate, B));
-  A(dmalloc(&e->m_gate, B));
-  A(dmalloc(&e->f_h, B * N * 2));
-  A(dmalloc(&e->f_Hx, B * N * 14));
-  A(dmalloc(&e->f_Hy, B * N * 6));
-  A(dmalloc(&e->f_R, B * N));
-  A(dmalloc(&e->f_S, B * N * 4));
-  A(dmalloc(&e->f_score, B * N));
-  A(dmalloc(&e->f_z, B * N * 2));
-  A(dmalloc(&e->f_nu, B * N * 2));
-  A(dmalloc(&e->sel_idx, B * N));
-  A(dmalloc(&e->n_sel, B));
-  A(dmalloc(&e->n_vis, B));
-  A(dmalloc(&e->meas_ok, B * N));
-  A(dmalloc(&e->meas_score, B * N));
-  A(dmalloc(&e->succ_idx, B * N));
-  A(dmalloc(&e->f_arow, B * N));
-  A(dmalloc(&e->m_count, B));
-  A(dmalloc(&e->work, B * kWorkDoubles));
-  A(dmalloc(&e->srch_i, B * N * 8));
-  A(dmalloc(&e->srch_d, B * N * 4));
-  A(dmalloc(&e->srch_res, B * N * 8));
-  A(dmalloc(&e->srch_sel, B * N * 16));
-  A(dmalloc(&e->At, B * mld * ld));
-  A(dmalloc(&e->Vt, B * mld * ld));
-  A(dmalloc(&e->St, B * mld * mld));
-  A(dmalloc(&e->LinvT, B * (size_t)e->nblk_max * 1024));
-  A(dmalloc(&e->part_i, B * kPartInts));
-  A(dmalloc(&e->part_d, B * kPartDoubles));
-  A(dmalloc(&e->ps_i, B * (size_t)e->kpart * kPsInts));
-  A(dmalloc(&e->ps_d, B * (size_t)e->kpart * kPsDoubles));
-  A(dmalloc(&e->pos_err, B * N));
-  A(dmalloc(&e->pos_err_any, B));
-  A(dmalloc(&e->f_hcol, B * N));
-  A(dmalloc(&e->particles, B * (size_t)e->kpart * e->pcap * kParticleDoubles));
-  A(dmalloc(&e->rand48, B));
-  A(dmalloc(&e->prev_r, B * 3));
-  A(dmalloc(&e->me_desc, B * (size_t)e->kpart * e->pcap * 8));
-#undef A
+  const size_t B = batch;
+  {   // every per-sequence array, zero-filled, in the order of the list (sl2_seq_arrays.hpp)
+    const size_t N = max_features, ld = e->ld, mld = e->mld, nblk_max = e->nblk_max, kpart = e->kpart, pcap = e->pcap;
+#define X(type, name, elems) { const int r = dmalloc(&e->name, B * (size_t)(elems)); if (r != SL2_OK) return r; }
+    SL2_SEQ_ARRAYS(X)
+#undef X
+  }
   SL2_HIP(hipMemset(e->active, 1, B));                               // every sequence takes part until sl2_set_active_sequences says otherwise
   SL2_HIP(hipMalloc((void**)&e->slots_max_dev, sizeof(int) * 2));
   SL2_HIP(hipMemset(e->slots_max_dev, 0, sizeof(int) * 2));
@@ -588,8 +535,7 @@ int sl2_set_groups(sl2_engine* e, int groups) {
   { int rc = e->sync_all(); if (rc != SL2_OK) return rc; }
   // captured steps carry the groups' pointers (srch_big is re-allocated per group below, the streams change): replaying one
   // after a rebuild would write through freed device memory
-  for (auto& sg : e->step_graphs) hipGraphExecDestroy(sg.exec);       // (synchronised above; drop_step_graphs is defined further down)
-  e->step_graphs.clear();
+  { int rc = drop_step_graphs(e); if (rc != SL2_OK) return rc; }
   return build_groups(e, groups);
 }
 
@@ -597,20 +543,14 @@ void sl2_destroy(sl2_engine* e) {
   if (!e) return;
   hipSetDevice(e->device);
   e->sync_all();
-  for (sl2_engine* g : e->groups) {
-    if (g->stream != e->stream) hipStreamDestroy(g->stream);
-    if (g->fork_event) hipEventDestroy(g->fork_event);
-    if (g->srch_big) hipFree(g->srch_big);
-    delete g;
-  }
+  for (sl2_engine* g : e->groups) free_group(e, g);
   if (e->fork_event) hipEventDestroy(e->fork_event);
   for (auto& sg : e->step_graphs) hipGraphExecDestroy(sg.exec);
-  void* ptrs[] = {e->x, e->P, e->patch, e->patch_sums, e->xp_org, e->f_flags, e->n_slots, e->attempted, e->successful,
-                  e->traj, e->traj_count, e->last_r, e->status, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score,
-                  e->f_z, e->f_nu, e->sel_idx, e->n_sel, e->n_vis, e->meas_ok, e->meas_score, e->succ_idx, e->f_arow, e->m_count,
-                  e->work, e->At, e->Vt, e->St, e->LinvT, e->frames_buf, e->pos_log, e->srch_i, e->srch_d, e->srch_res, e->srch_sel,
-                  e->part_i, e->part_d, e->particles, e->rand48, e->prev_r, e->me_desc, e->score_map, e->me_big_list, e->ps_i, e->ps_d, e->pos_err, e->pos_err_any, e->f_hcol, e->pos_count, e->init_uv, e->f_label, e->next_label, e->seq_age, e->active, e->sel_gate, e->m_gate};
-  for (void* p : ptrs) if (p) hipFree(p);
+#define X(type, name, elems) if (e->name) hipFree(e->name);
+  SL2_SEQ_ARRAYS(X)
+#undef X
+  void* lazy[] = {e->frames_buf, e->score_map, e->me_big_list, e->init_uv};      // (allocated on first use)
+  for (void* p : lazy) if (p) hipFree(p);
   release_checkpoint_staging(e);
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
   if (e->slots_mail) hipHostFree(e->slots_mail);
@@ -820,17 +760,6 @@ static int bind_frames(sl2_engine* e, const uint8_t* frames, size_t seq_stride, 
   return SL2_OK;
 }
 
-// Captured steps bake kernel choices, arguments and the groups' pointers in: every setter that changes one of them drops the
-// graphs through here - after the device has finished with them (a replay may still be in flight on the engine's streams).
-static int drop_step_graphs(sl2_engine* e) {
-  if (e->step_graphs.empty()) return SL2_OK;
-  SL2_HIP(hipSetDevice(e->device));
-  { int rc = e->sync_all(); if (rc != SL2_OK) return rc; }
-  for (auto& sg : e->step_graphs) hipGraphExecDestroy(sg.exec);
-  e->step_graphs.clear();
-  return SL2_OK;
-}
-
 int sl2_set_search_variant(sl2_engine* e, int variant) {
   if (!e || variant < 0 || variant > 1) return SL2_ERR_INVALID;
   { int rc = drop_step_graphs(e); if (rc != SL2_OK) return rc; }
@@ -957,6 +886,15 @@ static int enable_feature_initialisation(sl2_engine* e) {
   return SL2_OK;
 }
 
+// Feature initialisation runs on group 0, the whole batch (enable_feature_initialisation refuses sequence groups): hand it the
+// frame binding and the buffers that are allocated on first use, which build_groups does not copy.
+static sl2_engine* mapping_group(sl2_engine* e) {
+  sl2_engine* g = e->groups[0];
+  g->cur_frames = e->cur_frames; g->cur_stride = e->cur_stride;
+  g->score_map = e->score_map; g->me_big_list = e->me_big_list; g->me_big_count = e->me_big_count;
+  return g;
+}
+
 static int initialise_common(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int frames_on_device, const int32_t* uv,
                              int32_t* created) {
   if (!e) return SL2_ERR_INVALID;
@@ -964,9 +902,7 @@ static int initialise_common(sl2_engine* e, const uint8_t* frames, size_t seq_st
   int rc;
   if ((rc = enable_feature_initialisation(e)) != SL2_OK) return rc;
   if ((rc = bind_frames(e, frames, seq_stride, frames_on_device)) != SL2_OK) return rc;
-  sl2_engine* g = e->groups.empty() ? e : e->groups[0];
-  g->cur_frames = e->cur_frames; g->cur_stride = e->cur_stride;
-  g->score_map = e->score_map; g->me_big_list = e->me_big_list; g->me_big_count = e->me_big_count;
+  sl2_engine* g = mapping_group(e);
   if (uv) {
     if (!e->init_uv) SL2_HIP(hipMalloc((void**)&e->init_uv, sizeof(int) * 2 * e->B));
     // the caller's buffer may be pinned or registered memory, for which an asynchronous copy really is asynchronous: the copy
@@ -1039,11 +975,7 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
       return launch_finalize(g, tail ? 0 : save_trajectory);
     });
     if (r == SL2_OK && tail) {
-      sl2_engine* g = e->groups.empty() ? e : e->groups[0];
-      g->cur_frames = e->cur_frames; g->cur_stride = e->cur_stride;
-      g->score_map = e->score_map;
-      g->me_big_list = e->me_big_list; g->me_big_count = e->me_big_count;
-      r = launch_mapping(g, enable_mapping ? 1 : 0, save_trajectory, slots_bound, parts_state);
+      r = launch_mapping(mapping_group(e), enable_mapping ? 1 : 0, save_trajectory, slots_bound, parts_state);
     }
     return r;
   };

@@ -294,6 +294,16 @@ def test_ragged_batch_and_empty_map(groups):
     assert cnt["selected"] == 10 and cnt["visible"] == 16      # Q8: visible count, not selected count
 
 
+def test_groups_rebuilt_over_live_state():
+    """The sequence groups of one engine rebuilt before every frame, uneven splits included (5 sequences in 3, 2 and 4 groups):
+    each rebuild takes new views of the live per-sequence arrays, and the state stays the oracle's throughout."""
+    pr = Pair(16, 8, batch=5, n_select=10, feature_counts=[16, 0, 7, 11, 3], max_features=16)
+    for k, groups in enumerate([3, 2, 5, 1, 4, 3, 2, 1]):
+        pr.engine.set_groups(groups)
+        pr.step_both(k)
+        pr.compare_state(TOL_X, TOL_P)
+
+
 def test_all_measurements_fail_means_pure_prediction():
     pr = Pair(12, 1, batch=1)
     flat = np.full((1, 240, 320), 77, np.uint8)

@@ -92,7 +92,7 @@ def test_small_back_leaves_room_for_three_workgroups_per_cu(tmp_path):
     static = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
     panel = 8 * _constexpr("sl2_small.hip", "kSmallM") * _constexpr("sl2_small.hip", "kSmallW")
     n_max = (2048 - 13 - 6 - 1) // 3                       # ld = roundup(13 + 3 N + 6 kpart + 1, 64) <= 2048, kpart >= 1
-    scratch = 4 * (2 * n_max + 10) + 8 * (16 + 169 + 169 + 16 * _constexpr("sl2_common.hpp", "kWorkDoubles"))
+    scratch = 4 * (2 * n_max + 10) + 8 * (16 + 169 + 169 + 16 * _constexpr("sl2_seq_arrays.hpp", "kWorkDoubles"))
     dyn = max(panel, scratch)
     assert static + dyn <= LDS_PER_CU // 3, "k_small_back: %d B static + %d B dynamic > %d B (a third of the CU's LDS)" % (
         static, dyn, LDS_PER_CU // 3)
