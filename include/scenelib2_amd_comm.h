@@ -52,13 +52,20 @@ const char* sl2_comm_last_error(void);
 
 /* One step's frames, `total_sequences` x frame_bytes device bytes on rank `root` (frames_all; ignored elsewhere), to the owners:
  * rank r receives its sl2_shard_range block into recv (device memory of at least count * frame_bytes bytes).  Asynchronous on
- * `stream` (a hipStream_t of the rank's device; NULL: the default stream).  Every rank of the communicator calls it; within
- * one process over several communicators the calls must be bracketed by sl2_comm_group_begin / _end. */
+ * `stream` (a hipStream_t of the rank's device; NULL: the default stream) and ordered on it like a copy: recv may be read, and
+ * on the root frames_all rewritten, by whatever is queued on that stream next.  Every rank of the communicator calls it with the
+ * same root, frame_bytes and total_sequences - a rank whose block is empty too (it then neither sends nor receives; recv must
+ * still be a pointer); within one process over several communicators the calls must be bracketed by sl2_comm_group_begin /
+ * _end. */
 int sl2_scatter_frames(sl2_comm* c, int root, const uint8_t* frames_all, size_t frame_bytes, int total_sequences, uint8_t* recv,
                        void* stream);
 /* The per-sequence rows of engine e (all its sequences; every rank's engine must have the same batch and capacity) gathered on
  * every rank: out = device memory of nranks * batch * sl2_gather_row_doubles doubles, ordered by rank = by global sequence
- * index.  Ordered behind the engine's queued steps; asynchronous on `stream` - synchronise it before reading. */
+ * index: row r * batch + b is sequence b of rank r's engine, on every rank.  Ordered behind the engine's queued steps (whichever
+ * stream is given); asynchronous on `stream` - synchronise it before reading.  The rows are staged in a buffer that belongs to
+ * the communicator: two gathers through ONE communicator must be issued in stream order on one stream (or the first waited for).
+ * Within one process over several communicators the calls must be bracketed by sl2_comm_group_begin / _end; what a collective
+ * then has to refuse (engines of different batch, say) is the status of sl2_comm_group_end, the calls inside only queue. */
 int sl2_gather_states(sl2_comm* c, sl2_engine* e, int what, double* out, void* stream);
 /* ncclGroupStart / ncclGroupEnd: needed around the calls of SEVERAL communicators issued by one host thread. */
 int sl2_comm_group_begin(void);

@@ -116,12 +116,19 @@ int sl2_comm_create_all(int ndev, const int* devices, sl2_comm** out) {
   }
   std::vector<ncclComm_t> comms(ndev);
   SL2C_NCCL(ncclCommInitAll(comms.data(), ndev, devs.data()));
+  for (int i = 0; i < ndev; ++i) out[i] = nullptr;
   for (int i = 0; i < ndev; ++i) {
     sl2_comm* c = new sl2_comm();
     c->nccl = comms[i]; c->rank = i; c->nranks = ndev; c->device = devs[i];
     out[i] = c;
     int rc = finish_create(c);
-    if (rc != SL2_OK) return rc;
+    if (rc != SL2_OK) {
+      // all or nothing: the communicators wrapped so far (this one included) go with their sl2_comm, the rest as they are;
+      // the message of finish_create survives (nothing below sets it)
+      for (int j = 0; j <= i; ++j) { sl2_comm_destroy(out[j]); out[j] = nullptr; }
+      for (int j = i + 1; j < ndev; ++j) ncclCommDestroy(comms[j]);
+      return rc;
+    }
   }
   return SL2_OK;
 }

@@ -52,15 +52,21 @@ class Pair:
         self.engine = None
         if make_engine:
             # lib = _lib.load_testing(): the TEST build of the library (superseded kernel variants, SL2_* switches)
-            self.engine = Engine(self.cam, self.params, batch, max_features or max(n_features, 1), lib=lib)
-            self.engine.set_vehicle_state(np.stack([s.xv0 for s in self.specs]), np.stack([s.Pxx0 for s in self.specs]))
-            for b in range(batch):
-                nf = self.specs[b].feat_y.shape[0]
-                if nf:
-                    self.engine.add_known_features(self.specs[b].feat_y[None], np.tile(self.specs[b].poses[0], (1, nf, 1)),
-                                                   self.templates[b][None], seq0=b)
-                    if feature_sigma > 0.0:
-                        self.engine.set_feature_covariances(np.tile(np.eye(3) * feature_sigma ** 2, (1, nf, 1, 1)), seq0=b)
+            self.engine = self.make_engine_for(0, batch, max_features or max(n_features, 1), feature_sigma=feature_sigma, lib=lib)
+
+    def make_engine_for(self, seq0, batch, max_features, feature_sigma=0.0, lib=None):
+        """An engine of `batch` sequences holding this Pair's sequences seq0 .. seq0 + batch - 1 (initial state, known
+        features and their templates): the Pair's own engine is make_engine_for(0, B, ...); a sharded run makes one per rank."""
+        specs = self.specs[seq0:seq0 + batch]
+        engine = Engine(self.cam, self.params, batch, max_features, lib=lib)
+        engine.set_vehicle_state(np.stack([s.xv0 for s in specs]), np.stack([s.Pxx0 for s in specs]))
+        for b, spec in enumerate(specs):
+            nf = spec.feat_y.shape[0]
+            if nf:
+                engine.add_known_features(spec.feat_y[None], np.tile(spec.poses[0], (1, nf, 1)), self.templates[seq0 + b][None], seq0=b)
+                if feature_sigma > 0.0:
+                    engine.set_feature_covariances(np.tile(np.eye(3) * feature_sigma ** 2, (1, nf, 1, 1)), seq0=b)
+        return engine
 
     def frame_batch(self, k):
         return np.stack([f[k] for f in self.frames])
@@ -79,34 +85,41 @@ class Pair:
 
     def compare_state(self, tol_x=1e-9, tol_P=1e-9, exact_z=True):
         """Returns worst deviations; asserts structure equality."""
-        worst = dict(x=0.0, P=0.0)
-        for b in range(self.B):
-            o = self.oracles[b]
-            n = o.total_state_size
-            assert int(self.engine.total_state_sizes(b, 1)[0]) == n, "state size differs (seq %d)" % b
-            xo, xe = o.total_state(), self.engine.total_state(b)
-            Po, Pe = o.total_covariance(), self.engine.total_covariance(b)
-            dx = np.abs(xo - xe).max() if n else 0.0
-            dP = np.linalg.norm(Po - Pe) / max(np.linalg.norm(Po), 1e-300)
-            worst["x"] = max(worst["x"], float(dx))
-            worst["P"] = max(worst["P"], float(dP))
-            assert dx <= tol_x, "state differs by %g (seq %d)" % (dx, b)
-            assert dP <= tol_P, "covariance rel-Frobenius differs by %g (seq %d)" % (dP, b)
-            feats = self.engine.features(b)
-            assert len(feats) == o.num_features
-            sel, counters = self.engine.selection(b)
-            assert counters["visible"] == o.num_visible
-            assert list(sel) == list(o.selected_labels()), "selection order differs (seq %d)" % b
-            assert counters["measurement_size"] == (o.measurement_size if o.num_selected else counters["measurement_size"])
-            for i, fe in enumerate(feats):
-                fo = o.feature(i)
-                assert fe["label"] == fo["label"]
-                assert fe["attempted"] == fo["attempted"] and fe["successful"] == fo["successful"], \
-                    "counters differ (seq %d feature %d)" % (b, fe["label"])
-                assert fe["selected"] == fo["selected"]
-                if fe["selected"]:
-                    assert fe["success"] == fo["success"]
-                    if exact_z and fo["success"]:
-                        assert np.array_equal(fe["z"], fo["z"]), "measurement differs (seq %d feature %d): %s vs %s" % (
-                            b, fe["label"], fe["z"], fo["z"])
-        return worst
+        return compare_state(self.oracles, self.engine, tol_x, tol_P, exact_z)
+
+
+def compare_state(oracles, engine, tol_x=1e-9, tol_P=1e-9, exact_z=True):
+    """Sequence b of `engine` against oracles[b], for every oracle given: total state (max-abs) and covariance (relative
+    Frobenius) to the tolerances, and selection order, counters, flags and (exact_z) the measurements exactly.  Returns the
+    worst deviations."""
+    worst = dict(x=0.0, P=0.0)
+    for b in range(len(oracles)):
+        o = oracles[b]
+        n = o.total_state_size
+        assert int(engine.total_state_sizes(b, 1)[0]) == n, "state size differs (seq %d)" % b
+        xo, xe = o.total_state(), engine.total_state(b)
+        Po, Pe = o.total_covariance(), engine.total_covariance(b)
+        dx = np.abs(xo - xe).max() if n else 0.0
+        dP = np.linalg.norm(Po - Pe) / max(np.linalg.norm(Po), 1e-300)
+        worst["x"] = max(worst["x"], float(dx))
+        worst["P"] = max(worst["P"], float(dP))
+        assert dx <= tol_x, "state differs by %g (seq %d)" % (dx, b)
+        assert dP <= tol_P, "covariance rel-Frobenius differs by %g (seq %d)" % (dP, b)
+        feats = engine.features(b)
+        assert len(feats) == o.num_features
+        sel, counters = engine.selection(b)
+        assert counters["visible"] == o.num_visible
+        assert list(sel) == list(o.selected_labels()), "selection order differs (seq %d)" % b
+        assert counters["measurement_size"] == (o.measurement_size if o.num_selected else counters["measurement_size"])
+        for i, fe in enumerate(feats):
+            fo = o.feature(i)
+            assert fe["label"] == fo["label"]
+            assert fe["attempted"] == fo["attempted"] and fe["successful"] == fo["successful"], \
+                "counters differ (seq %d feature %d)" % (b, fe["label"])
+            assert fe["selected"] == fo["selected"]
+            if fe["selected"]:
+                assert fe["success"] == fo["success"]
+                if exact_z and fo["success"]:
+                    assert np.array_equal(fe["z"], fo["z"]), "measurement differs (seq %d feature %d): %s vs %s" % (
+                        b, fe["label"], fe["z"], fo["z"])
+    return worst

@@ -1,9 +1,13 @@
 """Host-C++ sharding over RCCL (include/scenelib2_amd_comm.h, scenelib2_amd/libscenelib2_amd_comm.so, examples/sharded_monoslam.cpp).
 
-CPU: the library exports exactly what its header declares; the partition rule every scatter / gather uses (sl2_shard_range)
-equals the Python launcher's (scenelib2_amd/sharding.py) for every (total, ranks) - the N > 1 arithmetic, with no collective
-involved.  GPU (one device on the test box): a single-rank communicator, frames scattered from the root, three sequences
-stepped, states and covariance blocks gathered - against the oracle fed the same bytes."""
+CPU: the library exports exactly what its header declares, and so does its test build over tests/rccl_standin.cpp; the
+partition rule every scatter / gather uses (sl2_shard_range) equals the Python launcher's (scenelib2_amd/sharding.py) for every
+(total, ranks).  GPU, over real RCCL (one device on the test box, so one rank): a single-rank communicator, frames scattered
+from the root, three sequences stepped, states and covariance blocks gathered - against the oracle fed the same bytes.
+
+The project's own multi-rank code - block offsets, empty blocks, a root other than 0, the grouped and the thread-per-rank
+form, stream ordering, the row order of the gather - runs in tests/test_gpu_comm_multirank.py: 2 .. 4 ranks on one device over
+the stand-in.  Not covered anywhere: RCCL itself with more than one rank (over xGMI), and any scaling figure."""
 import ctypes as C
 import os
 import re
@@ -14,6 +18,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "scenelib2_amd", "libscenelib2_amd_comm.so")
+LIB_TEST = os.path.join(ROOT, "scenelib2_amd", "libscenelib2_amd_comm_test.so")
 HDR = os.path.join(ROOT, "include", "scenelib2_amd_comm.h")
 
 
@@ -22,14 +27,26 @@ def _declared():
     return sorted(set(re.findall(r"\b(sl2_[a-z_0-9]+)\s*\(", text)))
 
 
-def _exported():
-    out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
+def _exported(lib=LIB):
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
     return sorted(ln.split()[-1] for ln in out.splitlines() if " T sl2_" in ln)
 
 
 def test_comm_library_exports_exactly_its_header():
     assert os.path.exists(LIB), "scenelib2_amd/libscenelib2_amd_comm.so not built (make -C scenelib2_amd/csrc)"
     assert _exported() == _declared()
+
+
+def test_comm_test_library_is_the_header_over_the_stand_in():
+    """scenelib2_amd/libscenelib2_amd_comm_test.so: the same sl2_comm.o over tests/rccl_standin.cpp in place of librccl - the
+    header's functions and the stand-in's one counter, and not one nccl* call left to be resolved by a real RCCL."""
+    assert os.path.exists(LIB_TEST), "scenelib2_amd/libscenelib2_amd_comm_test.so not built (make -C scenelib2_amd/csrc)"
+    assert _exported(LIB_TEST) == sorted(_declared() + ["sl2_standin_live_comms"])
+    und = subprocess.run(["nm", "-D", "--undefined-only", LIB_TEST], capture_output=True, text=True, check=True).stdout
+    assert "hipMemcpyAsync" in und                                     # (the listing is there: the copies are the HIP runtime's)
+    assert [ln for ln in und.splitlines() if "nccl" in ln.lower()] == []
+    needed = subprocess.run(["readelf", "-d", LIB_TEST], capture_output=True, text=True, check=True).stdout
+    assert "libscenelib2_amd.so" in needed and "rccl" not in needed
 
 
 def test_shard_range_is_the_block_partition_of_the_python_launcher():
@@ -54,8 +71,9 @@ def test_shard_range_is_the_block_partition_of_the_python_launcher():
 @pytest.mark.gpu
 def test_sharded_example_on_one_gpu_matches_the_oracle(tmp_path):
     """examples/sharded_monoslam --gpus 1 --per-gpu 3: ncclCommInitAll on one device, the root's frames to its own block
-    through sl2_scatter_frames, three engines' worth of sequences in one batch, ncclAllGather of xv and Pxx.  (More ranks need
-    more devices than the test box has: the N > 1 partition is the CPU test above, the collectives are RCCL's.)"""
+    through sl2_scatter_frames, three engines' worth of sequences in one batch, ncclAllGather of xv and Pxx.  (More ranks over RCCL need
+    more devices than the test box has; the library's own multi-rank branches run over a stand-in for RCCL in
+    tests/test_gpu_comm_multirank.py.)"""
     import oracle_api as oa
     from mapping_helpers import make_mapping_sequence, oracle_for
     from test_gpu_headless_example import _write_scene
