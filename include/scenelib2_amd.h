@@ -39,7 +39,7 @@ extern "C" {
  * sl2_set_step_fusion, sl2_get_stream, sl2_ingest_set_zero_copy; scenelib2_amd_comm.h.  Additions within 5: sl2_save_sequences,
  * sl2_load_sequences, sl2_copy_sequences, sl2_reset_sequences, sl2_sequence_blob_capacity, sl2_sequence_blob_layout;
  * sl2_snapshot_header.sequence_steps (taken from reserved[]); sl2_set_active_sequences, sl2_get_active_sequences,
- * sl2_ingest_frame_counts, sl2_ingest_next_ragged. */
+ * sl2_ingest_frame_counts, sl2_ingest_next_ragged; sl2_get_step_stats (sl2_step_stats). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -501,6 +501,48 @@ int sl2_delete_features(sl2_engine* e, int seq0, int nseq, const int32_t* labels
  * engine bug, and the sequence's filter is no longer the reference's. */
 #define SL2_STATUS_SMALL_STEP_REFUSED 8
 int sl2_get_status_flags(sl2_engine* e, int seq0, int nseq, int32_t* flags);
+
+/* The filter-consistency record of the last completed update, for a range of sequences in ONE launch (an addition within
+ * SL2_API_VERSION 5).  "Update" = the Kalman update of sl2_go_one_step in every form (ten, six or three launches, captured or
+ * not) or of the seams sl2_make_measurements + sl2_kalman_filter_update.  The update leaves w = L^-1 nu (S = L L^T the joint
+ * innovation covariance of the matched features, nu the stacked innovation) and the diagonal of L^-1 in its workspaces; one
+ * wavefront per sequence forms the record from them on demand (k_step_stats, sl2_stats.hip), FP64 throughout, in a fixed order:
+ * the bytes of a sequence's record do not depend on seq0, nseq, the host or device form, sequence groups, graph replay or how
+ * often the call is made.  A step pays nothing for it when nobody asks.
+ *   nis        = nu^T S^-1 nu = sum w_r^2: chi-square with `dof` degrees of freedom for a consistent filter.  The bounds are
+ *                the caller's business (a table, scipy.stats.chi2); the library ships none.
+ *   log_det_S  = 2 sum log L_rr (a log per pivot, summed): -(nis + log_det_S + dof log 2 pi) / 2 is the step's log-likelihood.
+ *   min_pivot, max_pivot = min / max L_rr, taken as 1 / (L^-1)_rr (the factorisation keeps L's diagonal blocks on chip and
+ *                writes their inverses): (max / min)^2 is a lower bound of cond(S).
+ *   worst_label, worst_feature_d2 = the matched feature with the largest OWN nu_i^T S_i^-1 nu_i (its 2 x 2 S_i and nu_i as
+ *                sl2_feature_info reports them; ties go to the earlier feature of feature_list_) - the first candidate for
+ *                sl2_delete_features when nis is out of bounds.
+ * stepped = 0 for a sequence the update did not run for - paused (sl2_set_active_sequences) in the last step; not stepped since
+ * sl2_create / sl2_load_sequences / sl2_copy_sequences (destination) / sl2_reset_sequences; or refused
+ * (SL2_STATUS_SMALL_STEP_REFUSED) - then dof = 0, worst_label = -1 and the doubles except position_var are zero, while the
+ * counts, status_flags and sequence_steps are live.  An active sequence without a match has stepped = 1, dof = 0.  The record is
+ * STALE between sl2_make_measurements and sl2_kalman_filter_update (dof is the new frame's, w the old one's): ask after the
+ * update.  position_var is read at query time.
+ * out_on_device == 0: one launch into a pinned buffer of the engine's, one stream synchronisation, a copy into out[nseq].
+ * out_on_device != 0: out is device memory (8-byte aligned); the launch only, on the engine's stream, no synchronisation - a
+ * kernel of the caller's on that stream, or sl2_set_active_sequences(on_device = 1), can consume it.  Never drops a captured step. */
+typedef struct sl2_step_stats {        /* 96 bytes, 8-byte aligned */
+  int32_t stepped;          /* 1 = the sequence took part in the last update (active, and stepped since it was loaded / copied in / reset) */
+  int32_t status_flags;     /* SL2_STATUS_* */
+  int32_t sequence_steps;   /* as sl2_snapshot_header.sequence_steps */
+  int32_t n_features;       /* as sl2_snapshot_header.n_features */
+  int32_t n_partial;
+  int32_t n_visible, n_selected, n_matched;   /* number_of_visible_features_, selected_feature_list_.size(), successful features */
+  int32_t dof;              /* rows of the innovation system the update solved: 2 * n_matched, 0 when no update ran */
+  int32_t worst_label;      /* label of the matched feature with the largest own nu_i^T S_i^-1 nu_i; -1 if none */
+  double nis;               /* nu^T S^-1 nu of the joint system */
+  double log_det_S;
+  double min_pivot, max_pivot;   /* min / max L_rr */
+  double worst_feature_d2;  /* that feature's nu_i^T S_i^-1 nu_i, from f_nu and f_S */
+  double position_var;      /* Pxx(0,0) + Pxx(1,1) + Pxx(2,2) after the step */
+  int32_t reserved[2];
+} sl2_step_stats;
+int sl2_get_step_stats(sl2_engine* e, int seq0, int nseq, sl2_step_stats* out, int out_on_device);
 
 /* ------------------------------------------------- save / restore / copy / reset of sequences */
 

@@ -321,6 +321,15 @@ class MonoSLAM {
     map_full_ = (status_flags_ & SL2_STATUS_LABELS_EXHAUSTED) != 0;
   }
 
+  // Not in the reference: the health of the last KalmanFilterUpdate (sl2_get_step_stats) - normalised innovation squared with its
+  // degrees of freedom, log det S, the extreme Cholesky pivots, the worst matched feature, the step's counts.  One launch and
+  // one synchronisation; chi-square bounds on nis are the caller's business.
+  sl2_step_stats StepStats() {
+    sl2_step_stats s;
+    check(sl2_get_step_stats(eng_, 0, 1, &s, 0), "sl2_get_step_stats");
+    return s;
+  }
+
   sl2_engine* engine() { return eng_; }
   // Wall time of the last GoOneStep: the sl2_go_one_step call and the read-back of the public members (one sl2_snapshot).
   // The step is asynchronous, so without measure_timing_ the first figure is its enqueue time and the second one holds the

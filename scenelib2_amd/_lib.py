@@ -85,11 +85,26 @@ class sl2_sequence_blob_header(C.Structure):
          ("n_selected", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class sl2_step_stats(C.Structure):
+    """One sequence's record of sl2_get_step_stats (Engine.step_stats)."""
+    _fields_ = [(n, C.c_int32) for n in ("stepped", "status_flags", "sequence_steps", "n_features", "n_partial", "n_visible",
+                                         "n_selected", "n_matched", "dof", "worst_label")] + \
+        [(n, C.c_double) for n in ("nis", "log_det_S", "min_pivot", "max_pivot", "worst_feature_d2", "position_var")] + \
+        [("reserved", C.c_int32 * 2)]
+
+
+# the same 96 bytes as a NumPy structured dtype (what Engine.step_stats returns)
+STEP_STATS_DTYPE = np.dtype([(n, np.int32) for n in ("stepped", "status_flags", "sequence_steps", "n_features", "n_partial",
+                                                     "n_visible", "n_selected", "n_matched", "dof", "worst_label")] +
+                            [(n, np.float64) for n in ("nis", "log_det_S", "min_pivot", "max_pivot", "worst_feature_d2",
+                                                       "position_var")] + [("reserved", np.int32, (2,))])
+
 SL2_BLOB_MAGIC = 0x51324C53
 SL2_BLOB_SLOT_ARRAYS = 22
 SL2_BLOB_LAYOUT_OFFSETS = 7 + SL2_BLOB_SLOT_ARRAYS
 
 assert C.sizeof(sl2_snapshot_header) == 256 and C.sizeof(sl2_partial_info) == 32 and C.sizeof(sl2_sequence_blob_header) == 256
+assert C.sizeof(sl2_step_stats) == 96 and STEP_STATS_DTYPE.itemsize == 96
 
 # every symbol include/scenelib2_amd.h declares (tests check the .so exports all of them)
 EXPORTED_SYMBOLS = [
@@ -107,6 +122,7 @@ EXPORTED_SYMBOLS = [
     "sl2_sequence_blob_layout", "sl2_sequence_blob_capacity", "sl2_save_sequences", "sl2_load_sequences", "sl2_copy_sequences",
     "sl2_reset_sequences",
     "sl2_set_active_sequences", "sl2_get_active_sequences", "sl2_ingest_frame_counts", "sl2_ingest_next_ragged",
+    "sl2_get_step_stats",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench"]
@@ -222,6 +238,8 @@ def _bind(L):
         L.sl2_get_active_sequences.argtypes = [vp, C.c_int, C.c_int, c_u8p]
         L.sl2_ingest_frame_counts.argtypes = [vp, c_ip, C.c_int]
         L.sl2_ingest_next_ragged.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), c_u8p]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_get_step_stats"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_get_step_stats.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
     return L
 
 

@@ -31,7 +31,7 @@ struct CkptArrays {
   double *x, *P, *prev_r, *last_r, *part_d, *ps_d, *particles, *traj, *pos_log;
   unsigned* slot[kSlotArrays];
   int slot_words[kSlotArrays];
-  int *n_slots, *next_label, *status, *pos_err_any, *n_sel, *n_vis, *m_count, *traj_count, *pos_count, *seq_age, *part_i, *ps_i, *sel_gate, *m_gate;
+  int *n_slots, *next_label, *status, *pos_err_any, *n_sel, *n_vis, *m_count, *traj_count, *pos_count, *seq_age, *part_i, *ps_i, *sel_gate, *m_gate, *step_mark;
   unsigned long long* rand48;
   int N, ld, ppos, kpart, pcap, mapping_used;
   sl2_camera cam;
@@ -259,6 +259,7 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int s
     A.n_slots[b] = ns; A.next_label[b] = qi[1]; A.status[b] = qi[2]; A.pos_err_any[b] = qi[3]; A.n_sel[b] = qi[4]; A.n_vis[b] = qi[5];
     A.m_count[b] = qi[6]; A.traj_count[b] = qi[7];
     A.sel_gate[b] = qi[4]; A.m_gate[b] = qi[6];       // the per-step gates (sl2_common.hpp) follow what they gate: a seam called next finds the loaded frame
+    A.step_mark[b] = 0;                               // ... but the record of sl2_get_step_stats starts again: this sequence has not stepped HERE
     A.rand48[b] = blob ? *reinterpret_cast<const unsigned long long*>(s_seq + 4) : kRand48Seed0;
     for (int k = 0; k < 3; ++k) { A.prev_r[b * 3 + k] = s_seq[5 + k]; A.last_r[b * 3 + k] = s_seq[8 + k]; }
     for (int k = 0; k < kPartDoubles; ++k) A.part_d[(size_t)b * kPartDoubles + k] = s_seq[11 + k];
@@ -305,7 +306,7 @@ static CkptArrays arrays_of(sl2_engine* e) {
   for (int a = 0; a < kSlotArrays; ++a) { A.slot[a] = (unsigned*)slot[a]; A.slot_words[a] = kSlotWords[a]; }
   A.n_slots = e->n_slots; A.next_label = e->next_label; A.status = e->status; A.pos_err_any = e->pos_err_any; A.n_sel = e->n_sel;
   A.n_vis = e->n_vis; A.m_count = e->m_count; A.traj_count = e->traj_count; A.pos_count = e->pos_count; A.seq_age = e->seq_age;
-  A.sel_gate = e->sel_gate; A.m_gate = e->m_gate;
+  A.sel_gate = e->sel_gate; A.m_gate = e->m_gate; A.step_mark = e->step_mark;
   A.part_i = e->part_i; A.ps_i = e->ps_i; A.rand48 = e->rand48;
   A.N = e->N; A.ld = e->ld; A.ppos = e->ppos; A.kpart = e->kpart; A.pcap = e->pcap; A.mapping_used = e->mapping_used ? 1 : 0;
   // (field by field into zeroed structures: the blob's copies carry no padding bytes of the caller's)

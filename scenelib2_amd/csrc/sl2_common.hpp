@@ -171,6 +171,13 @@ struct sl2_engine : sl2::SeqArrays {
   int search_split = sl2::kSrchSplitDefault;   // windows of at least this many 32 x 16 bands are shared out over wavefronts (0 = never); sl2_create: srch_split_default, then sl2_set_search_split
   // ---- large search windows (round 4): the step's units of work for every wavefront of k_search_mfma (layout: kSrchBig* above) ----
   int* srch_big = nullptr;    // per sequence GROUP (allocated by build_groups)
+  // ---- the per-step consistency record (sl2_get_step_stats, sl2_stats.hip) ----
+  // [B] 1 = the sequence took part in the last make_measurements (k_search_score / k_small_back write it next to m_gate: 1 for an
+  // active sequence, 0 for a paused one) and has not been loaded, copied in or reset since (k_seq_unpack clears it).  One word
+  // of engine state OUTSIDE SL2_SEQ_ARRAYS: allocated by sl2_create, a group sees it from its first sequence on (build_groups).
+  int* step_mark = nullptr;
+  void* stats_host = nullptr;      // pinned + mapped host memory the host form of sl2_get_step_stats fills: [B] records (first use)
+  void* stats_host_dev = nullptr;  // its device-side address
 
   // ---- engine-owned staging of the state accessors (no allocation per call; released by sl2_destroy) ----
   void* snap_stage = nullptr;     // device: the packed blob of sl2_snapshot

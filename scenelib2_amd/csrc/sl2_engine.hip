@@ -182,6 +182,7 @@ static int build_groups(sl2_engine* e, int G) {
     g->ppos = e->ppos; g->pcap = e->pcap; g->kpart = e->kpart;
     g->root = e; g->group_first = first;
     static_cast<SeqArrays&>(*g) = seq_arrays_view(*e, dims, first);
+    g->step_mark = e->step_mark + first;       // (not a row of SL2_SEQ_ARRAYS: sl2_common.hpp)
     const int rc = [&]() -> int {
       if (G == 1) g->stream = e->stream; else SL2_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
       // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
@@ -479,6 +480,7 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
 #undef X
   }
   SL2_HIP(hipMemset(e->active, 1, B));                               // every sequence takes part until sl2_set_active_sequences says otherwise
+  { const int r = dmalloc(&e->step_mark, B); if (r != SL2_OK) return r; }      // nobody has stepped yet (sl2_get_step_stats)
   SL2_HIP(hipMalloc((void**)&e->slots_max_dev, sizeof(int) * 2));
   SL2_HIP(hipMemset(e->slots_max_dev, 0, sizeof(int) * 2));
   SL2_HIP(hipHostMalloc((void**)&e->slots_mail, 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
@@ -553,6 +555,8 @@ void sl2_destroy(sl2_engine* e) {
   for (void* p : lazy) if (p) hipFree(p);
   release_checkpoint_staging(e);
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
+  if (e->step_mark) hipFree(e->step_mark);
+  if (e->stats_host) hipHostFree(e->stats_host);
   if (e->slots_mail) hipHostFree(e->slots_mail);
   if (e->snap_stage) hipFree(e->snap_stage);
   if (e->snap_host) hipHostFree(e->snap_host);

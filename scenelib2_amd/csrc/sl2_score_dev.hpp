@@ -10,7 +10,8 @@ namespace sl2 {
 // kernel of the update takes its row count from m_gate and leaves on 0, so x and P of the sequence are not touched while
 // m_count keeps last frame's value for the accessors - and the first sequence of a group returns the step's list of large
 // windows to zero as it always does (the list belongs to the group, not to the sequence).
-__device__ __forceinline__ void search_score_paused(const int b, int* __restrict__ srch_big, int* __restrict__ m_gate) {
+__device__ __forceinline__ void search_score_paused(const int b, int* __restrict__ srch_big, int* __restrict__ m_gate,
+                                                    int* __restrict__ step_mark) {
   const int tid = threadIdx.x;
   if (b == 0 && srch_big) {
     const int nunits_done = min(srch_big[0], kSrchBigUnits), nshared_done = srch_big[3];
@@ -18,7 +19,7 @@ __device__ __forceinline__ void search_score_paused(const int b, int* __restrict
     __syncthreads();                                              // (every thread has read the counters)
     if (tid == 0) { srch_big[1] = nshared_done; srch_big[0] = 0; srch_big[2] = 0; srch_big[3] = 0; }
   }
-  if (tid == 0) m_gate[b] = 0;
+  if (tid == 0) { m_gate[b] = 0; step_mark[b] = 0; }       // step_mark: sl2_get_step_stats' "took part in the last update"
 }
 
 // One workgroup per sequence, one thread per selected position.  Besides the deferred FP64 scores and the reference's
@@ -38,7 +39,8 @@ __device__ __forceinline__ void search_score_body(const int b, const int* __rest
                                                        const int* __restrict__ pos_err, const int* __restrict__ pos_err_any,
                                                        int* __restrict__ f_hcol, const int* __restrict__ ps_i, int kpart, int ppos0,
                                                        int N, int* __restrict__ srch_big, int* __restrict__ status, int* s_flag,
-                                                       int* __restrict__ m_gate, double* s_ext = nullptr) {
+                                                       int* __restrict__ m_gate, int* __restrict__ step_mark,
+                                                       double* s_ext = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = (int)blockDim.x >> 6;
   // s_flag: [N + 8] successful measurement of slot i in this frame (dynamic LDS of the caller)
   __shared__ int s_wcnt[16];
@@ -123,7 +125,7 @@ __device__ __forceinline__ void search_score_body(const int b, const int* __rest
     base += total;
     __syncthreads();
   }
-  if (tid == 0) { m_count[b] = base; m_gate[b] = base; }        // m_gate: what the update chain takes for m_count (search_score_paused)
+  if (tid == 0) { m_count[b] = base; m_gate[b] = base; step_mark[b] = 1; }        // m_gate: what the update chain takes for m_count (search_score_paused)
   for (int off = 32; off > 0; off >>= 1) {
     w_win += __shfl_xor(w_win, off, 64); w_n += __shfl_xor(w_n, off, 64);
     w_cand += __shfl_xor(w_cand, off, 64); w_fb += __shfl_xor(w_fb, off, 64); w_tiles += __shfl_xor(w_tiles, off, 64);

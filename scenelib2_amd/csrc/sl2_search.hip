@@ -1024,12 +1024,13 @@ __global__ void __launch_bounds__(1024) k_search_score(const int* __restrict__ s
                                                        const int* __restrict__ pos_err, const int* __restrict__ pos_err_any,
                                                        int* __restrict__ f_hcol, const int* __restrict__ ps_i, int kpart, int ppos0,
                                                        int N, int* __restrict__ srch_big, int* __restrict__ status,
-                                                       const uint8_t* __restrict__ active, int* __restrict__ m_gate) {
+                                                       const uint8_t* __restrict__ active, int* __restrict__ m_gate,
+                                                       int* __restrict__ step_mark) {
   extern __shared__ int s_flag[];
-  if (!active[blockIdx.x]) { search_score_paused(blockIdx.x, srch_big, m_gate); return; }      // a paused sequence (uniform)
+  if (!active[blockIdx.x]) { search_score_paused(blockIdx.x, srch_big, m_gate, step_mark); return; }      // a paused sequence (uniform)
   search_score_body(blockIdx.x, srch_res, srch_i, patch, f_h, sel_idx, n_sel, f_flags, f_z, f_nu, attempted, successful, meas_ok,
                     meas_score, work, succ_idx, f_arow, m_count, n_slots, pos_err, pos_err_any, f_hcol, ps_i, kpart, ppos0, N,
-                    srch_big, status, s_flag, m_gate);
+                    srch_big, status, s_flag, m_gate, step_mark);
 }
 
 // Stateless batch kernel (C-ABI seam S1): grid (count), one wave per search.  VARIANT 0 = exact, 1 = matrix-core walk.
@@ -1118,7 +1119,7 @@ int launch_search_score(sl2_engine* e) {
     if (e->root->score_threads > 0) threads = e->root->score_threads;     // experiments (SL2_SCORE_THREADS)
     hipLaunchKernelGGL(k_search_score, dim3(e->B), dim3(threads), sizeof(int) * (e->N + 8), e->stream, e->srch_res, e->srch_i, e->patch, e->f_h, e->sel_idx,
                        e->n_sel, e->f_flags, e->f_z, e->f_nu, e->attempted, e->successful, e->meas_ok, e->meas_score, e->work,
-                       e->succ_idx, e->f_arow, e->m_count, e->n_slots, e->pos_err, e->pos_err_any, e->f_hcol, e->ps_i, e->kpart, e->ppos, e->N, e->srch_big, e->status, e->active, e->m_gate);
+                       e->succ_idx, e->f_arow, e->m_count, e->n_slots, e->pos_err, e->pos_err_any, e->f_hcol, e->ps_i, e->kpart, e->ppos, e->N, e->srch_big, e->status, e->active, e->m_gate, e->step_mark);
     SL2_HIP(hipGetLastError());
   }
   return SL2_OK;

@@ -78,7 +78,8 @@ __device__ __forceinline__ void small_update_body(const int b, double* __restric
                                                   const int* __restrict__ succ_idx, const int* __restrict__ m_count,
                                                   const int* __restrict__ n_slots, const int* __restrict__ part_i, int ppos, int pend,
                                                   const int* __restrict__ pos_err_any, const int* __restrict__ f_hcol,
-                                                  int N, int ld, unsigned lds_bytes, int* __restrict__ status, double* sAt) {
+                                                  int N, int ld, unsigned lds_bytes, int* __restrict__ status, double* sAt,
+                                                  double* __restrict__ Vt, double* __restrict__ LinvT) {
   __shared__ double sH[kSmallM][10];
   __shared__ double sR[kSmallM];
   __shared__ int sPos[kSmallM];
@@ -215,6 +216,12 @@ __device__ __forceinline__ void small_update_body(const int b, double* __restric
     }
   }
   __syncthreads();
+  // what sl2_get_step_stats reads of an update (sl2_stats.hip), where the ten-launch chain leaves it: w = L^-1 nu in the last column
+  // of V^T's rows, and the diagonal of L^-1 in the inverted diagonal block (this system is one block: mld = 32, LinvT[b][p][k])
+  if (tid < m) {
+    Vt[((size_t)b * kSmallM + tid) * ld + ld - 1] = sAt[tid * W + W - 1];
+    LinvT[(size_t)b * 1024 + tid * 33] = sLinv[tid * kLinvPitch + tid];
+  }
   SST(4, 3);
   // ---- P -= V^T V (both triangles; the same products in the same order on either side of the diagonal, so mirrored entries
   // stay equal bit for bit), 4 x 4 outputs per thread; x += V^T w with w = L^-1 nu = the last column of V
@@ -268,11 +275,12 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
     double* __restrict__ traj, int* __restrict__ traj_count, const double* __restrict__ last_r, double* __restrict__ pos_log,
     int* __restrict__ pos_count, int min_attempts, double match_fraction, int save_trajectory, int* __restrict__ slots_max,
     unsigned long long* __restrict__ slots_mail, int publish, unsigned lds_bytes,
-    const uint8_t* __restrict__ active, int* __restrict__ m_gate, int* __restrict__ seq_age) {
+    const uint8_t* __restrict__ active, int* __restrict__ m_gate, int* __restrict__ seq_age,
+    int* __restrict__ step_mark, double* __restrict__ Vt, double* __restrict__ LinvT) {
   extern __shared__ double s_dynd[];                  // phase by phase: [N + 8] ints, [32][128] doubles, [2 N] ints
   const int b = blockIdx.x;
   if (!active[b]) {                                   // a paused sequence (uniform): the group's list of large windows and the step clock only
-    search_score_paused(b, srch_big, m_gate);
+    search_score_paused(b, srch_big, m_gate, step_mark);
     finalize_paused(b, x, n_slots, pos_log, pos_count, seq_age, ld, slots_max, slots_mail, publish);
     return;
   }
@@ -283,11 +291,11 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
   double* const s_ext_final = s_dynd + (size_t)N;
   search_score_body<true>(b, srch_res, srch_i, patch, f_h, sel_idx, n_sel, f_flags, f_z, f_nu, attempted, successful, meas_ok, meas_score,
                           work, succ_idx, f_arow, m_count, n_slots, pos_err, pos_err_any, f_hcol, ps_i, kpart, ppos0, N, srch_big, status,
-                          (int*)s_dynd, m_gate, s_ext_score);
+                          (int*)s_dynd, m_gate, step_mark, s_ext_score);
   __syncthreads();
   SST(3, 1);
   small_update_body(b, x, P, f_Hx, f_Hy, f_nu, f_R, succ_idx, m_count, n_slots, part_i, ppos0, pend, pos_err_any, f_hcol, N, ld, lds_bytes,
-                    status, s_dynd);
+                    status, s_dynd, Vt, LinvT);
   __syncthreads();
   SST(3, 2);
   finalize_body<true>(b, x, P, f_flags, n_slots, attempted, successful, m_count, n_sel, traj, traj_count, last_r, status, pos_log,
@@ -345,7 +353,7 @@ int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound) {
                      e->N, e->srch_big, e->status, e->x, e->P, e->f_Hx, e->f_Hy, e->f_R, e->part_i, e->ppos + 6 * e->kpart, e->ld,
                      e->traj, e->traj_count, e->last_r, e->pos_log, e->pos_count, e->prm.minimum_attempted_measurements_of_feature,
                      e->prm.successful_match_fraction, save_trajectory, e->root->slots_max_dev, e->root->slots_mail_dev,
-                     e->group_first == 0 ? 1 : 0, (unsigned)shm, e->active, e->m_gate, e->seq_age);
+                     e->group_first == 0 ? 1 : 0, (unsigned)shm, e->active, e->m_gate, e->seq_age, e->step_mark, e->Vt, e->LinvT);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }

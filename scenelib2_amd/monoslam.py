@@ -322,6 +322,23 @@ class Engine:
         self._ck(self.L.sl2_get_status_flags(self.h, 0, self.batch, _lib.ip(out)))
         return out
 
+    def step_stats(self, seq0=0, nseq=None):
+        """The filter-consistency record of the last completed update for sequences [seq0, seq0 + nseq) in ONE launch and one
+        synchronisation (sl2_get_step_stats): a NumPy structured array (_lib.STEP_STATS_DTYPE) with fields stepped,
+        status_flags, sequence_steps, n_features, n_partial, n_visible, n_selected, n_matched, dof, worst_label, nis, log_det_S,
+        min_pivot, max_pivot, worst_feature_d2, position_var.  nis is chi-square with dof degrees of freedom for a consistent
+        filter; the bounds are the caller's (scipy.stats.chi2.ppf, or a table)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        out = np.zeros(max(nseq, 1), dtype=_lib.STEP_STATS_DTYPE)
+        self._ck(self.L.sl2_get_step_stats(self.h, int(seq0), nseq, out.ctypes.data_as(_lib.vp), 0))
+        return out[:nseq]
+
+    def step_stats_device(self, dev_ptr, seq0=0, nseq=None):
+        """The same records into device memory (96 bytes each, 8-byte aligned): the launch only, on the engine's stream, no
+        synchronisation - for a policy kernel of the caller's, or set_active(on_device=True)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        self._ck(self.L.sl2_get_step_stats(self.h, int(seq0), nseq, _lib.vp(int(dev_ptr)), 1))
+
     # ---- save / restore / copy / reset of sequences (sl2_save_sequences ...) -------
     def sequence_blob_capacity(self):
         """Upper bound in bytes of one sequence blob of this engine (a multiple of 64)."""
@@ -574,6 +591,13 @@ class MonoSLAM:
     @property
     def successful_measurement_vector_size_(self):
         return self._engine.selection(0)[1]["measurement_size"]
+
+    # Not in the reference: the health of the last KalmanFilterUpdate (sl2_get_step_stats) as a dict - nis, dof, log_det_S,
+    # min_pivot, max_pivot, worst_label, worst_feature_d2, position_var and the step's counts
+    @property
+    def step_stats_(self):
+        r = self._engine.step_stats(0, 1)[0]
+        return {n: r[n].item() for n in r.dtype.names if n != "reserved"}
 
     @property
     def total_state_size_(self):
