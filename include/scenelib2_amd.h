@@ -39,7 +39,8 @@ extern "C" {
  * sl2_set_step_fusion, sl2_get_stream, sl2_ingest_set_zero_copy; scenelib2_amd_comm.h.  Additions within 5: sl2_save_sequences,
  * sl2_load_sequences, sl2_copy_sequences, sl2_reset_sequences, sl2_sequence_blob_capacity, sl2_sequence_blob_layout;
  * sl2_snapshot_header.sequence_steps (taken from reserved[]); sl2_set_active_sequences, sl2_get_active_sequences,
- * sl2_ingest_frame_counts, sl2_ingest_next_ragged; sl2_get_step_stats (sl2_step_stats). */
+ * sl2_ingest_frame_counts, sl2_ingest_next_ragged; sl2_get_step_stats (sl2_step_stats); sl2_set_delta_t, sl2_get_delta_t,
+ * sl2_set_pause_catch_up (the time step is the sequence's: sl2_params.delta_t is its initial value). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -67,7 +68,7 @@ typedef struct sl2_camera {
 /* cfg keys params.* (data/SceneLib2.cfg:59-69, monoslam.cpp:1583-1593) plus the two
  * hard-wired deletion constants (monoslam.cpp:1875-1876). */
 typedef struct sl2_params {
-  double delta_t;
+  double delta_t; /* the initial time step of every sequence; sl2_set_delta_t gives a sequence its own */
   int32_t number_of_features_to_select;
   int32_t number_of_features_to_keep_visible;
   int32_t max_features_to_init_at_once;
@@ -182,8 +183,9 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
  * clock is shared, so three things do move: the position log gets one more entry that repeats the unchanged camera position
  * (it stays aligned with the engine's steps), the sequence's own step count (sl2_sequence_blob_header.sequence_steps,
  * sl2_snapshot_header.sequence_steps) stands still while the engine's advances, and the sequence's map size still counts
- * towards the engine's choice of step kernels.  A sequence that is resumed predicts over one delta_t, as the reference does
- * when it is handed the next frame.  The bytes of a paused sequence's frame are not read.
+ * towards the engine's choice of step kernels.  A sequence that is resumed predicts over one nominal step of its own (sl2_set_delta_t) by
+ * default, as the reference does when it is handed the next frame, or over the nominal step plus the time owed by the predicts
+ * it skipped with catch-up on (sl2_set_pause_catch_up).  The bytes of a paused sequence's frame are not read.
  * The mask is not part of a sequence blob (it belongs to the engine that steps, not to the sequence) and is left alone by
  * sl2_load_sequences / sl2_copy_sequences / sl2_reset_sequences.  It is consulted by STEPS only: sl2_add_known_features,
  * sl2_set_vehicle_state, sl2_set_feature_covariances, sl2_delete_features, sl2_initialise_feature,
@@ -199,6 +201,34 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
 int sl2_set_active_sequences(sl2_engine* e, int seq0, int nseq, const uint8_t* active, int on_device);
 /* sl2_get_active_sequences: the mask as the steps queued so far leave it (1 / 0 per sequence), to host memory.  Synchronises. */
 int sl2_get_active_sequences(sl2_engine* e, int seq0, int nseq, uint8_t* active);
+
+/* The time step is the sequence's.  Every sequence has a record of engine state on the device: its nominal time step
+ * (sl2_params.delta_t after sl2_create), the time owed by predicts it skipped while paused, and the step its last predict used.
+ * A predict - sl2_kalman_filter_predict and sl2_go_one_step in every form - moves sequence b over nominal + owed, notes that as
+ * the step it used and clears what was owed; with nothing owed that is the nominal step, bit for bit.  The feature-
+ * initialisation tail divides the camera's displacement by the step the last predict used - the nominal step while the sequence
+ * has not predicted in this engine yet - (the 0.2 m/s speed gate) and looks
+ * ten NOMINAL steps ahead for its search region.  Like the mask, the record belongs to the engine that steps: it is in no
+ * sequence blob and sl2_load_sequences / sl2_copy_sequences / sl2_reset_sequences leave it alone.
+ *
+ * sl2_set_delta_t: dt[i] becomes the nominal step of sequence seq0 + i, and what that sequence was owed is cleared.  on_device
+ * == 0: `dt` is host memory of any kind and is consumed before the call returns; on_device != 0: a device pointer, read by a
+ * copy kernel on the engine's stream (keep it alive and unchanged until the stream has passed this point).  Either way the
+ * change is ordered on the engine's stream: after every step already queued, before the next one.  The call never waits for the
+ * device and drops no captured step (the record is data a replayed graph reads, not part of its key).  The mask is not
+ * consulted: a paused sequence can be given its time step before it resumes.  SL2_ERR_INVALID, and nothing changed: a range
+ * outside the batch, a null pointer, or - host form - any value that is not finite or is <= 0.  The device form cannot refuse:
+ * it SKIPS such entries, and those sequences keep the step they had. */
+int sl2_set_delta_t(sl2_engine* e, int seq0, int nseq, const double* dt, int on_device);
+/* sl2_get_delta_t: the record as the steps and setters queued so far leave it, to host memory: the nominal step, the time owed
+ * and the step the last predict used (0 before the first) of each sequence.  owed and last_used may be NULL.  Synchronises. */
+int sl2_get_delta_t(sl2_engine* e, int seq0, int nseq, double* dt, double* owed, double* last_used);
+/* sl2_set_pause_catch_up: enabled != 0 = from now on every predict a paused sequence sits out adds its nominal step to what
+ * the sequence is owed, so the predict that resumes it covers the whole gap (a camera that dropped frames); this one word is the
+ * only thing of a paused sequence a step then moves.  0 (the default) = a paused sequence is owed nothing, and what any
+ * sequence was owed is cleared.  For the whole batch, by a kernel on the engine's stream: ordered like sl2_set_delta_t, never
+ * waits, drops no captured step. */
+int sl2_set_pause_catch_up(sl2_engine* e, int enabled);
 
 /* The seams of GoOneStep, individually callable (same order as the reference):
  *   Kalman::KalmanFilterPredict(monoslam,u=0)            kalman.cpp:50-69
@@ -623,7 +653,9 @@ int sl2_save_sequences(sl2_engine* e, int seq0, int nseq, void* blobs, size_t bl
  * captured step graphs are dropped. */
 int sl2_load_sequences(sl2_engine* e, int seq0, int nseq, const void* blobs, size_t blob_stride, int blobs_on_device);
 /* Save + load without the host, between two engines on one device or inside one engine (overlapping ranges: SL2_ERR_INVALID).
- * Engines on different streams are ordered by an event.  The destination is treated as by sl2_load_sequences. */
+ * Engines on different streams are ordered by an event.  The destination is treated as by sl2_load_sequences, except that the two
+ * engines' params.delta_t need not agree: the time step is the destination's own record (sl2_set_delta_t) and is not copied, so
+ * engines created for cameras of different rates can hand sequences to each other. */
 int sl2_copy_sequences(sl2_engine* dst, int dst_seq0, sl2_engine* src, int src_seq0, int nseq);
 /* The sequences become what sl2_create left: empty map, next_free_label_ 0, counters, status, trajectory store, position log
  * and partial features cleared, drand48 as after srand48(0) (monoslam.cpp:1968), x and P zero.  The caller then sets the

@@ -168,6 +168,13 @@ class MonoSLAM {
   // The stream the engine steps on: what sl2_ingest_next wants, so that the upload of the next frame runs under this one's step.
   void* stream() const { return eng_ ? sl2_get_stream(eng_) : nullptr; }
 
+  // kDeltaT_ from the next GoOneStep on (the reference fixes it at Init; a camera whose frame rate changes does not).
+  void SetDeltaT(double delta_t) {
+    if (!eng_) throw std::runtime_error("MonoSLAM::SetDeltaT: call Init first");
+    check(sl2_set_delta_t(eng_, 0, 1, &delta_t, 0), "sl2_set_delta_t");
+    kDeltaT_ = delta_t;
+  }
+
   // MonoSLAM::GoOneStep (monoslam.cpp:108-180).  Always true, like the reference (:179).
   bool GoOneStep(const Frame& frame, bool save_trajectory, bool enable_mapping) {
     if (!eng_ || !frame.data || frame.cols != camera_->width_ || frame.rows != camera_->height_)

@@ -22,6 +22,10 @@ int sl2_set_feature_counters(sl2_engine* e, int seq, int label, int attempted, i
  * (SL2_STATUS_REFERENCE_OUT_OF_BOUNDS) without the dozen conversions that would take.  Synchronises. */
 int sl2_debug_set_position_error(sl2_engine* e, int seq, int label, int err);
 
+/* How many steps this engine has captured into graphs since sl2_create (sl2_set_graph_mode): a step that is replayed does not
+ * count, one that had to be captured again - because a setter dropped the graphs, or the step's key changed - does. */
+int sl2_debug_graph_captures(sl2_engine* e);
+
 /* FP64 epilogue of correlate2_warning (improc.cpp:99-133) evaluated ON THE DEVICE
  * for `count` tuples of the five integer sums: checks IEEE div/sqrt parity. */
 int sl2_debug_ncc_score(int device, const int32_t* sums5, int count, double* score, double* sd0, double* sd1);

@@ -123,9 +123,10 @@ EXPORTED_SYMBOLS = [
     "sl2_reset_sequences",
     "sl2_set_active_sequences", "sl2_get_active_sequences", "sl2_ingest_frame_counts", "sl2_ingest_next_ragged",
     "sl2_get_step_stats",
+    "sl2_set_delta_t", "sl2_get_delta_t", "sl2_set_pause_catch_up",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
-TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench"]
+TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
 TEST_LIB_PATH = os.path.join(_HERE, "libscenelib2_amd_test.so")
 _testlib = None
 
@@ -240,6 +241,10 @@ def _bind(L):
         L.sl2_ingest_next_ragged.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), c_u8p]
     if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_get_step_stats"):      # (an older build under test, scripts/ab_libs.sh)
         L.sl2_get_step_stats.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_set_delta_t"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_set_delta_t.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
+        L.sl2_get_delta_t.argtypes = [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp]
+        L.sl2_set_pause_catch_up.argtypes = [vp, C.c_int]
     return L
 
 
@@ -261,6 +266,7 @@ def load_testing():
     T.sl2_debug_ncc_score.argtypes = [C.c_int, c_ip, C.c_int, c_dp, c_dp, c_dp]
     T.sl2_debug_gemm_kt.argtypes = [C.c_int, c_dp, C.c_int, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, C.c_int]
     T.sl2_debug_microbench.argtypes = [C.c_int, C.c_int, c_dp]
+    T.sl2_debug_graph_captures.argtypes = [vp]
     _testlib = T
     return T
 

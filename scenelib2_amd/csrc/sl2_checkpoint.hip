@@ -380,7 +380,10 @@ static int refuse(int code, int index, const char* field, const char* what) {
 }
 
 // Does blob `index` (its header; `avail` bytes of it exist) describe a well-formed blob that fits engine e?
-static int check_header(sl2_engine* e, const sl2_sequence_blob_header& h, size_t avail, int index) {
+// (engine_to_engine: sl2_copy_sequences.  The time step is the destination's own record and travels in no blob, so two
+// engines created with different params.delta_t - cameras of different rates - may still hand sequences to each other; a blob
+// from outside is held to every word of params as before.)
+static int check_header(sl2_engine* e, const sl2_sequence_blob_header& h, size_t avail, int index, bool engine_to_engine = false) {
   if (h.magic != SL2_BLOB_MAGIC) return refuse(SL2_ERR_INVALID, index, "magic", "not a sequence blob");
   if (h.layout_version != SL2_BLOB_LAYOUT_VERSION) return refuse(SL2_ERR_INVALID, index, "layout_version", "unknown layout");
   if (h.n_slots < 0 || h.n_slots > 676) return refuse(SL2_ERR_INVALID, index, "n_slots", "out of range");
@@ -401,6 +404,7 @@ static int check_header(sl2_engine* e, const sl2_sequence_blob_header& h, size_t
   sl2_params p = h.params;
   p.max_features_to_init_at_once = A.prm.max_features_to_init_at_once;
   p.number_of_features_to_select = A.prm.number_of_features_to_select;
+  if (engine_to_engine) p.delta_t = A.prm.delta_t;
   if (memcmp(&p, &A.prm, sizeof(sl2_params)) != 0) return refuse(SL2_ERR_INVALID, index, "params", "differ from the engine's");
   if (h.n_slots > e->N) return refuse(SL2_ERR_CAPACITY, index, "n_slots", "more feature slots than the engine's max_features");
   if (h.n_partial_slots > e->kpart) return refuse(SL2_ERR_CAPACITY, index, "n_partial_slots", "more partial slots than the engine's max_features_to_init_at_once");
@@ -520,7 +524,7 @@ int sl2_copy_sequences(sl2_engine* dst, int dst_seq0, sl2_engine* src, int src_s
     SL2_HIP(hipStreamSynchronize(src->stream));
   }
   for (int i = 0; i < nseq; ++i) {
-    const int rc = check_header(dst, hs[i], cap, i);
+    const int rc = check_header(dst, hs[i], cap, i, true);
     if (rc != SL2_OK) return rc;
     mapping = mapping || hs[i].mapping_in_use != 0;
   }

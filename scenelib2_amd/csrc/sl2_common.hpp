@@ -66,6 +66,8 @@ constexpr int kSrchBigEntries = 4;                    // int offsets into srch_b
 constexpr int kSrchBigDone = kSrchBigEntries + 4 * kSrchBigUnits;
 constexpr int kSrchBigParts = kSrchBigDone + kSrchBigUnits;
 constexpr int kSrchBigInts = kSrchBigParts + 8 * kSrchBigUnits;
+// seq_time, the per-sequence time record (sl2_engine::seq_time): doubles per sequence and their places
+constexpr int kSeqTimeDoubles = 4, kSeqTimeNominal = 0, kSeqTimeOwed = 1, kSeqTimeUsed = 2, kSeqTimeCatchUp = 3;
 __host__ __device__ inline int srch_unit_bands(int bands) { const int g = (bands + kSrchBigSlots - 1) / kSrchBigSlots; return g > kSrchBigMinBands ? g : kSrchBigMinBands; }
 // Partially initialised features: up to kMaxPartial per sequence (params.max_features_to_init_at_once, monoslam.cpp:163-167).
 // part_i / part_d = the per-SEQUENCE record: feature_init_info_vector_.size(), the partial slots in the vector's order (a
@@ -140,6 +142,7 @@ struct sl2_engine : sl2::SeqArrays {
   struct StepGraph { const void* frames; size_t stride; int save_trajectory, enable_mapping, tail, small; hipGraphExec_t exec; };
   bool graph_mode = false;
   std::vector<StepGraph> step_graphs;
+  long long graph_captures = 0;   // steps captured so far (TEST build: sl2_debug_graph_captures - a setter that says it drops no captured step is held to it)
   int build_split = 0;        // development switches (TEST build only: SL2_BUILD_SPLIT, SL2_SCORE_THREADS, SL2_NO_KSPLIT read
   int score_threads = 0;      // once at sl2_create): 0 = the engine's own choice
   int no_ksplit = 0;
@@ -176,6 +179,13 @@ struct sl2_engine : sl2::SeqArrays {
   // active sequence, 0 for a paused one) and has not been loaded, copied in or reset since (k_seq_unpack clears it).  One word
   // of engine state OUTSIDE SL2_SEQ_ARRAYS: allocated by sl2_create, a group sees it from its first sequence on (build_groups).
   int* step_mark = nullptr;
+  // ---- the per-sequence time step (sl2_set_delta_t) ----
+  // [B][kSeqTimeDoubles]: [0] the sequence's nominal time step (params.delta_t after sl2_create), [1] time owed by predicts a
+  // paused sequence skipped (catch-up on only), [2] the step its last predict used (the speed gate of k_map_find divides by it),
+  // [3] the catch-up switch, 0 or 1.  Read and written by predict_body and the paused branch of its two kernels; the setters
+  // write it with kernels on the engine's stream, so a captured step reads it as data.  Engine state like step_mark: outside
+  // SL2_SEQ_ARRAYS, in no sequence blob, a group sees it from its first sequence on (build_groups).
+  double* seq_time = nullptr;
   void* stats_host = nullptr;      // pinned + mapped host memory the host form of sl2_get_step_stats fills: [B] records (first use)
   void* stats_host_dev = nullptr;  // its device-side address
 

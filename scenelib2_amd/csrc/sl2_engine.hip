@@ -183,6 +183,7 @@ static int build_groups(sl2_engine* e, int G) {
     g->root = e; g->group_first = first;
     static_cast<SeqArrays&>(*g) = seq_arrays_view(*e, dims, first);
     g->step_mark = e->step_mark + first;       // (not a row of SL2_SEQ_ARRAYS: sl2_common.hpp)
+    g->seq_time = e->seq_time + kSeqTimeDoubles * first;      // (nor is the time record)
     const int rc = [&]() -> int {
       if (G == 1) g->stream = e->stream; else SL2_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
       // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
@@ -481,6 +482,12 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
   }
   SL2_HIP(hipMemset(e->active, 1, B));                               // every sequence takes part until sl2_set_active_sequences says otherwise
   { const int r = dmalloc(&e->step_mark, B); if (r != SL2_OK) return r; }      // nobody has stepped yet (sl2_get_step_stats)
+  {   // every sequence starts on the engine's time step: nothing owed, no predict yet, catch-up off (sl2_set_delta_t)
+    const int r = dmalloc(&e->seq_time, B * kSeqTimeDoubles); if (r != SL2_OK) return r;
+    std::vector<double> rec(B * kSeqTimeDoubles, 0.0);
+    for (size_t b = 0; b < B; ++b) rec[b * kSeqTimeDoubles + kSeqTimeNominal] = e->prm.delta_t;
+    SL2_HIP(hipMemcpy(e->seq_time, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
+  }
   SL2_HIP(hipMalloc((void**)&e->slots_max_dev, sizeof(int) * 2));
   SL2_HIP(hipMemset(e->slots_max_dev, 0, sizeof(int) * 2));
   SL2_HIP(hipHostMalloc((void**)&e->slots_mail, 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
@@ -556,6 +563,7 @@ void sl2_destroy(sl2_engine* e) {
   release_checkpoint_staging(e);
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
   if (e->step_mark) hipFree(e->step_mark);
+  if (e->seq_time) hipFree(e->seq_time);
   if (e->stats_host) hipHostFree(e->stats_host);
   if (e->slots_mail) hipHostFree(e->slots_mail);
   if (e->snap_stage) hipFree(e->snap_stage);
@@ -744,6 +752,80 @@ int sl2_get_active_sequences(sl2_engine* e, int seq0, int nseq, uint8_t* active)
   SL2_HIP(hipSetDevice(e->device));
   { int _rc = e->sync_all(); if (_rc != SL2_OK) return _rc; }
   SL2_HIP(hipMemcpy(active, e->active + seq0, (size_t)nseq, hipMemcpyDeviceToHost));
+  return SL2_OK;
+}
+
+// ------------------------------------------------------------------- the per-sequence time step
+
+// Like the mask, the host form travels in the launch's own arguments (kDtChunk sequences a launch): consumed before the call
+// returns, nothing staged, nothing waited for.  A valid step is finite and > 0; the host form has refused anything else
+// before it launches, the device form leaves such a sequence as it was.
+constexpr int kDtChunk = 256;
+struct DtChunk { double v[kDtChunk]; };
+__device__ __forceinline__ void set_dt_one(double* __restrict__ rec, double v) {
+  if (!(v > 0.0) || !(v <= 1.7976931348623157e308)) return;       // NaN, <= 0, infinite
+  rec[kSeqTimeNominal] = v;
+  rec[kSeqTimeOwed] = 0.0;
+}
+__global__ void __launch_bounds__(256) k_set_dt_args(double* __restrict__ seq_time, DtChunk c, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) set_dt_one(seq_time + (size_t)i * kSeqTimeDoubles, c.v[i]);
+}
+__global__ void __launch_bounds__(256) k_set_dt_dev(double* __restrict__ seq_time, const double* __restrict__ src, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) set_dt_one(seq_time + (size_t)i * kSeqTimeDoubles, src[i]);
+}
+__global__ void __launch_bounds__(256) k_set_catch_up(double* __restrict__ seq_time, int enabled, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  double* rec = seq_time + (size_t)i * kSeqTimeDoubles;
+  rec[kSeqTimeCatchUp] = enabled ? 1.0 : 0.0;
+  if (!enabled) rec[kSeqTimeOwed] = 0.0;
+}
+
+int sl2_set_delta_t(sl2_engine* e, int seq0, int nseq, const double* dt, int on_device) {
+  if (!range_ok(e, seq0, nseq) || !dt) return SL2_ERR_INVALID;
+  SL2_HIP(hipSetDevice(e->device));
+  // on the engine's stream, outside any captured step, like the mask (sl2_set_active_sequences): the record is data a replayed
+  // graph reads
+  double* rec0 = e->seq_time + (size_t)seq0 * kSeqTimeDoubles;
+  if (on_device) {
+    hipLaunchKernelGGL(k_set_dt_dev, dim3((nseq + 255) / 256), dim3(256), 0, e->stream, rec0, dt, nseq);
+    SL2_HIP(hipGetLastError());
+    return SL2_OK;
+  }
+  for (int i = 0; i < nseq; ++i)
+    if (!std::isfinite(dt[i]) || !(dt[i] > 0.0)) { set_error("sl2_set_delta_t: a time step must be finite and > 0"); return SL2_ERR_INVALID; }
+  for (int c0 = 0; c0 < nseq; c0 += kDtChunk) {
+    const int cnt = nseq - c0 < kDtChunk ? nseq - c0 : kDtChunk;
+    DtChunk c;
+    memset(&c, 0, sizeof(c));
+    memcpy(c.v, dt + c0, sizeof(double) * cnt);
+    hipLaunchKernelGGL(k_set_dt_args, dim3((cnt + 255) / 256), dim3(256), 0, e->stream, rec0 + (size_t)c0 * kSeqTimeDoubles, c, cnt);
+    SL2_HIP(hipGetLastError());
+  }
+  return SL2_OK;
+}
+
+int sl2_get_delta_t(sl2_engine* e, int seq0, int nseq, double* dt, double* owed, double* last_used) {
+  if (!range_ok(e, seq0, nseq) || !dt) return SL2_ERR_INVALID;
+  SL2_HIP(hipSetDevice(e->device));
+  { int _rc = e->sync_all(); if (_rc != SL2_OK) return _rc; }
+  std::vector<double> rec;
+  { int _rc = fetch_vec(rec, e->seq_time, (size_t)seq0 * kSeqTimeDoubles, (size_t)nseq * kSeqTimeDoubles); if (_rc != SL2_OK) return _rc; }
+  for (int i = 0; i < nseq; ++i) {
+    dt[i] = rec[(size_t)i * kSeqTimeDoubles + kSeqTimeNominal];
+    if (owed) owed[i] = rec[(size_t)i * kSeqTimeDoubles + kSeqTimeOwed];
+    if (last_used) last_used[i] = rec[(size_t)i * kSeqTimeDoubles + kSeqTimeUsed];
+  }
+  return SL2_OK;
+}
+
+int sl2_set_pause_catch_up(sl2_engine* e, int enabled) {
+  if (!e) return SL2_ERR_INVALID;
+  SL2_HIP(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_set_catch_up, dim3((e->B + 255) / 256), dim3(256), 0, e->stream, e->seq_time, enabled ? 1 : 0, e->B);
+  SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 
@@ -1004,6 +1086,7 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
         SL2_HIP(ce);
       }
       SL2_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+      e->graph_captures += 1;
       hipGraphDestroy(graph);
       if (e->step_graphs.size() >= 8) { hipGraphExecDestroy(e->step_graphs.front().exec); e->step_graphs.erase(e->step_graphs.begin()); }
       e->step_graphs.push_back({(const void*)frames, seq_stride, save_trajectory, enable_mapping, (int)tail, (int)small_any, exec});
@@ -1307,6 +1390,8 @@ int sl2_get_position_log(sl2_engine* e, int seq0, int nseq, double* out, int cap
 }
 
 #ifdef SL2_TESTING   // test hook: libscenelib2_amd_test.so only (include/scenelib2_amd_testing.h)
+int sl2_debug_graph_captures(sl2_engine* e) { return e ? (int)e->graph_captures : -1; }
+
 int sl2_set_feature_counters(sl2_engine* e, int seq, int label, int attempted, int successful) {
   if (!range_ok(e, seq, 1) || label < 0) return SL2_ERR_INVALID;
   SL2_HIP(hipSetDevice(e->device));

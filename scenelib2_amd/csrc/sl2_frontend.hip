@@ -13,9 +13,9 @@ namespace sl2 {
 
 __global__ void __launch_bounds__(256) k_predict(double* __restrict__ x, double* __restrict__ P, const int* __restrict__ n_slots,
                                                  double* __restrict__ prev_r, const int* __restrict__ part_i, int pend, int ld,
-                                                 double dt, const uint8_t* __restrict__ active) {
-  if (!active[blockIdx.x]) return;           // a paused sequence (uniform)
-  predict_body(blockIdx.x, x, P, n_slots, prev_r, part_i, pend, ld, dt);
+                                                 double* __restrict__ seq_time, const uint8_t* __restrict__ active) {
+  if (!active[blockIdx.x]) { predict_paused(blockIdx.x, seq_time); return; }      // a paused sequence (uniform)
+  predict_body(blockIdx.x, x, P, n_slots, prev_r, part_i, pend, ld, seq_time);
 }
 
 __global__ void __launch_bounds__(64) k_feature_prediction(const double* __restrict__ x, const double* __restrict__ P,
@@ -70,7 +70,7 @@ namespace sl2 {
 int launch_predict(sl2_engine* e) {
   LaunchScope ls(e, "k_predict");
   hipLaunchKernelGGL(k_predict, dim3(e->B), dim3(256), 0, e->stream, e->x, e->P, e->n_slots, e->prev_r, e->part_i, e->ppos + 6 * e->kpart, e->ld,
-                     e->prm.delta_t, e->active);
+                     e->seq_time, e->active);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }

@@ -23,10 +23,13 @@ static __device__ long long* g_front_trace = nullptr;        // development only
 // ---------------------------------------------------------------------------
 // k_predict: one workgroup per sequence.  Only the first 13 rows/cols of P change
 // (static map): Pxx <- (F Pxx) F^T + Q, strip P[0:13, j] <- F P[0:13, j], mirrored.
+// The time step is the sequence's own (seq_time, sl2_common.hpp): the nominal step plus whatever paused predicts left owed.
+// Thread 0 alone touches the record - it reads it next to the state, notes the step it uses and clears the debt - and hands
+// dt to the others through LDS beside s_f, so no thread can read a word another has already rewritten.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void predict_body(const int b, double* __restrict__ x, double* __restrict__ P, const int* __restrict__ n_slots,
                                                  double* __restrict__ prev_r, const int* __restrict__ part_i, int pend, int ld,
-                                                 double dt) {
+                                                 double* __restrict__ seq_time) {
   const int tid = threadIdx.x;
   double* xb = x + (size_t)b * ld;
   double* Pb = P + (size_t)b * ld * ld;
@@ -37,18 +40,24 @@ __device__ __forceinline__ void predict_body(const int b, double* __restrict__ x
   // the first batch of strip columns is fetched now: its memory latency hides behind the serial motion model
   double v0[13];
   for (int k = 0; k < 13; ++k) v0[k] = (13 + tid < n_used) ? Pb[(size_t)k * ld + 13 + tid] : 0.0;
-  __shared__ double s_f[13], s_A[16], s_B[12], s_P[169], s_T[169];
+  __shared__ double s_f[13], s_A[16], s_B[12], s_P[169], s_T[169], s_dt;
   if (tid == 0) {
+    double* rec = seq_time + (size_t)b * kSeqTimeDoubles;
+    const double dt0 = rec[kSeqTimeNominal] + rec[kSeqTimeOwed];      // (nothing owed: nominal + 0.0, the nominal step's own bits)
     double xv[13];
     for (int i = 0; i < 13; ++i) xv[i] = xb[i];
+    rec[kSeqTimeUsed] = dt0;
+    rec[kSeqTimeOwed] = 0.0;
+    s_dt = dt0;
     double f[13], A44[16], B43[12];
-    motion_f_and_blocks(xv, dt, f, A44, B43);
+    motion_f_and_blocks(xv, dt0, f, A44, B43);
     for (int i = 0; i < 13; ++i) s_f[i] = f[i];
     for (int i = 0; i < 16; ++i) s_A[i] = A44[i];
     for (int i = 0; i < 12; ++i) s_B[i] = B43[i];
   }
   for (int e = tid; e < 169; e += blockDim.x) s_P[e] = Pb[(size_t)(e / 13) * ld + (e % 13)];
   __syncthreads();
+  const double dt = s_dt;
   FTR(0, 1);
   for (int e = tid; e < 169; e += blockDim.x) {
     const int i = e / 13, j = e % 13;
@@ -90,6 +99,15 @@ __device__ __forceinline__ void predict_body(const int b, double* __restrict__ x
   }
   if (tid < 13) xb[tid] = s_f[tid];
   FTR(0, 4);
+}
+
+// A paused sequence's share of a predict launch: with catch-up on (sl2_set_pause_catch_up) the step it skips is owed to its
+// next predict; nothing else of the sequence moves.
+__device__ __forceinline__ void predict_paused(const int b, double* __restrict__ seq_time) {
+  if (threadIdx.x == 0) {
+    double* rec = seq_time + (size_t)b * kSeqTimeDoubles;
+    if (rec[kSeqTimeCatchUp] != 0.0) rec[kSeqTimeOwed] += rec[kSeqTimeNominal];
+  }
 }
 
 // ---------------------------------------------------------------------------

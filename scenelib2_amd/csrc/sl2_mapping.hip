@@ -28,7 +28,7 @@ struct MapParams {
   int enable_mapping, save_trajectory;
   int force;      // InitialiseAutoFeature (monoslam.cpp:1535-1541): no speed gate, no visible-feature count
   int keep_visible, n_particles, min_particles, erase_after;
-  double min_lambda, max_lambda, sd_ratio, prune_threshold, dt;
+  double min_lambda, max_lambda, sd_ratio, prune_threshold;
   int pcap;       // particle slots per partial feature in `particles` / `me_desc` (sl2_engine::pcap)
   int kpart;      // partial slots per sequence (sl2_engine::kpart)
   // One-sequence engines (launch_mapping): k_map_update reports how many partially initialised features the step leaves, and a
@@ -45,7 +45,8 @@ struct MapParams {
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void region_body(const double* __restrict__ x, const int* __restrict__ f_flags,
                                             const int* __restrict__ n_slots, const int* __restrict__ n_vis,
-                                            const double* __restrict__ prev_r, int* __restrict__ part_i,
+                                            const double* __restrict__ prev_r, const double* __restrict__ seq_time,
+                                            int* __restrict__ part_i,
                                             unsigned long long* __restrict__ rand48, double* __restrict__ last_r,
                                             int* __restrict__ status, const CameraParams& cam, const MapParams& mp, int N, int ld,
                                             double* s_uv /* [2 * N] projections of the known features in front of the camera */) {
@@ -60,9 +61,13 @@ __device__ __forceinline__ void region_body(const double* __restrict__ x, const 
     pi[kPartCreated] = 0;
     s_cnt = 0;
     s_go = 0;
-    // camera speed estimate (monoslam.cpp:152-157)
-    const double vx = (xb[0] - prev_r[b * 3 + 0]) / mp.dt, vy = (xb[1] - prev_r[b * 3 + 1]) / mp.dt,
-                 vz = (xb[2] - prev_r[b * 3 + 2]) / mp.dt;
+    // camera speed estimate (monoslam.cpp:152-157): the displacement since prev_r over the time the last predict used
+    const double* rec = seq_time + (size_t)b * kSeqTimeDoubles;
+    // (a sequence that has not predicted in this engine yet - a tail reached through the seams on a fresh engine, or right after a
+    // load or copy - has used nothing: its nominal step stands in, as the engine's scalar did)
+    const double dt_used = rec[kSeqTimeUsed] > 0.0 ? rec[kSeqTimeUsed] : rec[kSeqTimeNominal];
+    const double vx = (xb[0] - prev_r[b * 3 + 0]) / dt_used, vy = (xb[1] - prev_r[b * 3 + 1]) / dt_used,
+                 vz = (xb[2] - prev_r[b * 3 + 2]) / dt_used;
     const double speed = sqrt(vx * vx + vy * vy + vz * vz);
     // feature_init_info_vector_.size() < kMaxFeaturesToInitAtOnce_ (monoslam.cpp:163-165; the buttons have no such gate in the
     // reference, but a sequence has only kpart partial slots here)
@@ -71,10 +76,11 @@ __device__ __forceinline__ void region_body(const double* __restrict__ x, const 
         status[b] |= 2;            // the map is full: cannot reserve a label (capacity chosen at sl2_create)
       } else {
         status[b] &= ~2;           // (the bit tells about the LAST attempt: room again after deletions / the slot squeeze)
-        // FindNonOverlappingRegion (:867-943): where will the image centre be in ten steps?
+        // FindNonOverlappingRegion (:867-943): where will the image centre be in ten steps?  (ten FRAME intervals - kDeltaT_,
+        // the sequence's nominal step - whatever the last predict had to catch up on)
         double x0[13], xv[13];
         for (int i = 0; i < 13; ++i) x0[i] = xb[i];
-        motion_f_repeated(x0, mp.dt, 10, xv);
+        motion_f_repeated(x0, rec[kSeqTimeNominal], 10, xv);
         double R[9], yW[3], xp[7], zeroed[3], h[2], Hx[14], Hy[6], Rn;
         quat_to_rot(&xv[3], R);
         for (int i = 0; i < 3; ++i) {
@@ -145,14 +151,15 @@ __device__ __forceinline__ void region_body(const double* __restrict__ x, const 
 
 __global__ void __launch_bounds__(kDetThreads) k_map_find(const double* __restrict__ x, const int* __restrict__ f_flags,
                                                           const int* __restrict__ n_slots, const int* __restrict__ n_vis,
-                                                          const double* __restrict__ prev_r, int* __restrict__ part_i,
+                                                          const double* __restrict__ prev_r, const double* __restrict__ seq_time,
+                                                          int* __restrict__ part_i,
                                                           double* __restrict__ part_d, unsigned long long* __restrict__ rand48,
                                                           double* __restrict__ last_r, int* __restrict__ status,
                                                           const uint8_t* __restrict__ frames, size_t seq_stride, CameraParams cam,
                                                           MapParams mp, int N, int ld, const uint8_t* __restrict__ active) {
   extern __shared__ double s_uv[];
   if (active && !active[blockIdx.x]) return;          // a paused sequence of a step (uniform; the "initialise feature" calls pass no mask)
-  region_body(x, f_flags, n_slots, n_vis, prev_r, part_i, rand48, last_r, status, cam, mp, N, ld, s_uv);
+  region_body(x, f_flags, n_slots, n_vis, prev_r, seq_time, part_i, rand48, last_r, status, cam, mp, N, ld, s_uv);
   const int b = blockIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
   if (!pi[kPartRegionValid]) return;
@@ -959,7 +966,6 @@ static MapParams map_params(const sl2_engine* e, int enable_mapping, int save_tr
   mp.erase_after = e->prm.erase_partially_init_feature_after_this_many_attempts;
   mp.min_lambda = e->prm.min_lambda; mp.max_lambda = e->prm.max_lambda;
   mp.sd_ratio = e->prm.standard_deviation_depth_ratio; mp.prune_threshold = e->prm.prune_probability_threshold;
-  mp.dt = e->prm.delta_t;
   mp.pcap = e->root->pcap;
   mp.kpart = e->root->kpart;
   return mp;
@@ -987,7 +993,7 @@ static int launch_create(sl2_engine* e, const MapParams& mp, bool honour_mask) {
 static int launch_find(sl2_engine* e, const MapParams& mp, bool honour_mask) {
   LaunchScope ls(e, "k_map_find");
   hipLaunchKernelGGL(k_map_find, dim3(e->B), dim3(kDetThreads), sizeof(double) * 2 * e->N, e->stream, e->x, e->f_flags, e->n_slots, e->n_vis,
-                     e->prev_r, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride, e->cam, mp, e->N, e->ld,
+                     e->prev_r, e->seq_time, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride, e->cam, mp, e->N, e->ld,
                      honour_mask ? e->active : nullptr);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
@@ -1023,7 +1029,6 @@ int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int s
   mp.erase_after = e->prm.erase_partially_init_feature_after_this_many_attempts;
   mp.min_lambda = e->prm.min_lambda; mp.max_lambda = e->prm.max_lambda;
   mp.sd_ratio = e->prm.standard_deviation_depth_ratio; mp.prune_threshold = e->prm.prune_probability_threshold;
-  mp.dt = e->prm.delta_t;
   mp.pcap = e->root->pcap;
   mp.kpart = e->root->kpart;
   // The three launches that serve partially initialised features are dead weight while there is none, and at one sequence each

@@ -35,7 +35,7 @@ constexpr int kSmallM = 32;          // rows of the innovation system (one Chole
 
 __global__ void __launch_bounds__(kSmallThreads) k_small_front(
     double* __restrict__ x, double* __restrict__ P, const int* __restrict__ n_slots, double* __restrict__ prev_r,
-    const int* __restrict__ part_i, int pend, int ld, double dt,
+    const int* __restrict__ part_i, int pend, int ld, double* __restrict__ seq_time,
     const double* __restrict__ xp_org, int* __restrict__ f_flags, double* __restrict__ f_h, double* __restrict__ f_Hx,
     double* __restrict__ f_Hy, double* __restrict__ f_R, double* __restrict__ f_S, double* __restrict__ f_score,
     int* __restrict__ srch_i, double* __restrict__ srch_d, CameraParams cam, int N,
@@ -44,9 +44,9 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
     const uint8_t* __restrict__ active, int* __restrict__ sel_gate) {
   extern __shared__ double s_dyn[];
   const int b = blockIdx.x;
-  if (!active[b]) { select_paused(b, sel_gate); return; }      // a paused sequence (uniform): nothing predicted, nothing selected
+  if (!active[b]) { predict_paused(b, seq_time); select_paused(b, sel_gate); return; }      // a paused sequence (uniform): nothing predicted, nothing selected
   SST(2, 0);
-  predict_body(b, x, P, n_slots, prev_r, part_i, pend, ld, dt);
+  predict_body(b, x, P, n_slots, prev_r, part_i, pend, ld, seq_time);
   __syncthreads();                                    // x and P of this sequence: written above, read below (same workgroup)
   SST(2, 1);
   for (int i = threadIdx.x; i < N; i += (int)blockDim.x)
@@ -333,7 +333,7 @@ int launch_small_front(sl2_engine* e, int n) {
   if (n > e->nsel_max) n = e->nsel_max;
   const size_t shm = (size_t)e->N * (sizeof(double) + 3 * sizeof(int));
   hipLaunchKernelGGL(k_small_front, dim3(e->B), dim3(kSmallThreads), shm, e->stream, e->x, e->P, e->n_slots, e->prev_r, e->part_i,
-                     e->ppos + 6 * e->kpart, e->ld, e->prm.delta_t, e->xp_org, e->f_flags, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S,
+                     e->ppos + 6 * e->kpart, e->ld, e->seq_time, e->xp_org, e->f_flags, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S,
                      e->f_score, e->srch_i, e->srch_d, e->cam, e->N, e->sel_idx, e->n_sel, e->n_vis, e->last_r, e->srch_sel, n,
                      e->srch_big, (e->srch_big && e->root->search_variant == 1) ? e->root->search_split : 0, e->active, e->sel_gate);
   SL2_HIP(hipGetLastError());

@@ -111,6 +111,31 @@ class Engine:
         self._ck(self.L.sl2_get_active_sequences(self.h, int(seq0), int(nseq), _lib.u8p(out)))
         return out
 
+    def set_delta_t(self, dt, seq0=0, on_device=False):
+        """The time step of sequences seq0, seq0 + 1, ... from their next predict on (sl2_set_delta_t); what they were owed is
+        cleared.  dt: a scalar or array-like of len <= batch - seq0, every value finite and > 0 (consumed before the call
+        returns), or with on_device=True a (device pointer, count) pair, whose invalid entries are skipped.  Never
+        synchronises, drops no captured step, does not consult the mask."""
+        if on_device:
+            ptr, n = dt
+            self._ck(self.L.sl2_set_delta_t(self.h, int(seq0), int(n), _lib.vp(int(ptr)), 1))
+            return
+        d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1)
+        self._ck(self.L.sl2_set_delta_t(self.h, int(seq0), int(d.size), d.ctypes.data_as(_lib.vp), 0))
+
+    def get_delta_t(self, seq0=0, nseq=None):
+        """(dt, owed, last_used), float64 [nseq] each: the nominal time step, the time owed by skipped predicts and the step the
+        last predict used (sl2_get_delta_t; synchronises)."""
+        nseq = self.batch - seq0 if nseq is None else nseq
+        dt, owed, used = np.zeros(nseq), np.zeros(nseq), np.zeros(nseq)
+        self._ck(self.L.sl2_get_delta_t(self.h, int(seq0), int(nseq), _lib.dp(dt), _lib.dp(owed), _lib.dp(used)))
+        return dt, owed, used
+
+    def set_pause_catch_up(self, enabled=True):
+        """With catch-up on, a resumed sequence predicts over its nominal step plus one for every predict it sat out; off (the
+        default) clears what is owed (sl2_set_pause_catch_up)."""
+        self._ck(self.L.sl2_set_pause_catch_up(self.h, int(bool(enabled))))
+
     def set_groups(self, groups):
         self._ck(self.L.sl2_set_groups(self.h, int(groups)))
 
@@ -486,6 +511,11 @@ class MonoSLAM:
         self._engine = Engine(cam, params, 1, self._max_features, self._device)
         self._engine.set_vehicle_state(np.asarray(xv).reshape(1, 13), np.asarray(Pxx).reshape(1, 13, 13))
         return self
+
+    def SetDeltaT(self, delta_t):
+        """kDeltaT_ from the next GoOneStep on (the reference fixes it at Init; a camera whose frame rate changes does not)."""
+        self._engine.set_delta_t(float(delta_t))
+        self.kDeltaT_ = float(delta_t)
 
     # MonoSLAM::AddNewKnownFeature(y, xp, identifier) — monoslam.cpp:1278-1291
     def AddNewKnownFeature(self, y, xp, identifier):
