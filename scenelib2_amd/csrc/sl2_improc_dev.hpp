@@ -288,7 +288,13 @@ __device__ __forceinline__ void me_score_box_wg(const uint8_t* __restrict__ img,
   const int ye = (ys + per < s_box[3]) ? ys + per : s_box[3];
   const int iw = bw + 10;
   const int band = kMeBandBytes / iw - 10;               // rows of positions whose windows fit the LDS band (iw <= width + 10)
-  if (band <= 0) return;                                 // (a frame wider than ~1600 pixels: not reachable, me_big is bounded by sl2_create's checks)
+  if (band <= 0) {
+    // bw >= 1480 (a union spanning a 1920-wide frame; nothing bounds the width from above): not even one row of positions
+    // has its windows in the band, so the slice is scored from memory - the same integer sums, row by row
+    for (int y = ys; y < ye; ++y)
+      for (int q = tid; q < bw; q += 256) map[(size_t)y * width + (x0 + q)] = me_score_position(img, width, s_patch, Sg0, Sg0sq, x0 + q, y);
+    return;
+  }
   const float rcpi = 1.0f / (float)iw, rcpw = 1.0f / (float)bw;
   for (int yb = ys; yb < ye; yb += band) {
     const int nr = min(band, ye - yb);
