@@ -11,6 +11,7 @@
 #include "../../include/scenelib2_amd.h"
 #include "sl2_math.hpp"
 #include "sl2_seq_arrays.hpp"
+#include "sl2_step_plan.hpp"
 
 namespace sl2 {
 
@@ -139,7 +140,7 @@ struct sl2_engine : sl2::SeqArrays {
   bool mapping_used = false;
   int* init_uv = nullptr;                // [B][2] pixel selections of sl2_initialise_feature (allocated on first use)
   // ---- whole-step HIP graphs (small batches are launch-bound: ~12 kernels per step) ----
-  struct StepGraph { const void* frames; size_t stride; int save_trajectory, enable_mapping, tail, small; hipGraphExec_t exec; };
+  struct StepGraph { const void* frames; size_t stride; sl2::StepPlan plan; hipGraphExec_t exec; };   // a captured step: what it bakes in is its key
   bool graph_mode = false;
   std::vector<StepGraph> step_graphs;
   long long graph_captures = 0;   // steps captured so far (TEST build: sl2_debug_graph_captures - a setter that says it drops no captured step is held to it)
@@ -261,14 +262,12 @@ int launch_select(sl2_engine* e, int n);
 int launch_search(sl2_engine* e);            // the search kernel, then k_search_score
 int launch_search_kernel(sl2_engine* e);     // the search kernel alone (the fused small-map step scores in k_small_back)
 int launch_search_score(sl2_engine* e);
-int small_step_mode(const sl2_engine* e, int slots_bound);       // sl2_small.hip: 0 = ten launches, 1 = three (both sides of the search fused), 2 = the back side only
 int launch_small_front(sl2_engine* e, int n);                 // predict + feature prediction + selection in one launch
-int small_panel_w(const sl2_engine* e, int slots_bound);         // sl2_small.hip: columns of k_small_back's LDS panel (64 or 128)
-int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound);   // scoring + EKF update + normalise / delete / symmetrise in one launch
+int launch_small_back(sl2_engine* e, int save_trajectory, int panel_w);   // (GroupPlan::panel_w) scoring + EKF update + normalise / delete / symmetrise in one launch
 int launch_update(sl2_engine* e);
 int launch_syrk_on(sl2_engine* e, const double* Vt, double* P);
 int launch_finalize(sl2_engine* e, int save_trajectory);
-int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int slots_bound, int parts_state);
+int launch_mapping(sl2_engine* e, const TailPlan& tp);
 int launch_manual_init(sl2_engine* e, const int* d_uv);
 int launch_auto_init(sl2_engine* e);
 int launch_compact_slots(sl2_engine* e, int need, bool honour_mask = false);   // sl2_mapping.hip: retired slots squeezed out when a sequence lacks room for `need` more features (honour_mask: the launch of a step, which leaves paused sequences alone)

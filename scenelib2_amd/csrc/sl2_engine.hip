@@ -973,11 +973,10 @@ static int enable_feature_initialisation(sl2_engine* e) {
 }
 
 // Feature initialisation runs on group 0, the whole batch (enable_feature_initialisation refuses sequence groups): hand it the
-// frame binding and the buffers that are allocated on first use, which build_groups does not copy.
+// frame binding (the buffers allocated on first use are read through root).
 static sl2_engine* mapping_group(sl2_engine* e) {
   sl2_engine* g = e->groups[0];
   g->cur_frames = e->cur_frames; g->cur_stride = e->cur_stride;
-  g->score_map = e->score_map; g->me_big_list = e->me_big_list; g->me_big_count = e->me_big_count;
   return g;
 }
 
@@ -1031,49 +1030,39 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
   if (enable_mapping && !e->mapping_used && (rc = enable_feature_initialisation(e)) != SL2_OK) return rc;
   if ((rc = bind_frames(e, frames, seq_stride, frames_on_device)) != SL2_OK) return rc;
   const int nsel = e->prm.number_of_features_to_select;
-  // Once mapping has been on, MatchPartiallyInitialisedFeatures has work to do in every later step
-  // (monoslam.cpp:167 is unconditional); the trajectory push then moves behind it (k_map_update).
-  const bool tail = e->mapping_used;
-  const int slots_bound = slots_upper_bound(e);
-  const int parts_state = tail ? parts_state_for_step(e) : 0;
-  const int small_any = [&]() { int m = ((slots_bound + 1 > e->N) ? 1 : 0) + 2 * parts_state; for (const sl2_engine* g : e->groups) { const int md = small_step_mode(g, slots_bound); m = (m * 7 + (md == 0 ? 0 : md + (small_panel_w(g, slots_bound) == 64 ? 3 : 0))) % 1000003; } return m; }();   // (which launches the step consists of, and the LDS panel k_small_back is launched with: part of a captured step's key)
+  // What this step launches, decided once (sl2_step_plan.hpp): the launch list walks the plan, and a captured step is keyed by it.
+  const StepShape shape = {e->N, e->ld, e->mld, e->kpart, e->step_fusion, e->mapping_used, {e->groups.front()->B, e->groups.back()->B}};
+  const StepPlan plan = make_step_plan(shape, slots_upper_bound(e), e->mapping_used ? parts_state_for_step(e) : 0, save_trajectory, enable_mapping);
   auto issue = [=]() -> int {
     int r = for_each_group(e, [=](sl2_engine* g) {
+      const GroupPlan& gp = plan.group[g->B == shape.group_B[0] ? 0 : 1];
       int q;
-      const int mode = small_step_mode(g, slots_bound);
-      if (mode == 1) {                   // small maps: three launches (sl2_small.hip)
+      if (gp.small_front) {
         if ((q = launch_small_front(g, nsel)) != SL2_OK) return q;
-        if ((q = launch_search_kernel(g)) != SL2_OK) return q;
-        return launch_small_back(g, tail ? 0 : save_trajectory, slots_bound);
-      }
-      if (mode == 2) {                   // small maps, large batch, small capacity: the back side only
+      } else {
         if ((q = launch_predict(g)) != SL2_OK) return q;
         if ((q = launch_feature_prediction(g)) != SL2_OK) return q;
         if ((q = launch_select(g, nsel)) != SL2_OK) return q;
-        if ((q = launch_search_kernel(g)) != SL2_OK) return q;
-        return launch_small_back(g, tail ? 0 : save_trajectory, slots_bound);
       }
-      if ((q = launch_predict(g)) != SL2_OK) return q;
-      if ((q = launch_feature_prediction(g)) != SL2_OK) return q;
-      if ((q = launch_select(g, nsel)) != SL2_OK) return q;
+      if (gp.small_back) {               // small maps (sl2_small.hip): the search kernel alone, scoring is the back's
+        if ((q = launch_search_kernel(g)) != SL2_OK) return q;
+        return launch_small_back(g, gp.save_trajectory, gp.panel_w);
+      }
       if ((q = launch_search(g)) != SL2_OK) return q;
       if ((q = launch_update(g)) != SL2_OK) return q;
-      return launch_finalize(g, tail ? 0 : save_trajectory);
+      return launch_finalize(g, gp.save_trajectory);
     });
-    if (r == SL2_OK && tail) {
-      r = launch_mapping(mapping_group(e), enable_mapping ? 1 : 0, save_trajectory, slots_bound, parts_state);
-    }
+    if (r == SL2_OK && plan.tail.runs) r = launch_mapping(mapping_group(e), plan.tail);
     return r;
   };
-  // Whole-step HIP graph: the dozen launches of a step are captured once per (frame buffer, flags) and replayed -
+  // Whole-step HIP graph: the dozen launches of a step are captured once per (frame buffer, step plan) and replayed -
   // at small batches the step is launch-bound.  Needs device-resident frames (the capture bakes the pointer in; a
   // double-buffered ingest alternates between two graphs), one sequence group and no per-kernel profiling.
   const bool use_graph = e->graph_mode && frames_on_device && !e->profiling && e->groups.size() <= 1;
   if (use_graph) {
     hipGraphExec_t exec = nullptr;
     for (const auto& sg : e->step_graphs)
-      if (sg.frames == (const void*)frames && sg.stride == seq_stride && sg.save_trajectory == save_trajectory &&
-          sg.enable_mapping == enable_mapping && sg.tail == (int)tail && sg.small == (int)small_any) { exec = sg.exec; break; }
+      if (sg.frames == (const void*)frames && sg.stride == seq_stride && sg.plan == plan) { exec = sg.exec; break; }
     if (!exec) {
       hipGraph_t graph = nullptr;
       SL2_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeRelaxed));
@@ -1089,7 +1078,7 @@ int sl2_go_one_step(sl2_engine* e, const uint8_t* frames, size_t seq_stride, int
       e->graph_captures += 1;
       hipGraphDestroy(graph);
       if (e->step_graphs.size() >= 8) { hipGraphExecDestroy(e->step_graphs.front().exec); e->step_graphs.erase(e->step_graphs.begin()); }
-      e->step_graphs.push_back({(const void*)frames, seq_stride, save_trajectory, enable_mapping, (int)tail, (int)small_any, exec});
+      e->step_graphs.push_back({(const void*)frames, seq_stride, plan, exec});
     }
     SL2_HIP(hipGraphLaunch(exec, e->stream));
     rc = SL2_OK;

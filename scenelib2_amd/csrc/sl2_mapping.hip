@@ -11,7 +11,7 @@
 //                    convert_from_partially_to_fully_initialised, sell-by deletion, trajectory push
 //                                                                           :1299-1342, 1449-1538, feature.cpp:204-269
 //   k_map_finish     k_map_create + k_map_update in one launch (one sequence, no partial feature at the start of the frame)
-// Which of them a step consists of: launch_mapping, from what the host knows about the partial features (parts_state).
+// Which of them a step consists of: the step plan's TailPlan (sl2_step_plan.hpp), which launch_mapping walks.
 //
 // State layout: the six states (r_W, hhat_W) of the partial feature in partial slot k live in columns ppos + 6 k ..
 // ppos + 6 k + 5 of x / P, ppos = 13 + 3N (behind the map: the update's algebra does not care where a state sits, and the
@@ -1017,48 +1017,29 @@ int launch_auto_init(sl2_engine* e) {
   return launch_create(e, mp, false);
 }
 
-int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int slots_bound, int parts_state) {
-  const int parts_none = parts_state == 1, parts_full = parts_state == 2;
+// The feature-initialisation tail of a step: the launches the plan lists (sl2_step_plan.hpp: TailPlan, where the reasons are).
+int launch_mapping(sl2_engine* e, const TailPlan& tp) {
   const int B = e->B;
-  MapParams mp;
-  mp.force = 0;
-  mp.enable_mapping = enable_mapping; mp.save_trajectory = save_trajectory;
-  mp.keep_visible = e->prm.number_of_features_to_keep_visible;
-  mp.n_particles = e->prm.number_of_particles;
-  mp.min_particles = e->prm.min_number_of_particles;
-  mp.erase_after = e->prm.erase_partially_init_feature_after_this_many_attempts;
-  mp.min_lambda = e->prm.min_lambda; mp.max_lambda = e->prm.max_lambda;
-  mp.sd_ratio = e->prm.standard_deviation_depth_ratio; mp.prune_threshold = e->prm.prune_probability_threshold;
-  mp.pcap = e->root->pcap;
-  mp.kpart = e->root->kpart;
-  // The three launches that serve partially initialised features are dead weight while there is none, and at one sequence each
-  // is a link of the frame's dependent chain: k_map_update's report (sl2_engine.hip: parts_state_for_step) lets the host leave
-  // them out (state 1).  me_big_count keeps its last value meanwhile; k_map_particles zeroes it before anything reads it again.
-  // The other way round (state 2): every partial slot is taken, so FindNonOverlappingRegion's gate (k_map_find: kPartCount <
-  // kpart, monoslam.cpp:163-165) is shut whatever the camera does - no region, no detector, no creation: k_map_find and
-  // k_map_create are left out, and k_map_particles clears the two per-step flags k_map_find would have.
-  mp.parts_skipped = parts_none ? 1 : 0;
+  MapParams mp = map_params(e, tp.enable_mapping, tp.save_trajectory, 0);
+  mp.parts_skipped = tp.finish ? 1 : 0;
   mp.publish_parts = (e->root->B == 1 && e->root->parts_mail_dev) ? 1 : 0;
   const int W = e->cam.width, H = e->cam.height;
-  if (!e->score_map) { set_error("launch_mapping: score map not allocated"); return SL2_ERR_INVALID; }
-  // Retired slots are squeezed out only when a sequence is about to run out of slots; the host's upper bound on the slots in use
-  // (sl2_engine.hip: slots_upper_bound) says when none can be: the launch - one of the step's dependent chain, 7 us at one
-  // sequence, 0.03 ms at 1024 - is then left out altogether.
-  if (enable_mapping && slots_bound + 1 > e->N) { int rc = launch_compact_slots(e, 1, true); if (rc != SL2_OK) return rc; }
-  if (!parts_full) { int rc = launch_find(e, mp, true); if (rc != SL2_OK) return rc; }
+  if (!e->root->score_map) { set_error("launch_mapping: score map not allocated"); return SL2_ERR_INVALID; }
+  if (tp.squeeze) { int rc = launch_compact_slots(e, 1, true); if (rc != SL2_OK) return rc; }
+  if (tp.find) { int rc = launch_find(e, mp, true); if (rc != SL2_OK) return rc; }
   const size_t shm_particles = sizeof(double) * kParticleDoubles * (size_t)mp.n_particles;
-  if (parts_none) {
+  if (tp.finish) {
     LaunchScope ls(e, "k_map_finish");
     hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), e->cam, mp);
     SL2_HIP(hipGetLastError());
-    return SL2_OK;
   }
-  if (!parts_full) { int rc = launch_create(e, mp, true); if (rc != SL2_OK) return rc; }
+  if (tp.create) { int rc = launch_create(e, mp, true); if (rc != SL2_OK) return rc; }
+  if (!tp.partials) return SL2_OK;
   {
     LaunchScope ls(e, "k_map_particles");
     const int pc = e->root->pcap;
 #define SL2_PARTICLES(T) hipLaunchKernelGGL(k_map_particles<T>, dim3(B, mp.kpart), dim3(pc), 0, e->stream, e->x, e->P, e->ps_i, e->particles, \
-                                            e->me_desc, e->last_r, e->me_big_count, e->part_i, parts_full, e->cam, e->ld, e->ppos, pc, mp.kpart, e->active)
+                                            e->me_desc, e->last_r, e->root->me_big_count, e->part_i, tp.parts_full, e->cam, e->ld, e->ppos, pc, mp.kpart, e->active)
     if (pc <= 128) SL2_PARTICLES(128);
     else if (pc <= 256) SL2_PARTICLES(256);
     else if (pc <= 512) SL2_PARTICLES(512);
@@ -1069,16 +1050,16 @@ int launch_mapping(sl2_engine* e, int enable_mapping, int save_trajectory, int s
   {
     MeJobsEngine J;
     J.frames = e->cur_frames; J.seq_stride = e->cur_stride; J.patch_base = e->patch; J.ps_i = e->ps_i; J.me_desc = e->me_desc;
-    J.particles = e->particles; J.map_base = e->score_map; J.N = e->N; J.pcap = e->root->pcap;
+    J.particles = e->particles; J.map_base = e->root->score_map; J.N = e->N; J.pcap = e->root->pcap;
     J.width = W; J.height = H; J.kpart = mp.kpart; J.active = e->active;
     {
       LaunchScope ls(e, "k_map_me_search");
-      hipLaunchKernelGGL(k_map_me_search, dim3(B * mp.kpart), dim3(1024), 0, e->stream, J, e->me_big_list, e->me_big_count);
+      hipLaunchKernelGGL(k_map_me_search, dim3(B * mp.kpart), dim3(1024), 0, e->stream, J, e->root->me_big_list, e->root->me_big_count);
       SL2_HIP(hipGetLastError());
     }
     {
       LaunchScope ls(e, "k_me_big");
-      me_big_launch(J, e->me_big_list, e->me_big_count, W, e->stream);
+      me_big_launch(J, e->root->me_big_list, e->root->me_big_count, W, e->stream);
       SL2_HIP(hipGetLastError());
     }
   }

@@ -30,8 +30,7 @@ namespace sl2 {
 #define SST(row, slot) do { } while (0)
 #endif
 
-constexpr int kSmallThreads = 256;
-constexpr int kSmallM = 32;          // rows of the innovation system (one Cholesky block)
+constexpr int kSmallThreads = 256;   // (kSmallM, kSmallW: sl2_step_plan.hpp)
 
 __global__ void __launch_bounds__(kSmallThreads) k_small_front(
     double* __restrict__ x, double* __restrict__ P, const int* __restrict__ n_slots, double* __restrict__ prev_r,
@@ -70,8 +69,6 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
 // Then the block sits at the engine column search_score_body<true> put in f_hcol, exactly as in k_build_AS: a column inside
 // the partial feature's six states is compact column nlive + (column - ppos), and a column below 7 OVERWRITES the dh_by_dxv
 // coefficients it lands on (monoslam.cpp:562-565).
-constexpr int kSmallW = 128;         // compact columns at most: 13 + 3 * 36 + 6 + 1
-constexpr int kSmallBatchMax = 256;  // sequences per group up to which the fused step is the faster one at ANY capacity (scripts/small_latency.py)
 __device__ __forceinline__ void small_update_body(const int b, double* __restrict__ x, double* __restrict__ P,
                                                   const double* __restrict__ f_Hx, const double* __restrict__ f_Hy,
                                                   const double* __restrict__ f_nu, const double* __restrict__ f_R,
@@ -304,30 +301,6 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_back(
   SST(3, 3);
 }
 
-// Which stages of a sequence group's step are fused: 0 = none (ten launches), 1 = both sides of the search (three launches),
-// 2 = the back side only (scoring + update + finalize in one launch, the front-end stages on their own: six launches).
-// Static conditions: at most 16 features measured per frame - the innovation system is one 32 x 32 block - and one partially
-// initialised feature in flight at most (a misplaced recorded position, Q28, is taken from f_hcol like the ten-launch step
-// does; the host cannot know of one without a synchronisation, so it is not a condition).  Dynamic: the LIVE maps fit
-// kSmallW columns - `slots_bound` = the host's upper bound on n_slots of any sequence (sl2_engine.hip: slots_upper_bound, exact
-// at synchronised points, from the device's mailbox in between).  Then: everything fused when the group is small enough to be
-// latency-bound or the capacity is large (the one-stage kernels work on all ld columns, the fused ones on the live ones:
-// scripts/small_latency.py, a dozen features at capacity 128 - ld = 448 - fused is 1.2 x faster at one sequence and 1.8 x at
-// 1024); at a small capacity and a large batch only the back side, which holds its own there (0.107 against 0.118 ms for the six
-// stages it replaces at 1024 sequences, ld = 128) - k_small_front does not (0.065 against 0.038 ms: 304 registers, one workgroup
-// per CU).
-int small_step_mode(const sl2_engine* e, int slots_bound) {
-  if (!e->root->step_fusion || e->mld != kSmallM || e->kpart != 1 || 13 + 3 * slots_bound + 6 * e->kpart + 1 > kSmallW) return 0;
-  return (e->B <= kSmallBatchMax || e->ld >= 256 || e->root->step_fusion == 2) ? 1 : 2;
-}
-
-// Columns of k_small_back's LDS panel for a group whose live maps are at most `slots_bound` slots: 64 while every map fits
-// them (a third workgroup per CU at large batches), else kSmallW.  The kernel picks its own W from each sequence's size, which
-// the bound bounds; a captured step bakes this choice in, so it is part of the step's key (sl2_go_one_step).
-int small_panel_w(const sl2_engine* e, int slots_bound) {
-  return (13 + 3 * slots_bound + 6 * e->kpart + 1 <= 64) ? 64 : kSmallW;
-}
-
 int launch_small_front(sl2_engine* e, int n) {
   LaunchScope ls(e, "k_small_front", true);
   if (n > e->nsel_max) n = e->nsel_max;
@@ -340,10 +313,10 @@ int launch_small_front(sl2_engine* e, int n) {
   return SL2_OK;
 }
 
-int launch_small_back(sl2_engine* e, int save_trajectory, int slots_bound) {
+int launch_small_back(sl2_engine* e, int save_trajectory, int panel_w) {
   LaunchScope ls(e, "k_small_back", true);
-  // the LDS panel is [32][W] (small_panel_w)
-  size_t shm = sizeof(double) * kSmallM * small_panel_w(e, slots_bound);
+  // the LDS panel is [32][W] (sl2_step_plan.hpp: small_panel_w)
+  size_t shm = sizeof(double) * kSmallM * panel_w;
   // (the bookkeeping phases: [N + 8] ints + 16 x kWorkDoubles doubles, then [2 N] ints + 354 doubles)
   const size_t ints = sizeof(int) * (2 * (size_t)e->N + 10) + sizeof(double) * (16 + 169 + 169 + 16 * kWorkDoubles);
   if (ints > shm) shm = ints;

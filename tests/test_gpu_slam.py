@@ -1030,7 +1030,7 @@ def test_q28_block_inside_the_vehicle_state_and_below_column_zero():
 @pytest.mark.gpu
 def test_large_batch_of_small_maps_fuses_the_back_side_only():
     """More than 256 sequences at a small capacity (ld < 256): the front-end stages stay on their own kernels, the stages behind
-    the search run as k_small_back (sl2_small.hip: small_step_mode 2).  Against an engine on the ten-launch step: integer
+    the search run as k_small_back (sl2_step_plan.hpp: small_step_mode 2).  Against an engine on the ten-launch step: integer
     outputs identical, state and covariance to 1e-13 / 1e-12, three sequences of the batch against the oracle."""
     B, N, F = 300, 6, 4
     pr = Pair(N, F, batch=3, max_features=8, feature_sigma=0.004)

@@ -9,7 +9,7 @@ only runs it eagerly on a map of fixed size:
   - a known feature added behind a partially initialised one is three columns off in H once that one converts
     (feature.cpp:254); the fused update must place its block where the ten-launch step and the reference do.
 
-Fused modes (sl2_small.hip: small_step_mode): 1 = both sides of the search fused (a few sequences), 2 = the back side only
+Fused modes (sl2_step_plan.hpp: small_step_mode): 1 = both sides of the search fused (a few sequences), 2 = the back side only
 (more than 256 sequences at a capacity with ld < 256: three distinct sequences tiled to 300, a sample of them compared).
 Every test shows by per-launch profiling on a directly launched engine that the fused kernels ran."""
 import numpy as np
@@ -86,11 +86,11 @@ class GraphTwin:
     alternating buffers), engine 1 launches the same steps directly, with per-launch profiling.  Between steps the same calls
     go to both (`both`)."""
 
-    def __init__(self, cam, params, B, capacity, setup):
+    def __init__(self, cam, params, B, capacity, setup, lib=None):
         self.W, self.H, self.B = cam["width"], cam["height"], B
         self.engines = []
         for graph in (True, False):
-            e = Engine(cam, params, B, capacity)
+            e = Engine(cam, params, B, capacity, lib=lib)
             setup(e)
             e.set_graph_mode(graph)
             if not graph:
@@ -283,6 +283,29 @@ def test_graph_replay_after_calls_that_change_the_map_between_steps(mode):
         tw.compare(SAMPLE[mode])
     assert tw.eager.partial_feature(0)["info"]["initialised"] >= 1
     _assert_fused_ran(tw.eager, mode)
+
+
+def test_graph_replay_captures_once_per_buffer_and_step_plan():
+    """A captured step is keyed by its frame buffer and its step plan (sl2_step_plan.hpp).  One sequence at capacity 128
+    (ld = 448), frames alternating between two device buffers; sl2_add_known_features - which drops no captured step - puts the
+    map at 4 slots (k_small_back with the 64-column panel), then 20 (the 128-column panel), then 40 (the one-stage kernels), six
+    steps in each.  sl2_debug_graph_captures of the TEST build must read 2, 4 and 6: one capture per (buffer, plan), none for a
+    repeat, none lost to eviction - and every step bit-identical to direct launches."""
+    T = _lib.load_testing()
+    kf = KnownFeatures(40, 18, 10, 1)
+    tw = GraphTwin(kf.pr.cam, kf.pr.params, 1, 128, kf.setup, lib=T)
+    k, lo = 0, 0
+    for hi, captures in ((4, 2), (20, 4), (40, 6)):
+        kf.add(tw.engines, lo, hi)
+        lo = hi
+        for _ in range(6):
+            tw.step(kf.frames(k))
+            tw.compare((0,))
+            k += 1
+        assert [T.sl2_debug_graph_captures(e.h) for e in tw.engines] == [captures, 0], hi
+    assert int(tw.eager.total_state_sizes()[0]) == 13 + 3 * 40
+    t = tw.eager.kernel_times()
+    assert t["k_small_front"]["launches"] == 12 and t["k_small_back"]["launches"] == 12 and t["k_syrk"]["launches"] == 6, t
 
 
 # ---------------------------------------------------------------- B: Q28 offsets on the fused update

@@ -90,7 +90,7 @@ def test_small_back_leaves_room_for_three_workgroups_per_cu(tmp_path):
     per CU at large batches (sl2_small.hip).  A static array added to the kernel fails no parity test; it fails this one."""
     block = _descriptor(_assembly("sl2_small.hip", ["-ffp-contract=off"], tmp_path), "k_small_back")
     static = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
-    panel = 8 * _constexpr("sl2_small.hip", "kSmallM") * _constexpr("sl2_small.hip", "kSmallW")
+    panel = 8 * _constexpr("sl2_step_plan.hpp", "kSmallM") * _constexpr("sl2_step_plan.hpp", "kSmallW")
     n_max = (2048 - 13 - 6 - 1) // 3                       # ld = roundup(13 + 3 N + 6 kpart + 1, 64) <= 2048, kpart >= 1
     scratch = 4 * (2 * n_max + 10) + 8 * (16 + 169 + 169 + 16 * _constexpr("sl2_seq_arrays.hpp", "kWorkDoubles"))
     dyn = max(panel, scratch)
