@@ -96,6 +96,12 @@ class MonoSLAM {             // monoslam.h:69-219
     refresh();
     return r;
   }
+  // Camera::SetCameraParameters (camera.cpp:49-62) on the camera of a running filter: from the next GoOneStep on
+  void SetCameraParameters(const int camera_width, const int camera_height, const double fku, const double fkv, const double u0,
+                           const double v0, const double kd1, const int sd) {
+    impl_.SetCameraParameters(camera_width, camera_height, fku, fkv, u0, v0, kd1, sd);
+    refresh();
+  }
   void InitialiseFeature(cv::Mat frame) {                                  // monoslam.cpp:1211-1235: at the clicked (uu_, vv_)
     impl_.uu_ = uu_; impl_.vv_ = vv_;
     impl_.InitialiseFeature(view(frame));

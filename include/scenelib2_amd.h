@@ -40,7 +40,8 @@ extern "C" {
  * sl2_load_sequences, sl2_copy_sequences, sl2_reset_sequences, sl2_sequence_blob_capacity, sl2_sequence_blob_layout;
  * sl2_snapshot_header.sequence_steps (taken from reserved[]); sl2_set_active_sequences, sl2_get_active_sequences,
  * sl2_ingest_frame_counts, sl2_ingest_next_ragged; sl2_get_step_stats (sl2_step_stats); sl2_set_delta_t, sl2_get_delta_t,
- * sl2_set_pause_catch_up (the time step is the sequence's: sl2_params.delta_t is its initial value). */
+ * sl2_set_pause_catch_up (the time step is the sequence's: sl2_params.delta_t is its initial value); sl2_set_cameras,
+ * sl2_get_cameras (the calibration is the sequence's: the sl2_create camera is its initial value and the batch's image size). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -229,6 +230,27 @@ int sl2_get_delta_t(sl2_engine* e, int seq0, int nseq, double* dt, double* owed,
  * sequence was owed is cleared.  For the whole batch, by a kernel on the engine's stream: ordered like sl2_set_delta_t, never
  * waits, drops no captured step. */
 int sl2_set_pause_catch_up(sl2_engine* e, int enabled);
+
+/* The camera calibration is the sequence's.  The camera given to sl2_create fixes the image size of the whole batch (frame
+ * strides, search tiles and the detector's tiling depend on it) and is the calibration every sequence starts with; the six
+ * intrinsics fku, fkv, u0, v0, kd1, sd are then a record per sequence on the device, read by every kernel of a step that
+ * projects or unprojects, so one batch serves physically different cameras of one image size.
+ *
+ * sl2_set_cameras: cams[i] becomes the calibration of sequence seq0 + i for every step issued after the call.  `cams` is host
+ * memory of any kind and is consumed before the call returns.  The change is ordered on the engine's stream: after every step
+ * already queued, before the next one.  The call never waits for the device and drops no captured step (the record is data
+ * a replayed graph reads, not part of its key).  The mask is not consulted: a paused sequence can be given its camera before it
+ * resumes.  SL2_ERR_INVALID, and NOTHING changed in any sequence of the range: a range outside the batch, a null pointer, any
+ * cams[i] whose width / height differ from the engine's, any of fku, fkv, u0, v0, kd1 that is not finite, fku == 0 or
+ * fkv == 0, sd < 0.
+ * Sequence blobs record the calibration (sl2_sequence_blob_header.camera is the SEQUENCE's) and sl2_load_sequences /
+ * sl2_copy_sequences refuse a blob whose camera differs from the destination sequence's: a map continued under another
+ * calibration would be silently wrong.  They, and sl2_reset_sequences, never change a calibration: to move a sequence, set the
+ * destination's camera first. */
+int sl2_set_cameras(sl2_engine* e, int seq0, int nseq, const sl2_camera* cams);
+/* sl2_get_cameras: the calibration of each sequence as the setters called so far leave it, with the engine's width / height.
+ * Answered from the engine's host-side copy: does NOT synchronise. */
+int sl2_get_cameras(sl2_engine* e, int seq0, int nseq, sl2_camera* cams);
 
 /* The seams of GoOneStep, individually callable (same order as the reference):
  *   Kalman::KalmanFilterPredict(monoslam,u=0)            kalman.cpp:50-69
@@ -580,7 +602,8 @@ int sl2_get_step_stats(sl2_engine* e, int seq0, int nseq, sl2_step_stats* out, i
  * the public view of sl2_snapshot but everything a later step reads - x and P, templates in their packed form, retired slots,
  * counters, the recorded-position offsets (Q28), the partially initialised features with their particles, the drand48 state,
  * both trajectory stores.  k_seq_pack / k_seq_unpack (sl2_checkpoint.hip) write and read it on the device.  A blob can be loaded
- * into any sequence of any engine that FITS: the same sl2_camera and sl2_params (bytewise, except max_features_to_init_at_once
+ * into any sequence of any engine that FITS: the destination SEQUENCE's sl2_camera (sl2_set_cameras; the sl2_create camera unless
+ * set) equal to the one the blob records, the same sl2_params (bytewise, except max_features_to_init_at_once
  * and number_of_features_to_select, which must be at least what the blob uses: its partial slots, its selected features),
  * max_features >= n_slots, partial slots >= n_partial_slots, particle capacity >= n_particles.  Same-shape engines continue a
  * loaded sequence bit for bit; another shape keeps every integer result and agrees to rounding (the partial features' columns
@@ -627,7 +650,7 @@ typedef struct sl2_sequence_blob_header {
   uint32_t off_x, off_P, off_slots, off_seq, off_particles, off_traj, off_pos_log;
   int32_t row_pitch;                           /* doubles per row of x / P in the blob */
   int32_t state_size;                          /* n */
-  sl2_camera camera;
+  sl2_camera camera;                           /* the calibration the SEQUENCE ran under (sl2_set_cameras) */
   sl2_params params;
   int32_t n_selected;                          /* features selected in the sequence's last selection (rows of the innovation system) */
   int32_t reserved[3];
@@ -650,16 +673,19 @@ int sl2_save_sequences(sl2_engine* e, int seq0, int nseq, void* blobs, size_t bl
  * fit this engine) with sl2_last_error() naming the field, and the engine untouched.  A blob with mapping in use switches
  * feature initialisation on (MatchPartiallyInitialisedFeatures goes on running, monoslam.cpp:167) and is refused with more
  * than one sequence group, like mapping itself.  Rows, columns and slots the blob does not cover are zeroed.  Synchronises;
- * captured step graphs are dropped. */
+ * captured step graphs are dropped.  The camera compared is the destination sequence's own (sl2_get_cameras), and a load never
+ * changes it: give the slot the sequence's camera first (sl2_set_cameras). */
 int sl2_load_sequences(sl2_engine* e, int seq0, int nseq, const void* blobs, size_t blob_stride, int blobs_on_device);
 /* Save + load without the host, between two engines on one device or inside one engine (overlapping ranges: SL2_ERR_INVALID).
  * Engines on different streams are ordered by an event.  The destination is treated as by sl2_load_sequences, except that the two
  * engines' params.delta_t need not agree: the time step is the destination's own record (sl2_set_delta_t) and is not copied, so
- * engines created for cameras of different rates can hand sequences to each other. */
+ * engines created for cameras of different rates can hand sequences to each other.  The calibration is held to the same rule as
+ * a load: source sequence i's camera must equal destination sequence i's. */
 int sl2_copy_sequences(sl2_engine* dst, int dst_seq0, sl2_engine* src, int src_seq0, int nseq);
 /* The sequences become what sl2_create left: empty map, next_free_label_ 0, counters, status, trajectory store, position log
  * and partial features cleared, drand48 as after srand48(0) (monoslam.cpp:1968), x and P zero.  The caller then sets the
- * vehicle state and adds features as for a fresh engine.  Synchronises; captured step graphs are dropped. */
+ * vehicle state and adds features as for a fresh engine.  The sequence keeps its camera (sl2_set_cameras), its time step and
+ * its place in the mask.  Synchronises; captured step graphs are dropped. */
 int sl2_reset_sequences(sl2_engine* e, int seq0, int nseq);
 
 /* ------------------------------------------------------------------- profiling */

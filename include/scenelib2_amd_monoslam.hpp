@@ -175,6 +175,16 @@ class MonoSLAM {
     kDeltaT_ = delta_t;
   }
 
+  // Camera::SetCameraParameters (camera.cpp:49-62) from the next GoOneStep on: a recalibrated camera, or another unit of the
+  // same model.  The image size is fixed at Init; the engine refuses another one, and values that are not a calibration.
+  void SetCameraParameters(int camera_width, int camera_height, double fku, double fkv, double u0, double v0, double kd1, int sd) {
+    if (!eng_) throw std::runtime_error("MonoSLAM::SetCameraParameters: call Init first");
+    sl2_camera cam;
+    cam.width = camera_width; cam.height = camera_height; cam.fku = fku; cam.fkv = fkv; cam.u0 = u0; cam.v0 = v0; cam.kd1 = kd1; cam.sd = sd;
+    check(sl2_set_cameras(eng_, 0, 1, &cam), "sl2_set_cameras");
+    camera_->fku_ = fku; camera_->fkv_ = fkv; camera_->centre_ = {{u0, v0}}; camera_->kd1_ = kd1; camera_->measurement_sd_ = sd;
+  }
+
   // MonoSLAM::GoOneStep (monoslam.cpp:108-180).  Always true, like the reference (:179).
   bool GoOneStep(const Frame& frame, bool save_trajectory, bool enable_mapping) {
     if (!eng_ || !frame.data || frame.cols != camera_->width_ || frame.rows != camera_->height_)

@@ -124,6 +124,7 @@ EXPORTED_SYMBOLS = [
     "sl2_set_active_sequences", "sl2_get_active_sequences", "sl2_ingest_frame_counts", "sl2_ingest_next_ragged",
     "sl2_get_step_stats",
     "sl2_set_delta_t", "sl2_get_delta_t", "sl2_set_pause_catch_up",
+    "sl2_set_cameras", "sl2_get_cameras",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -245,6 +246,9 @@ def _bind(L):
         L.sl2_set_delta_t.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
         L.sl2_get_delta_t.argtypes = [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp]
         L.sl2_set_pause_catch_up.argtypes = [vp, C.c_int]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_set_cameras"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_set_cameras.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.sl2_get_cameras.argtypes = [vp, C.c_int, C.c_int, vp]
     return L
 
 

@@ -33,8 +33,9 @@ struct CkptArrays {
   int slot_words[kSlotArrays];
   int *n_slots, *next_label, *status, *pos_err_any, *n_sel, *n_vis, *m_count, *traj_count, *pos_count, *seq_age, *part_i, *ps_i, *sel_gate, *m_gate, *step_mark;
   unsigned long long* rand48;
+  const double* seq_cam;      // every sequence's calibration: k_seq_pack records it in the header, nothing here writes it
   int N, ld, ppos, kpart, pcap, mapping_used;
-  sl2_camera cam;
+  int width, height;          // the engine's image size
   sl2_params prm;
 };
 
@@ -179,12 +180,18 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
     hd.magic = SL2_BLOB_MAGIC; hd.layout_version = SL2_BLOB_LAYOUT_VERSION; hd.bytes = t.bytes;
     hd.sequence_steps = (long long)A.pos_count[b] + A.seq_age[b];
     hd.src_max_features = A.N; hd.src_partial_slots = A.kpart; hd.src_particle_capacity = A.pcap;
-    hd.width = A.cam.width; hd.height = A.cam.height;
+    hd.width = A.width; hd.height = A.height;
     hd.n_slots = ns; hd.n_partial_slots = kp; hd.n_particles = pc; hd.mapping_in_use = A.mapping_used;
     hd.off_x = off_x; hd.off_P = off_P; hd.off_slots = off_slots; hd.off_seq = t.off_seq; hd.off_particles = t.off_particles;
     hd.off_traj = t.off_traj; hd.off_pos_log = t.off_pos_log;
     hd.row_pitch = (int)pitch; hd.state_size = (int)n;
-    hd.camera = A.cam; hd.params = A.prm;
+    {   // the calibration the sequence ran under: its own record (the sl2_create camera's values until sl2_set_cameras)
+      const double* rec = A.seq_cam + (size_t)b * kSeqCamDoubles;
+      hd.camera.width = A.width; hd.camera.height = A.height;
+      hd.camera.fku = rec[kSeqCamFku]; hd.camera.fkv = rec[kSeqCamFkv]; hd.camera.u0 = rec[kSeqCamU0]; hd.camera.v0 = rec[kSeqCamV0];
+      hd.camera.kd1 = rec[kSeqCamKd1]; hd.camera.sd = (int)rec[kSeqCamSd];
+    }
+    hd.params = A.prm;
     hd.n_selected = A.n_sel[b];
   }
   __syncthreads();
@@ -307,11 +314,10 @@ static CkptArrays arrays_of(sl2_engine* e) {
   A.n_slots = e->n_slots; A.next_label = e->next_label; A.status = e->status; A.pos_err_any = e->pos_err_any; A.n_sel = e->n_sel;
   A.n_vis = e->n_vis; A.m_count = e->m_count; A.traj_count = e->traj_count; A.pos_count = e->pos_count; A.seq_age = e->seq_age;
   A.sel_gate = e->sel_gate; A.m_gate = e->m_gate; A.step_mark = e->step_mark;
-  A.part_i = e->part_i; A.ps_i = e->ps_i; A.rand48 = e->rand48;
+  A.part_i = e->part_i; A.ps_i = e->ps_i; A.rand48 = e->rand48; A.seq_cam = e->seq_cam;
   A.N = e->N; A.ld = e->ld; A.ppos = e->ppos; A.kpart = e->kpart; A.pcap = e->pcap; A.mapping_used = e->mapping_used ? 1 : 0;
   // (field by field into zeroed structures: the blob's copies carry no padding bytes of the caller's)
-  A.cam.width = e->cam.width; A.cam.height = e->cam.height; A.cam.fku = e->cam.fku; A.cam.fkv = e->cam.fkv; A.cam.u0 = e->cam.u0;
-  A.cam.v0 = e->cam.v0; A.cam.kd1 = e->cam.kd1; A.cam.sd = e->cam.sd;
+  A.width = e->cam.width; A.height = e->cam.height;
   const sl2_params& p = e->prm;
   A.prm.delta_t = p.delta_t; A.prm.number_of_features_to_select = p.number_of_features_to_select;
   A.prm.number_of_features_to_keep_visible = p.number_of_features_to_keep_visible;
@@ -379,11 +385,13 @@ static int refuse(int code, int index, const char* field, const char* what) {
   return code;
 }
 
-// Does blob `index` (its header; `avail` bytes of it exist) describe a well-formed blob that fits engine e?
+// Does blob `index` (its header; `avail` bytes of it exist) describe a well-formed blob that fits sequence dst_seq of engine e?
+// (The calibration is the destination SEQUENCE's, from the host's mirror of seq_cam: a map continued under another camera is
+// silently wrong, so the caller gives the slot the sequence's camera - sl2_set_cameras - before it loads or copies into it.)
 // (engine_to_engine: sl2_copy_sequences.  The time step is the destination's own record and travels in no blob, so two
 // engines created with different params.delta_t - cameras of different rates - may still hand sequences to each other; a blob
 // from outside is held to every word of params as before.)
-static int check_header(sl2_engine* e, const sl2_sequence_blob_header& h, size_t avail, int index, bool engine_to_engine = false) {
+static int check_header(sl2_engine* e, int dst_seq, const sl2_sequence_blob_header& h, size_t avail, int index, bool engine_to_engine = false) {
   if (h.magic != SL2_BLOB_MAGIC) return refuse(SL2_ERR_INVALID, index, "magic", "not a sequence blob");
   if (h.layout_version != SL2_BLOB_LAYOUT_VERSION) return refuse(SL2_ERR_INVALID, index, "layout_version", "unknown layout");
   if (h.n_slots < 0 || h.n_slots > 676) return refuse(SL2_ERR_INVALID, index, "n_slots", "out of range");
@@ -399,8 +407,8 @@ static int check_header(sl2_engine* e, const sl2_sequence_blob_header& h, size_t
       h.row_pitch != (int)pitch || h.state_size != (int)n)
     return refuse(SL2_ERR_INVALID, index, "section offsets", "do not match the layout");
   const CkptArrays A = arrays_of(e);
-  if (memcmp(&h.camera, &A.cam, sizeof(sl2_camera)) != 0 || h.width != A.cam.width || h.height != A.cam.height)
-    return refuse(SL2_ERR_INVALID, index, "camera", "differs from the engine's");
+  if (memcmp(&h.camera, &e->cams_host[dst_seq], sizeof(sl2_camera)) != 0 || h.width != A.width || h.height != A.height)
+    return refuse(SL2_ERR_INVALID, index, "camera", "differs from the destination sequence's");
   sl2_params p = h.params;
   p.max_features_to_init_at_once = A.prm.max_features_to_init_at_once;
   p.number_of_features_to_select = A.prm.number_of_features_to_select;
@@ -482,7 +490,7 @@ int sl2_load_sequences(sl2_engine* e, int seq0, int nseq, const void* blobs, siz
   bool mapping = false;
   size_t largest = 0;
   for (int i = 0; i < nseq; ++i) {
-    const int rc = check_header(e, hs[i], blob_stride, i);
+    const int rc = check_header(e, seq0 + i, hs[i], blob_stride, i);
     if (rc != SL2_OK) return rc;
     mapping = mapping || hs[i].mapping_in_use != 0;
     largest = hs[i].bytes > largest ? (size_t)hs[i].bytes : largest;
@@ -524,7 +532,7 @@ int sl2_copy_sequences(sl2_engine* dst, int dst_seq0, sl2_engine* src, int src_s
     SL2_HIP(hipStreamSynchronize(src->stream));
   }
   for (int i = 0; i < nseq; ++i) {
-    const int rc = check_header(dst, hs[i], cap, i, true);
+    const int rc = check_header(dst, dst_seq0 + i, hs[i], cap, i, true);
     if (rc != SL2_OK) return rc;
     mapping = mapping || hs[i].mapping_in_use != 0;
   }

@@ -69,6 +69,10 @@ constexpr int kSrchBigParts = kSrchBigDone + kSrchBigUnits;
 constexpr int kSrchBigInts = kSrchBigParts + 8 * kSrchBigUnits;
 // seq_time, the per-sequence time record (sl2_engine::seq_time): doubles per sequence and their places
 constexpr int kSeqTimeDoubles = 4, kSeqTimeNominal = 0, kSeqTimeOwed = 1, kSeqTimeUsed = 2, kSeqTimeCatchUp = 3;
+// seq_cam, the per-sequence camera calibration (sl2_engine::seq_cam): doubles per sequence - one 64-byte line - and their places;
+// [6] and [7] are spare and stay 0.  sd is kept as a double: CameraParams::sd only ever enters cam.sd * (1.0 + ratio), an exact conversion.
+constexpr int kSeqCamDoubles = 8, kSeqCamFku = 0, kSeqCamFkv = 1, kSeqCamU0 = 2, kSeqCamV0 = 3, kSeqCamKd1 = 4, kSeqCamSd = 5;
+static_assert(kSeqCamDoubles * sizeof(double) == 64, "one cache line per sequence");
 __host__ __device__ inline int srch_unit_bands(int bands) { const int g = (bands + kSrchBigSlots - 1) / kSrchBigSlots; return g > kSrchBigMinBands ? g : kSrchBigMinBands; }
 // Partially initialised features: up to kMaxPartial per sequence (params.max_features_to_init_at_once, monoslam.cpp:163-167).
 // part_i / part_d = the per-SEQUENCE record: feature_init_info_vector_.size(), the partial slots in the vector's order (a
@@ -99,6 +103,20 @@ __device__ __forceinline__ bool xcd_map(int tiles, int B, int* seq, int* tile) {
 }
 #endif
 
+#if defined(__HIPCC__)
+// The camera of sequence b, built in registers: its six intrinsics from the sequence's line of seq_cam, the geometry from the
+// engine.  Called with a workgroup-uniform b the address is uniform too and the line arrives by scalar loads, in the SGPRs the
+// by-value kernel argument used to occupy.  Nothing is precomputed: the models see the same six numbers as before.
+__device__ __forceinline__ CameraParams load_cam(const double* __restrict__ seq_cam, int b, int width, int height) {
+  const double* rec = seq_cam + (size_t)b * kSeqCamDoubles;
+  CameraParams cam;
+  cam.width = width; cam.height = height;
+  cam.fku = rec[kSeqCamFku]; cam.fkv = rec[kSeqCamFkv]; cam.u0 = rec[kSeqCamU0]; cam.v0 = rec[kSeqCamV0];
+  cam.kd1 = rec[kSeqCamKd1]; cam.sd = (int)rec[kSeqCamSd];
+  return cam;
+}
+#endif
+
 struct KernelTimer {
   std::string name;
   double total_ms = 0.0;
@@ -117,7 +135,7 @@ struct sl2_engine : sl2::SeqArrays {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  sl2::CameraParams cam;
+  sl2::CameraParams cam;      // the camera of sl2_create: the image geometry of every sequence, and the calibration each one starts with (seq_cam)
   sl2_params prm;
   int B = 0;         // sequences
   int N = 0;         // feature capacity per sequence
@@ -187,6 +205,15 @@ struct sl2_engine : sl2::SeqArrays {
   // write it with kernels on the engine's stream, so a captured step reads it as data.  Engine state like step_mark: outside
   // SL2_SEQ_ARRAYS, in no sequence blob, a group sees it from its first sequence on (build_groups).
   double* seq_time = nullptr;
+  // ---- the per-sequence camera calibration (sl2_set_cameras) ----
+  // [B][kSeqCamDoubles]: fku, fkv, u0, v0, kd1, sd of the sequence (the sl2_create camera's until sl2_set_cameras), two spare
+  // words.  Read through load_cam by every step kernel that projects or unprojects; written only by the setter's kernel on the
+  // engine's stream, so a captured step reads it as data.  Engine state like seq_time: outside SL2_SEQ_ARRAYS, a group sees it
+  // from its first sequence on (build_groups); a sequence blob RECORDS it (header.camera) and a load checks it, but nothing
+  // but the setter writes it.  cams_host (root only) is the host's copy of what the setters queued so far: sl2_get_cameras and the
+  // checkpoint checks answer from it without waiting for the device.
+  double* seq_cam = nullptr;
+  std::vector<sl2_camera> cams_host;
   void* stats_host = nullptr;      // pinned + mapped host memory the host form of sl2_get_step_stats fills: [B] records (first use)
   void* stats_host_dev = nullptr;  // its device-side address
 

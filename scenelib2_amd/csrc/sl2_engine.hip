@@ -184,6 +184,7 @@ static int build_groups(sl2_engine* e, int G) {
     static_cast<SeqArrays&>(*g) = seq_arrays_view(*e, dims, first);
     g->step_mark = e->step_mark + first;       // (not a row of SL2_SEQ_ARRAYS: sl2_common.hpp)
     g->seq_time = e->seq_time + kSeqTimeDoubles * first;      // (nor is the time record)
+    g->seq_cam = e->seq_cam + kSeqCamDoubles * first;         // (nor the calibration)
     const int rc = [&]() -> int {
       if (G == 1) g->stream = e->stream; else SL2_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
       // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
@@ -488,6 +489,21 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
     for (size_t b = 0; b < B; ++b) rec[b * kSeqTimeDoubles + kSeqTimeNominal] = e->prm.delta_t;
     SL2_HIP(hipMemcpy(e->seq_time, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
   }
+  {   // every sequence starts with the engine's calibration (sl2_set_cameras)
+    const int r = dmalloc(&e->seq_cam, B * kSeqCamDoubles); if (r != SL2_OK) return r;
+    std::vector<double> rec(B * kSeqCamDoubles, 0.0);
+    for (size_t b = 0; b < B; ++b) {
+      double* c = &rec[b * kSeqCamDoubles];
+      c[kSeqCamFku] = cam->fku; c[kSeqCamFkv] = cam->fkv; c[kSeqCamU0] = cam->u0; c[kSeqCamV0] = cam->v0;
+      c[kSeqCamKd1] = cam->kd1; c[kSeqCamSd] = (double)cam->sd;
+    }
+    SL2_HIP(hipMemcpy(e->seq_cam, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
+    sl2_camera c0;
+    memset(&c0, 0, sizeof(c0));      // (padding too: blobs and the checkpoint checks compare the struct's bytes)
+    c0.width = cam->width; c0.height = cam->height; c0.fku = cam->fku; c0.fkv = cam->fkv; c0.u0 = cam->u0; c0.v0 = cam->v0;
+    c0.kd1 = cam->kd1; c0.sd = cam->sd;
+    e->cams_host.assign(B, c0);
+  }
   SL2_HIP(hipMalloc((void**)&e->slots_max_dev, sizeof(int) * 2));
   SL2_HIP(hipMemset(e->slots_max_dev, 0, sizeof(int) * 2));
   SL2_HIP(hipHostMalloc((void**)&e->slots_mail, 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
@@ -564,6 +580,7 @@ void sl2_destroy(sl2_engine* e) {
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
   if (e->step_mark) hipFree(e->step_mark);
   if (e->seq_time) hipFree(e->seq_time);
+  if (e->seq_cam) hipFree(e->seq_cam);
   if (e->stats_host) hipHostFree(e->stats_host);
   if (e->slots_mail) hipHostFree(e->slots_mail);
   if (e->snap_stage) hipFree(e->snap_stage);
@@ -826,6 +843,60 @@ int sl2_set_pause_catch_up(sl2_engine* e, int enabled) {
   SL2_HIP(hipSetDevice(e->device));
   hipLaunchKernelGGL(k_set_catch_up, dim3((e->B + 255) / 256), dim3(256), 0, e->stream, e->seq_time, enabled ? 1 : 0, e->B);
   SL2_HIP(hipGetLastError());
+  return SL2_OK;
+}
+
+// ------------------------------------------------------------------- the per-sequence camera calibration
+
+// The six intrinsics of kCamChunk sequences travel in one launch's own arguments, like the time steps above: 64 x 48 bytes
+// = 3 KB, under the 4 KB a launch may carry.  Everything was validated on the host before the first launch.
+constexpr int kCamChunk = 64;
+struct CamChunk { double v[kCamChunk][6]; };
+static_assert(sizeof(CamChunk) + 64 <= 4096, "a chunk and the two other arguments must fit the kernel-argument segment");
+__global__ void __launch_bounds__(64) k_set_cam_args(double* __restrict__ seq_cam, CamChunk c, int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  double* rec = seq_cam + (size_t)i * kSeqCamDoubles;
+  for (int k = 0; k < 6; ++k) rec[k] = c.v[i][k];       // (kSeqCamFku .. kSeqCamSd are places 0 .. 5; the two spare words stay 0)
+}
+
+int sl2_set_cameras(sl2_engine* e, int seq0, int nseq, const sl2_camera* cams) {
+  if (!range_ok(e, seq0, nseq) || !cams) return SL2_ERR_INVALID;
+  for (int i = 0; i < nseq; ++i) {
+    const sl2_camera& c = cams[i];
+    if (c.width != e->cam.width || c.height != e->cam.height) {
+      set_error("sl2_set_cameras: the image size is the engine's; a sequence's camera cannot change it"); return SL2_ERR_INVALID;
+    }
+    if (!std::isfinite(c.fku) || !std::isfinite(c.fkv) || !std::isfinite(c.u0) || !std::isfinite(c.v0) || !std::isfinite(c.kd1) ||
+        c.fku == 0.0 || c.fkv == 0.0 || c.sd < 0) {
+      set_error("sl2_set_cameras: fku, fkv, u0, v0 and kd1 must be finite, fku and fkv not 0, sd >= 0"); return SL2_ERR_INVALID;
+    }
+  }
+  SL2_HIP(hipSetDevice(e->device));
+  // on the engine's stream, outside any captured step, like the mask and the time step: the record is data a replayed graph reads
+  for (int c0 = 0; c0 < nseq; c0 += kCamChunk) {
+    const int cnt = nseq - c0 < kCamChunk ? nseq - c0 : kCamChunk;
+    CamChunk ch;
+    memset(&ch, 0, sizeof(ch));
+    for (int i = 0; i < cnt; ++i) {
+      const sl2_camera& c = cams[c0 + i];
+      double* v = ch.v[i];
+      v[kSeqCamFku] = c.fku; v[kSeqCamFkv] = c.fkv; v[kSeqCamU0] = c.u0; v[kSeqCamV0] = c.v0; v[kSeqCamKd1] = c.kd1; v[kSeqCamSd] = (double)c.sd;
+    }
+    hipLaunchKernelGGL(k_set_cam_args, dim3(1), dim3(64), 0, e->stream, e->seq_cam + (size_t)(seq0 + c0) * kSeqCamDoubles, ch, cnt);
+    SL2_HIP(hipGetLastError());
+    for (int i = 0; i < cnt; ++i) {      // the mirror follows launch by launch: it never says more than was queued
+      sl2_camera& m = e->cams_host[seq0 + c0 + i];
+      const sl2_camera& c = cams[c0 + i];
+      m.fku = c.fku; m.fkv = c.fkv; m.u0 = c.u0; m.v0 = c.v0; m.kd1 = c.kd1; m.sd = c.sd;
+    }
+  }
+  return SL2_OK;
+}
+
+int sl2_get_cameras(sl2_engine* e, int seq0, int nseq, sl2_camera* cams) {
+  if (!range_ok(e, seq0, nseq) || !cams) return SL2_ERR_INVALID;
+  for (int i = 0; i < nseq; ++i) cams[i] = e->cams_host[seq0 + i];      // (the host's mirror: no wait for the device)
   return SL2_OK;
 }
 

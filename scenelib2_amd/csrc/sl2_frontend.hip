@@ -24,8 +24,10 @@ __global__ void __launch_bounds__(64) k_feature_prediction(const double* __restr
                                                            double* __restrict__ f_Hx, double* __restrict__ f_Hy,
                                                            double* __restrict__ f_R, double* __restrict__ f_S,
                                                            double* __restrict__ f_score, int* __restrict__ srch_i, double* __restrict__ srch_d,
-                                                           CameraParams cam, int N, int ld, const uint8_t* __restrict__ active) {
+                                                           const double* __restrict__ seq_cam, int width, int height, int N, int ld,
+                                                           const uint8_t* __restrict__ active) {
   if (!active[blockIdx.y]) return;           // a paused sequence (uniform)
+  const CameraParams cam = load_cam(seq_cam, blockIdx.y, width, height);      // (grid.y = sequence: one sequence per workgroup, a uniform address)
   feature_prediction_body(blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, x, P, xp_org, f_flags, n_slots, f_h, f_Hx, f_Hy, f_R, f_S,
                           f_score, srch_i, srch_d, cam, N, ld);
 }
@@ -79,7 +81,8 @@ int launch_feature_prediction(sl2_engine* e) {
   LaunchScope ls(e, "k_feature_prediction");
   dim3 grid((e->N + 63) / 64, e->B);
   hipLaunchKernelGGL(k_feature_prediction, grid, dim3(64), 0, e->stream, e->x, e->P, e->xp_org, e->f_flags, e->n_slots,
-                     e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score, e->srch_i, e->srch_d, e->cam, e->N, e->ld, e->active);
+                     e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score, e->srch_i, e->srch_d, e->seq_cam, e->cam.width, e->cam.height, e->N, e->ld,
+                     e->active);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }

@@ -111,7 +111,8 @@ __device__ __forceinline__ void predict_paused(const int b, double* __restrict__
 }
 
 // ---------------------------------------------------------------------------
-// k_feature_prediction: one thread per (sequence, feature slot).
+// k_feature_prediction: one thread per (sequence, feature slot).  cam = the sequence's own camera (load_cam, once per
+// workgroup: every workgroup of the two kernels that call this serves one sequence).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void feature_prediction_body(const int b, const int i, const double* __restrict__ x, const double* __restrict__ P,
                                                            const double* __restrict__ xp_org, int* __restrict__ f_flags,
@@ -119,7 +120,7 @@ __device__ __forceinline__ void feature_prediction_body(const int b, const int i
                                                            double* __restrict__ f_Hx, double* __restrict__ f_Hy,
                                                            double* __restrict__ f_R, double* __restrict__ f_S,
                                                            double* __restrict__ f_score, int* __restrict__ srch_i, double* __restrict__ srch_d,
-                                                           CameraParams cam, int N, int ld) {
+                                                           const CameraParams& cam, int N, int ld) {
   if (i >= n_slots[b]) return;
   const size_t fi = (size_t)b * N + i;
   int flags = f_flags[fi] & ~(FF_SELECTED | FF_VISIBLE);

@@ -155,10 +155,12 @@ __global__ void __launch_bounds__(kDetThreads) k_map_find(const double* __restri
                                                           int* __restrict__ part_i,
                                                           double* __restrict__ part_d, unsigned long long* __restrict__ rand48,
                                                           double* __restrict__ last_r, int* __restrict__ status,
-                                                          const uint8_t* __restrict__ frames, size_t seq_stride, CameraParams cam,
+                                                          const uint8_t* __restrict__ frames, size_t seq_stride,
+                                                          const double* __restrict__ seq_cam, int width, int height,
                                                           MapParams mp, int N, int ld, const uint8_t* __restrict__ active) {
   extern __shared__ double s_uv[];
   if (active && !active[blockIdx.x]) return;          // a paused sequence of a step (uniform; the "initialise feature" calls pass no mask)
+  const CameraParams cam = load_cam(seq_cam, blockIdx.x, width, height);
   region_body(x, f_flags, n_slots, n_vis, prev_r, seq_time, part_i, rand48, last_r, status, cam, mp, N, ld, s_uv);
   const int b = blockIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
@@ -180,9 +182,10 @@ struct MapArrays {
   double *particles, *last_r, *traj; int* traj_count; const int* pos_count; unsigned long long* parts_mail;
   int N, ld, ppos0;
   const uint8_t* active;      // the step's mask (sl2_set_active_sequences); nullptr: the caller's explicit act on every sequence
+  const double* seq_cam; int width, height;      // every sequence's calibration (load_cam) and the engine's image geometry
 };
 
-__device__ __forceinline__ void create_body(const MapArrays& a, const CameraParams& cam, const MapParams& mp) {
+__device__ __forceinline__ void create_body(const MapArrays& a, const MapParams& mp) {
   double* __restrict__ x = a.x; double* __restrict__ P = a.P; const uint8_t* __restrict__ frames = a.frames;
   const size_t seq_stride = a.seq_stride;
   uint8_t* __restrict__ patch = a.patch; int* __restrict__ patch_sums = a.patch_sums; double* __restrict__ xp_org = a.xp_org;
@@ -198,6 +201,7 @@ __device__ __forceinline__ void create_body(const MapArrays& a, const CameraPara
   if (a.active && !a.active[b]) return;        // a paused sequence (uniform): its flags of the last frame it saw are not acted on again
   if (!pi[kPartRegionValid]) return;
   if (!(pd[2] > 20000)) return;        // SUITABLE_PATCH_SCORE_THRESHOLD (:837, 850-858)
+  const CameraParams cam = load_cam(a.seq_cam, b, a.width, a.height);
   // the partial slot this feature takes: the first free one (k_map_find / k_map_manual checked that there is one)
   int* psb = ps_i + (size_t)b * mp.kpart * kPsInts;
   int ks = 0;
@@ -334,7 +338,7 @@ __device__ __forceinline__ void create_body(const MapArrays& a, const CameraPara
   }
 }
 
-__global__ void __launch_bounds__(64) k_map_create(MapArrays a, CameraParams cam, MapParams mp) { create_body(a, cam, mp); }
+__global__ void __launch_bounds__(64) k_map_create(MapArrays a, MapParams mp) { create_body(a, mp); }
 
 // ---------------------------------------------------------------------------
 // k_map_particles: one workgroup per sequence, one thread per particle.
@@ -347,8 +351,8 @@ __global__ void __launch_bounds__(THREADS) k_map_particles(const double* __restr
                                                                  int* __restrict__ ps_i, double* __restrict__ particles,
                                                                  int* __restrict__ me_desc, double* __restrict__ last_r,
                                                                  int* __restrict__ me_big_count, int* __restrict__ part_i, int clear_region,
-                                                                 CameraParams cam, int ld, int ppos0, int pcap, int kpart,
-                                                                 const uint8_t* __restrict__ active) {
+                                                                 const double* __restrict__ seq_cam, int width, int height, int ld,
+                                                                 int ppos0, int pcap, int kpart, const uint8_t* __restrict__ active) {
   const int b = blockIdx.x, ks = blockIdx.y, tid = threadIdx.x;       // one workgroup per (sequence, partial slot)
   int* ps = ps_i + ((size_t)b * kpart + ks) * kPsInts;
   if (b == 0 && ks == 0 && tid == 0) *me_big_count = 0;     // the step's list of oversized multi-ellipse searches starts empty
@@ -379,6 +383,7 @@ __global__ void __launch_bounds__(THREADS) k_map_particles(const double* __restr
   for (int i = 0; i < 6; ++i) ypi[i] = xb[ppos + i];
   double* o = particles + (((size_t)b * kpart + ks) * pcap + tid) * kParticleDoubles;
   double h[2], Hx[14], Hy[12], Rn;
+  const CameraParams cam = load_cam(seq_cam, b, width, height);
   part_measurement_model(cam, xp, ypi, o[0], h, Hx, Hy, &Rn);
   double Pxx7[49], Pxy7[42], Pyy[36], S[4];
   for (int r = 0; r < 7; ++r) {
@@ -723,9 +728,9 @@ __global__ void __launch_bounds__(64) k_map_update(MapArrays a, MapParams mp) {
 
 // A step that starts without a partially initialised feature (launch_mapping: parts_none) has nothing between the creation of
 // a feature and the end-of-frame bookkeeping: both in one launch.
-__global__ void __launch_bounds__(64) k_map_finish(MapArrays a, CameraParams cam, MapParams mp) {
+__global__ void __launch_bounds__(64) k_map_finish(MapArrays a, MapParams mp) {
   extern __shared__ double s_particles[];
-  create_body(a, cam, mp);
+  create_body(a, mp);
   __syncthreads();           // what lane 0 wrote about the new feature is read by every lane below
   update_body(a, mp, s_particles);
 }
@@ -980,12 +985,13 @@ static MapArrays map_arrays(const sl2_engine* e, bool honour_mask) {
   a.traj_count = e->traj_count; a.pos_count = e->pos_count; a.parts_mail = e->root->parts_mail_dev;
   a.N = e->N; a.ld = e->ld; a.ppos0 = e->ppos;
   a.active = honour_mask ? e->active : nullptr;
+  a.seq_cam = e->seq_cam; a.width = e->cam.width; a.height = e->cam.height;
   return a;
 }
 
 static int launch_create(sl2_engine* e, const MapParams& mp, bool honour_mask) {
   LaunchScope ls(e, "k_map_create");
-  hipLaunchKernelGGL(k_map_create, dim3(e->B), dim3(64), 0, e->stream, map_arrays(e, honour_mask), e->cam, mp);
+  hipLaunchKernelGGL(k_map_create, dim3(e->B), dim3(64), 0, e->stream, map_arrays(e, honour_mask), mp);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -993,7 +999,8 @@ static int launch_create(sl2_engine* e, const MapParams& mp, bool honour_mask) {
 static int launch_find(sl2_engine* e, const MapParams& mp, bool honour_mask) {
   LaunchScope ls(e, "k_map_find");
   hipLaunchKernelGGL(k_map_find, dim3(e->B), dim3(kDetThreads), sizeof(double) * 2 * e->N, e->stream, e->x, e->f_flags, e->n_slots, e->n_vis,
-                     e->prev_r, e->seq_time, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride, e->cam, mp, e->N, e->ld,
+                     e->prev_r, e->seq_time, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride,
+                     e->seq_cam, e->cam.width, e->cam.height, mp, e->N, e->ld,
                      honour_mask ? e->active : nullptr);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
@@ -1030,7 +1037,7 @@ int launch_mapping(sl2_engine* e, const TailPlan& tp) {
   const size_t shm_particles = sizeof(double) * kParticleDoubles * (size_t)mp.n_particles;
   if (tp.finish) {
     LaunchScope ls(e, "k_map_finish");
-    hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), e->cam, mp);
+    hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), mp);
     SL2_HIP(hipGetLastError());
   }
   if (tp.create) { int rc = launch_create(e, mp, true); if (rc != SL2_OK) return rc; }
@@ -1039,7 +1046,7 @@ int launch_mapping(sl2_engine* e, const TailPlan& tp) {
     LaunchScope ls(e, "k_map_particles");
     const int pc = e->root->pcap;
 #define SL2_PARTICLES(T) hipLaunchKernelGGL(k_map_particles<T>, dim3(B, mp.kpart), dim3(pc), 0, e->stream, e->x, e->P, e->ps_i, e->particles, \
-                                            e->me_desc, e->last_r, e->root->me_big_count, e->part_i, tp.parts_full, e->cam, e->ld, e->ppos, pc, mp.kpart, e->active)
+                                            e->me_desc, e->last_r, e->root->me_big_count, e->part_i, tp.parts_full, e->seq_cam, e->cam.width, e->cam.height, e->ld, e->ppos, pc, mp.kpart, e->active)
     if (pc <= 128) SL2_PARTICLES(128);
     else if (pc <= 256) SL2_PARTICLES(256);
     else if (pc <= 512) SL2_PARTICLES(512);

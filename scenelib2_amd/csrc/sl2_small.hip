@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
     const int* __restrict__ part_i, int pend, int ld, double* __restrict__ seq_time,
     const double* __restrict__ xp_org, int* __restrict__ f_flags, double* __restrict__ f_h, double* __restrict__ f_Hx,
     double* __restrict__ f_Hy, double* __restrict__ f_R, double* __restrict__ f_S, double* __restrict__ f_score,
-    int* __restrict__ srch_i, double* __restrict__ srch_d, CameraParams cam, int N,
+    int* __restrict__ srch_i, double* __restrict__ srch_d, const double* __restrict__ seq_cam, int width, int height, int N,
     int* __restrict__ sel_idx, int* __restrict__ n_sel, int* __restrict__ n_vis, double* __restrict__ last_r,
     int* __restrict__ srch_sel, int n_want, int* __restrict__ srch_big, int split_bands,
     const uint8_t* __restrict__ active, int* __restrict__ sel_gate) {
@@ -48,6 +48,7 @@ __global__ void __launch_bounds__(kSmallThreads) k_small_front(
   predict_body(b, x, P, n_slots, prev_r, part_i, pend, ld, seq_time);
   __syncthreads();                                    // x and P of this sequence: written above, read below (same workgroup)
   SST(2, 1);
+  const CameraParams cam = load_cam(seq_cam, b, width, height);
   for (int i = threadIdx.x; i < N; i += (int)blockDim.x)
     feature_prediction_body(b, i, x, P, xp_org, f_flags, n_slots, f_h, f_Hx, f_Hy, f_R, f_S, f_score, srch_i, srch_d, cam, N, ld);
   __syncthreads();
@@ -307,7 +308,7 @@ int launch_small_front(sl2_engine* e, int n) {
   const size_t shm = (size_t)e->N * (sizeof(double) + 3 * sizeof(int));
   hipLaunchKernelGGL(k_small_front, dim3(e->B), dim3(kSmallThreads), shm, e->stream, e->x, e->P, e->n_slots, e->prev_r, e->part_i,
                      e->ppos + 6 * e->kpart, e->ld, e->seq_time, e->xp_org, e->f_flags, e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S,
-                     e->f_score, e->srch_i, e->srch_d, e->cam, e->N, e->sel_idx, e->n_sel, e->n_vis, e->last_r, e->srch_sel, n,
+                     e->f_score, e->srch_i, e->srch_d, e->seq_cam, e->cam.width, e->cam.height, e->N, e->sel_idx, e->n_sel, e->n_vis, e->last_r, e->srch_sel, n,
                      e->srch_big, (e->srch_big && e->root->search_variant == 1) ? e->root->search_split : 0, e->active, e->sel_gate);
   SL2_HIP(hipGetLastError());
   return SL2_OK;

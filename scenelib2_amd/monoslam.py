@@ -136,6 +136,24 @@ class Engine:
         default) clears what is owed (sl2_set_pause_catch_up)."""
         self._ck(self.L.sl2_set_pause_catch_up(self.h, int(bool(enabled))))
 
+    def set_cameras(self, cams, seq0=0):
+        """The calibration of sequences seq0, seq0 + 1, ... for every step issued from now on (sl2_set_cameras).  cams: a list of
+        camera dicts (or one dict) with the engine's width / height; fku, fkv, u0, v0, kd1 finite, fku and fkv not 0, sd >= 0 -
+        otherwise SL2_ERR_INVALID and nothing changes.  Consumed before the call returns; never synchronises, drops no captured
+        step, does not consult the mask."""
+        if isinstance(cams, dict):
+            cams = [cams]
+        arr = (_lib.sl2_camera * len(cams))(*[_lib.make_camera(c) for c in cams])
+        self._ck(self.L.sl2_set_cameras(self.h, int(seq0), len(cams), C.cast(arr, _lib.vp)))
+
+    def get_cameras(self, seq0=0, nseq=None):
+        """A list of camera dicts, one per sequence: the calibration as the setters called so far leave it (sl2_get_cameras; the
+        engine's host-side copy, no synchronisation)."""
+        nseq = self.batch - seq0 if nseq is None else nseq
+        arr = (_lib.sl2_camera * max(int(nseq), 1))()
+        self._ck(self.L.sl2_get_cameras(self.h, int(seq0), int(nseq), C.cast(arr, _lib.vp)))
+        return [dict(width=c.width, height=c.height, fku=c.fku, fkv=c.fkv, u0=c.u0, v0=c.v0, kd1=c.kd1, sd=c.sd) for c in arr[:nseq]]
+
     def set_groups(self, groups):
         self._ck(self.L.sl2_set_groups(self.h, int(groups)))
 
@@ -516,6 +534,15 @@ class MonoSLAM:
         """kDeltaT_ from the next GoOneStep on (the reference fixes it at Init; a camera whose frame rate changes does not)."""
         self._engine.set_delta_t(float(delta_t))
         self.kDeltaT_ = float(delta_t)
+
+    # Camera::SetCameraParameters(width, height, fku, fkv, u0, v0, kd1, sd) — camera.cpp:49-62
+    def SetCameraParameters(self, width, height, fku, fkv, u0, v0, kd1, sd):
+        """camera_'s calibration from the next GoOneStep on (a recalibrated camera, or another unit of the same model).  The image
+        size is fixed at Init: width / height must be the ones it was given."""
+        cam = dict(width=int(width), height=int(height), fku=float(fku), fkv=float(fkv), u0=float(u0), v0=float(v0),
+                   kd1=float(kd1), sd=int(sd))
+        self._engine.set_cameras([cam])
+        self.camera_.update(cam)
 
     # MonoSLAM::AddNewKnownFeature(y, xp, identifier) — monoslam.cpp:1278-1291
     def AddNewKnownFeature(self, y, xp, identifier):
