@@ -27,13 +27,10 @@ static_assert(kTrajCapacity * 24 % 64 == 0, "ring sections keep the 64-byte alig
 // 4-byte words per slot of the blob's per-slot arrays, in blob order (the header comment of include/scenelib2_amd.h)
 static const int kSlotWords[kSlotArrays] = {kPatchStride / 4, 2, 16, 1, 1, 1, 1, 1, 1, 4, 28, 12, 2, 8, 2, 4, 4, 1, 1, 2, 1, 1};
 
-struct CkptArrays {
-  double *x, *P, *prev_r, *last_r, *part_d, *ps_d, *particles, *traj, *pos_log;
+// What the two kernels take beside the engine's SeqArrays: the blob's per-slot arrays as a table they walk by index, and scalars.
+struct CkptParams {
   unsigned* slot[kSlotArrays];
   int slot_words[kSlotArrays];
-  int *n_slots, *next_label, *status, *pos_err_any, *n_sel, *n_vis, *m_count, *traj_count, *pos_count, *seq_age, *part_i, *ps_i, *sel_gate, *m_gate, *step_mark;
-  unsigned long long* rand48;
-  const double* seq_cam;      // every sequence's calibration: k_seq_pack records it in the header, nothing here writes it
   int N, ld, ppos, kpart, pcap, mapping_used;
   int width, height;          // the engine's image size
   sl2_params prm;
@@ -77,17 +74,17 @@ static size_t layout_host(int ns, int kp, int pc, uint64_t* out /* SL2_BLOB_LAYO
 // ----------------------------------------------------------------------------------------------------------------- pack
 // tiles - 1 row blocks of P, then the workgroup of the small arrays (header_only: that one alone, and of it the header alone:
 // what sl2_copy_sequences checks before it writes anything).
-__global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq0, int nseq, int tiles, unsigned char* __restrict__ blobs,
-                                                           size_t stride, int header_only) {
+__global__ void __launch_bounds__(kCkptThreads) k_seq_pack(const SeqArrays S, const CkptParams A, int seq0, int nseq, int tiles,
+                                                           unsigned char* __restrict__ blobs, size_t stride, int header_only) {
   int s, tile;
   if (!xcd_map(tiles, nseq, &s, &tile)) return;
   const int b = seq0 + s, tid = threadIdx.x;
   unsigned char* blob = blobs + (size_t)s * stride;
-  int ns = A.n_slots[b];
+  int ns = S.n_slots[b];
   ns = ns < 0 ? 0 : (ns > A.N ? A.N : ns);
   int kp = 0, pc = 0;
   for (int k = 0; k < A.kpart; ++k) {
-    const int* ps = A.ps_i + ((size_t)b * A.kpart + k) * kPsInts;
+    const int* ps = S.ps_i + ((size_t)b * A.kpart + k) * kPsInts;
     if (ps[kPsActive]) { kp = k + 1; const int np = ps[kPsNp]; pc = np > pc ? np : pc; }
   }
   pc = pc < 0 ? 0 : (pc > A.pcap ? A.pcap : pc);
@@ -99,7 +96,7 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
     const int r_end = (tile + 1) * kCkptRows < (int)n ? (tile + 1) * kCkptRows : (int)n;
     for (int r = tile * kCkptRows + wave; r < r_end; r += kCkptThreads / 64) {
       const int re = r < c1 ? r : ppos + (r - c1);
-      const double* __restrict__ src = A.P + (size_t)b * A.ld * A.ld + (size_t)re * A.ld;
+      const double* __restrict__ src = S.P + (size_t)b * A.ld * A.ld + (size_t)re * A.ld;
       double* __restrict__ dst = reinterpret_cast<double*>(blob + off_P) + (size_t)r * pitch;
       for (int c = 2 * lane; c < (int)pitch; c += 128) {
         double2 v;
@@ -118,7 +115,7 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
   for (int a = 0; a < kSlotArrays; ++a) off += up64((unsigned)ns * A.slot_words[a] * 4u);
   const BlobTail t = blob_tail(off, kp, pc);
   if (!header_only) {
-    const double* xb = A.x + (size_t)b * A.ld;
+    const double* xb = S.x + (size_t)b * A.ld;
     double* ox = reinterpret_cast<double*>(blob + off_x);
     for (int c = tid; c < (int)pitch; c += kCkptThreads) ox[c] = c < c1 ? xb[c] : (c < (int)n ? xb[ppos + (c - c1)] : 0.0);
     off = off_slots;
@@ -138,31 +135,31 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
     __syncthreads();
     int* qi = reinterpret_cast<int*>(s_seq);
     if (tid == 0) {
-      qi[0] = ns; qi[1] = A.next_label[b]; qi[2] = A.status[b]; qi[3] = A.pos_err_any[b]; qi[4] = A.n_sel[b]; qi[5] = A.n_vis[b];
-      qi[6] = A.m_count[b]; qi[7] = A.traj_count[b];
-      *reinterpret_cast<unsigned long long*>(s_seq + 4) = A.rand48[b];
-      for (int k = 0; k < 3; ++k) { s_seq[5 + k] = A.prev_r[b * 3 + k]; s_seq[8 + k] = A.last_r[b * 3 + k]; }
-      for (int k = 0; k < kPartDoubles; ++k) s_seq[11 + k] = A.part_d[(size_t)b * kPartDoubles + k];
+      qi[0] = ns; qi[1] = S.next_label[b]; qi[2] = S.status[b]; qi[3] = S.pos_err_any[b]; qi[4] = S.n_sel[b]; qi[5] = S.n_vis[b];
+      qi[6] = S.m_count[b]; qi[7] = S.traj_count[b];
+      *reinterpret_cast<unsigned long long*>(s_seq + 4) = S.rand48[b];
+      for (int k = 0; k < 3; ++k) { s_seq[5 + k] = S.prev_r[b * 3 + k]; s_seq[8 + k] = S.last_r[b * 3 + k]; }
+      for (int k = 0; k < kPartDoubles; ++k) s_seq[11 + k] = S.part_d[(size_t)b * kPartDoubles + k];
     }
-    if (tid < kPartInts) qi[32 + tid] = A.part_i[(size_t)b * kPartInts + tid];
-    if (tid >= 64 && tid < 64 + kp * kPsInts) qi[48 + tid - 64] = A.ps_i[(size_t)b * A.kpart * kPsInts + tid - 64];
-    if (tid >= 128 && tid < 128 + kp * kPsDoubles) s_seq[40 + tid - 128] = A.ps_d[(size_t)b * A.kpart * kPsDoubles + tid - 128];
+    if (tid < kPartInts) qi[32 + tid] = S.part_i[(size_t)b * kPartInts + tid];
+    if (tid >= 64 && tid < 64 + kp * kPsInts) qi[48 + tid - 64] = S.ps_i[(size_t)b * A.kpart * kPsInts + tid - 64];
+    if (tid >= 128 && tid < 128 + kp * kPsDoubles) s_seq[40 + tid - 128] = S.ps_d[(size_t)b * A.kpart * kPsDoubles + tid - 128];
     __syncthreads();
     double* oq = reinterpret_cast<double*>(blob + t.off_seq);
     for (int i = tid; i < kSeqBytes / 8; i += kCkptThreads) oq[i] = s_seq[i];
     double* op = reinterpret_cast<double*>(blob + t.off_particles);
     const int per = pc * kParticleDoubles, ptot = kp * per, ppad = (ptot + 7) & ~7;
     for (int i = tid; i < ppad; i += kCkptThreads)
-      op[i] = i < ptot ? A.particles[((size_t)b * A.kpart + i / per) * A.pcap * kParticleDoubles + i % per] : 0.0;
+      op[i] = i < ptot ? S.particles[((size_t)b * A.kpart + i / per) * A.pcap * kParticleDoubles + i % per] : 0.0;
     double* ot = reinterpret_cast<double*>(blob + t.off_traj);
-    const double* tr = A.traj + (size_t)b * kTrajCapacity * 3;
+    const double* tr = S.traj + (size_t)b * kTrajCapacity * 3;
     for (int i = tid; i < kTrajCapacity * 3; i += kCkptThreads) ot[i] = tr[i];
     double* ol = reinterpret_cast<double*>(blob + t.off_pos_log);
-    const double* lg = A.pos_log + (size_t)b * kTrajCapacity * 3;
+    const double* lg = S.pos_log + (size_t)b * kTrajCapacity * 3;
     // oldest first, the newest entry last.  The ring is indexed by the ENGINE's step; how far back it holds this sequence is
     // the sequence's own age (a loaded sequence brought entries from before this engine's first step along).
-    const int steps = A.pos_count[b];
-    const long long own = (long long)steps + A.seq_age[b];
+    const int steps = S.pos_count[b];
+    const long long own = (long long)steps + S.seq_age[b];
     for (int i = tid; i < kTrajCapacity * 3; i += kCkptThreads) {
       const int j = i / 3;
       int slot = (steps - kTrajCapacity + j) % kTrajCapacity;
@@ -178,7 +175,7 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
   __syncthreads();
   if (tid == 0) {
     hd.magic = SL2_BLOB_MAGIC; hd.layout_version = SL2_BLOB_LAYOUT_VERSION; hd.bytes = t.bytes;
-    hd.sequence_steps = (long long)A.pos_count[b] + A.seq_age[b];
+    hd.sequence_steps = (long long)S.pos_count[b] + S.seq_age[b];
     hd.src_max_features = A.N; hd.src_partial_slots = A.kpart; hd.src_particle_capacity = A.pcap;
     hd.width = A.width; hd.height = A.height;
     hd.n_slots = ns; hd.n_partial_slots = kp; hd.n_particles = pc; hd.mapping_in_use = A.mapping_used;
@@ -186,13 +183,13 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
     hd.off_traj = t.off_traj; hd.off_pos_log = t.off_pos_log;
     hd.row_pitch = (int)pitch; hd.state_size = (int)n;
     {   // the calibration the sequence ran under: its own record (the sl2_create camera's values until sl2_set_cameras)
-      const double* rec = A.seq_cam + (size_t)b * kSeqCamDoubles;
+      const double* rec = S.seq_cam + (size_t)b * kSeqCamDoubles;
       hd.camera.width = A.width; hd.camera.height = A.height;
       hd.camera.fku = rec[kSeqCamFku]; hd.camera.fkv = rec[kSeqCamFkv]; hd.camera.u0 = rec[kSeqCamU0]; hd.camera.v0 = rec[kSeqCamV0];
       hd.camera.kd1 = rec[kSeqCamKd1]; hd.camera.sd = (int)rec[kSeqCamSd];
     }
     hd.params = A.prm;
-    hd.n_selected = A.n_sel[b];
+    hd.n_selected = S.n_sel[b];
   }
   __syncthreads();
   if (tid < 64) reinterpret_cast<int*>(blob)[tid] = reinterpret_cast<const int*>(&hd)[tid];
@@ -201,8 +198,8 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_pack(CkptArrays A, int seq
 // --------------------------------------------------------------------------------------------------------------- unpack
 // blobs == nullptr: the empty blob (sl2_reset_sequences).  Headers were checked on the host; a blob that does not fit is left
 // alone here all the same (nothing is written outside the destination's arrays whatever the bytes say).
-__global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int seq0, int nseq, int tiles, const unsigned char* __restrict__ blobs,
-                                                             size_t stride, long long steps_done) {
+__global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(const SeqArrays S, const CkptParams A, int seq0, int nseq, int tiles,
+                                                             const unsigned char* __restrict__ blobs, size_t stride, long long steps_done) {
   int s, tile;
   if (!xcd_map(tiles, nseq, &s, &tile)) return;
   const int b = seq0 + s, tid = threadIdx.x;
@@ -222,7 +219,7 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int s
     const int r_end = (tile + 1) * kCkptRows < ld ? (tile + 1) * kCkptRows : ld;
     for (int r = tile * kCkptRows + wave; r < r_end; r += kCkptThreads / 64) {
       const int rb = !blob ? -1 : (r < c1 ? r : (r >= ppos && r < pend ? c1 + (r - ppos) : -1));
-      double* __restrict__ dst = A.P + (size_t)b * ld * ld + (size_t)r * ld;
+      double* __restrict__ dst = S.P + (size_t)b * ld * ld + (size_t)r * ld;
       const double* __restrict__ src = rb >= 0 ? reinterpret_cast<const double*>(blob + off_P) + (size_t)rb * pitch : nullptr;
       for (int c = 2 * lane; c < ld; c += 128) {
         double2 v = make_double2(0.0, 0.0);
@@ -240,7 +237,7 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int s
   }
   // ---- the small arrays
   {
-    double* xb = A.x + (size_t)b * ld;
+    double* xb = S.x + (size_t)b * ld;
     const double* ix = blob ? reinterpret_cast<const double*>(blob + off_x) : nullptr;
     for (int c = tid; c < ld; c += kCkptThreads) xb[c] = !ix ? 0.0 : (c < c1 ? ix[c] : (c >= ppos && c < pend ? ix[c1 + (c - ppos)] : 0.0));
   }
@@ -263,24 +260,24 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int s
   __syncthreads();
   const int* qi = reinterpret_cast<const int*>(s_seq);
   if (tid == 0) {
-    A.n_slots[b] = ns; A.next_label[b] = qi[1]; A.status[b] = qi[2]; A.pos_err_any[b] = qi[3]; A.n_sel[b] = qi[4]; A.n_vis[b] = qi[5];
-    A.m_count[b] = qi[6]; A.traj_count[b] = qi[7];
-    A.sel_gate[b] = qi[4]; A.m_gate[b] = qi[6];       // the per-step gates (sl2_common.hpp) follow what they gate: a seam called next finds the loaded frame
-    A.step_mark[b] = 0;                               // ... but the record of sl2_get_step_stats starts again: this sequence has not stepped HERE
-    A.rand48[b] = blob ? *reinterpret_cast<const unsigned long long*>(s_seq + 4) : kRand48Seed0;
-    for (int k = 0; k < 3; ++k) { A.prev_r[b * 3 + k] = s_seq[5 + k]; A.last_r[b * 3 + k] = s_seq[8 + k]; }
-    for (int k = 0; k < kPartDoubles; ++k) A.part_d[(size_t)b * kPartDoubles + k] = s_seq[11 + k];
+    S.n_slots[b] = ns; S.next_label[b] = qi[1]; S.status[b] = qi[2]; S.pos_err_any[b] = qi[3]; S.n_sel[b] = qi[4]; S.n_vis[b] = qi[5];
+    S.m_count[b] = qi[6]; S.traj_count[b] = qi[7];
+    S.sel_gate[b] = qi[4]; S.m_gate[b] = qi[6];       // the per-step gates (sl2_common.hpp) follow what they gate: a seam called next finds the loaded frame
+    S.step_mark[b] = 0;                               // ... but the record of sl2_get_step_stats starts again: this sequence has not stepped HERE
+    S.rand48[b] = blob ? *reinterpret_cast<const unsigned long long*>(s_seq + 4) : kRand48Seed0;
+    for (int k = 0; k < 3; ++k) { S.prev_r[b * 3 + k] = s_seq[5 + k]; S.last_r[b * 3 + k] = s_seq[8 + k]; }
+    for (int k = 0; k < kPartDoubles; ++k) S.part_d[(size_t)b * kPartDoubles + k] = s_seq[11 + k];
     // the step clock is the destination's (finalize_body and k_map_update publish pos_count, the host compares it with steps_done)
-    A.pos_count[b] = (int)steps_done;
-    A.seq_age[b] = (int)(age - steps_done);
+    S.pos_count[b] = (int)steps_done;
+    S.seq_age[b] = (int)(age - steps_done);
   }
-  if (tid < kPartInts) A.part_i[(size_t)b * kPartInts + tid] = qi[32 + tid];
-  if (tid >= 64 && tid < 64 + A.kpart * kPsInts) A.ps_i[(size_t)b * A.kpart * kPsInts + tid - 64] = tid - 64 < kp * kPsInts ? qi[48 + tid - 64] : 0;
-  if (tid >= 128 && tid < 128 + A.kpart * kPsDoubles) A.ps_d[(size_t)b * A.kpart * kPsDoubles + tid - 128] = tid - 128 < kp * kPsDoubles ? s_seq[40 + tid - 128] : 0.0;
+  if (tid < kPartInts) S.part_i[(size_t)b * kPartInts + tid] = qi[32 + tid];
+  if (tid >= 64 && tid < 64 + A.kpart * kPsInts) S.ps_i[(size_t)b * A.kpart * kPsInts + tid - 64] = tid - 64 < kp * kPsInts ? qi[48 + tid - 64] : 0;
+  if (tid >= 128 && tid < 128 + A.kpart * kPsDoubles) S.ps_d[(size_t)b * A.kpart * kPsDoubles + tid - 128] = tid - 128 < kp * kPsDoubles ? s_seq[40 + tid - 128] : 0.0;
   {
     const double* ip = blob ? reinterpret_cast<const double*>(blob + t.off_particles) : nullptr;
     const int per = pc * kParticleDoubles, cap = A.pcap * kParticleDoubles;
-    double* dp = A.particles + (size_t)b * A.kpart * cap;
+    double* dp = S.particles + (size_t)b * A.kpart * cap;
     for (int i = tid; i < A.kpart * cap; i += kCkptThreads) {
       const int k = i / cap, j = i % cap;
       dp[i] = (k < kp && j < per) ? ip[k * per + j] : 0.0;
@@ -288,10 +285,10 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int s
   }
   {
     const double* it = blob ? reinterpret_cast<const double*>(blob + t.off_traj) : nullptr;
-    double* tr = A.traj + (size_t)b * kTrajCapacity * 3;
+    double* tr = S.traj + (size_t)b * kTrajCapacity * 3;
     for (int i = tid; i < kTrajCapacity * 3; i += kCkptThreads) tr[i] = it ? it[i] : 0.0;
     const double* il = blob ? reinterpret_cast<const double*>(blob + t.off_pos_log) : nullptr;
-    double* lg = A.pos_log + (size_t)b * kTrajCapacity * 3;
+    double* lg = S.pos_log + (size_t)b * kTrajCapacity * 3;
     for (int i = tid; i < kTrajCapacity * 3; i += kCkptThreads) {
       long long logical = (steps_done - kTrajCapacity + i / 3) % kTrajCapacity;     // the blob's newest entry becomes the destination's newest
       if (logical < 0) logical += kTrajCapacity;
@@ -302,19 +299,13 @@ __global__ void __launch_bounds__(kCkptThreads) k_seq_unpack(CkptArrays A, int s
 
 // ----------------------------------------------------------------------------------------------------------------- host
 
-static CkptArrays arrays_of(sl2_engine* e) {
-  CkptArrays A;
+static CkptParams ckpt_params(sl2_engine* e) {
+  CkptParams A;
   memset(&A, 0, sizeof(A));
-  A.x = e->x; A.P = e->P; A.prev_r = e->prev_r; A.last_r = e->last_r; A.part_d = e->part_d; A.ps_d = e->ps_d; A.particles = e->particles;
-  A.traj = e->traj; A.pos_log = e->pos_log;
   void* slot[kSlotArrays] = {e->patch, e->patch_sums, e->xp_org, e->f_flags, e->f_label, e->attempted, e->successful, e->pos_err, e->f_hcol,
                              e->f_h, e->f_Hx, e->f_Hy, e->f_R, e->f_S, e->f_score, e->f_z, e->f_nu, e->sel_idx, e->meas_ok, e->meas_score,
                              e->succ_idx, e->f_arow};
   for (int a = 0; a < kSlotArrays; ++a) { A.slot[a] = (unsigned*)slot[a]; A.slot_words[a] = kSlotWords[a]; }
-  A.n_slots = e->n_slots; A.next_label = e->next_label; A.status = e->status; A.pos_err_any = e->pos_err_any; A.n_sel = e->n_sel;
-  A.n_vis = e->n_vis; A.m_count = e->m_count; A.traj_count = e->traj_count; A.pos_count = e->pos_count; A.seq_age = e->seq_age;
-  A.sel_gate = e->sel_gate; A.m_gate = e->m_gate; A.step_mark = e->step_mark;
-  A.part_i = e->part_i; A.ps_i = e->ps_i; A.rand48 = e->rand48; A.seq_cam = e->seq_cam;
   A.N = e->N; A.ld = e->ld; A.ppos = e->ppos; A.kpart = e->kpart; A.pcap = e->pcap; A.mapping_used = e->mapping_used ? 1 : 0;
   // (field by field into zeroed structures: the blob's copies carry no padding bytes of the caller's)
   A.width = e->cam.width; A.height = e->cam.height;
@@ -336,15 +327,15 @@ static int unpack_tiles(const sl2_engine* e) { return (e->ld + kCkptRows - 1) / 
 static int launch_pack(sl2_engine* e, int seq0, int nseq, void* blobs, size_t stride, int header_only, hipStream_t st) {
   const int tiles = header_only ? 1 : pack_tiles(e);
   LaunchScope ls(e, "k_seq_pack");
-  hipLaunchKernelGGL(k_seq_pack, dim3(xcd_grid(tiles, nseq)), dim3(kCkptThreads), 0, st, arrays_of(e), seq0, nseq, tiles, (unsigned char*)blobs,
-                     stride, header_only);
+  hipLaunchKernelGGL(k_seq_pack, dim3(xcd_grid(tiles, nseq)), dim3(kCkptThreads), 0, st, seq_arrays(e), ckpt_params(e), seq0, nseq, tiles,
+                     (unsigned char*)blobs, stride, header_only);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 static int launch_unpack(sl2_engine* e, int seq0, int nseq, const void* blobs, size_t stride, hipStream_t st) {
   const int tiles = unpack_tiles(e);
   LaunchScope ls(e, "k_seq_unpack");
-  hipLaunchKernelGGL(k_seq_unpack, dim3(xcd_grid(tiles, nseq)), dim3(kCkptThreads), 0, st, arrays_of(e), seq0, nseq, tiles,
+  hipLaunchKernelGGL(k_seq_unpack, dim3(xcd_grid(tiles, nseq)), dim3(kCkptThreads), 0, st, seq_arrays(e), ckpt_params(e), seq0, nseq, tiles,
                      (const unsigned char*)blobs, stride, e->steps_done);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
@@ -406,7 +397,7 @@ static int check_header(sl2_engine* e, int dst_seq, const sl2_sequence_blob_head
       h.off_particles != off[4 + kSlotArrays] || h.off_traj != off[5 + kSlotArrays] || h.off_pos_log != off[6 + kSlotArrays] ||
       h.row_pitch != (int)pitch || h.state_size != (int)n)
     return refuse(SL2_ERR_INVALID, index, "section offsets", "do not match the layout");
-  const CkptArrays A = arrays_of(e);
+  const CkptParams A = ckpt_params(e);
   if (memcmp(&h.camera, &e->cams_host[dst_seq], sizeof(sl2_camera)) != 0 || h.width != A.width || h.height != A.height)
     return refuse(SL2_ERR_INVALID, index, "camera", "differs from the destination sequence's");
   sl2_params p = h.params;

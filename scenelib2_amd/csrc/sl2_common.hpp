@@ -67,11 +67,11 @@ constexpr int kSrchBigEntries = 4;                    // int offsets into srch_b
 constexpr int kSrchBigDone = kSrchBigEntries + 4 * kSrchBigUnits;
 constexpr int kSrchBigParts = kSrchBigDone + kSrchBigUnits;
 constexpr int kSrchBigInts = kSrchBigParts + 8 * kSrchBigUnits;
-// seq_time, the per-sequence time record (sl2_engine::seq_time): doubles per sequence and their places
-constexpr int kSeqTimeDoubles = 4, kSeqTimeNominal = 0, kSeqTimeOwed = 1, kSeqTimeUsed = 2, kSeqTimeCatchUp = 3;
-// seq_cam, the per-sequence camera calibration (sl2_engine::seq_cam): doubles per sequence - one 64-byte line - and their places;
+// seq_time, the per-sequence time record (sl2_engine::seq_time): the places of its kSeqTimeDoubles doubles
+constexpr int kSeqTimeNominal = 0, kSeqTimeOwed = 1, kSeqTimeUsed = 2, kSeqTimeCatchUp = 3;
+// seq_cam, the per-sequence camera calibration (sl2_engine::seq_cam): the places of its kSeqCamDoubles doubles - one 64-byte line;
 // [6] and [7] are spare and stay 0.  sd is kept as a double: CameraParams::sd only ever enters cam.sd * (1.0 + ratio), an exact conversion.
-constexpr int kSeqCamDoubles = 8, kSeqCamFku = 0, kSeqCamFkv = 1, kSeqCamU0 = 2, kSeqCamV0 = 3, kSeqCamKd1 = 4, kSeqCamSd = 5;
+constexpr int kSeqCamFku = 0, kSeqCamFkv = 1, kSeqCamU0 = 2, kSeqCamV0 = 3, kSeqCamKd1 = 4, kSeqCamSd = 5;
 static_assert(kSeqCamDoubles * sizeof(double) == 64, "one cache line per sequence");
 __host__ __device__ inline int srch_unit_bands(int bands) { const int g = (bands + kSrchBigSlots - 1) / kSrchBigSlots; return g > kSrchBigMinBands ? g : kSrchBigMinBands; }
 // Partially initialised features: up to kMaxPartial per sequence (params.max_features_to_init_at_once, monoslam.cpp:163-167).
@@ -193,26 +193,19 @@ struct sl2_engine : sl2::SeqArrays {
   int search_split = sl2::kSrchSplitDefault;   // windows of at least this many 32 x 16 bands are shared out over wavefronts (0 = never); sl2_create: srch_split_default, then sl2_set_search_split
   // ---- large search windows (round 4): the step's units of work for every wavefront of k_search_mfma (layout: kSrchBig* above) ----
   int* srch_big = nullptr;    // per sequence GROUP (allocated by build_groups)
-  // ---- the per-step consistency record (sl2_get_step_stats, sl2_stats.hip) ----
-  // [B] 1 = the sequence took part in the last make_measurements (k_search_score / k_small_back write it next to m_gate: 1 for an
-  // active sequence, 0 for a paused one) and has not been loaded, copied in or reset since (k_seq_unpack clears it).  One word
-  // of engine state OUTSIDE SL2_SEQ_ARRAYS: allocated by sl2_create, a group sees it from its first sequence on (build_groups).
-  int* step_mark = nullptr;
-  // ---- the per-sequence time step (sl2_set_delta_t) ----
-  // [B][kSeqTimeDoubles]: [0] the sequence's nominal time step (params.delta_t after sl2_create), [1] time owed by predicts a
-  // paused sequence skipped (catch-up on only), [2] the step its last predict used (the speed gate of k_map_find divides by it),
-  // [3] the catch-up switch, 0 or 1.  Read and written by predict_body and the paused branch of its two kernels; the setters
-  // write it with kernels on the engine's stream, so a captured step reads it as data.  Engine state like step_mark: outside
-  // SL2_SEQ_ARRAYS, in no sequence blob, a group sees it from its first sequence on (build_groups).
-  double* seq_time = nullptr;
-  // ---- the per-sequence camera calibration (sl2_set_cameras) ----
-  // [B][kSeqCamDoubles]: fku, fkv, u0, v0, kd1, sd of the sequence (the sl2_create camera's until sl2_set_cameras), two spare
-  // words.  Read through load_cam by every step kernel that projects or unprojects; written only by the setter's kernel on the
-  // engine's stream, so a captured step reads it as data.  Engine state like seq_time: outside SL2_SEQ_ARRAYS, a group sees it
-  // from its first sequence on (build_groups); a sequence blob RECORDS it (header.camera) and a load checks it, but nothing
-  // but the setter writes it.  cams_host (root only) is the host's copy of what the setters queued so far: sl2_get_cameras and the
-  // checkpoint checks answer from it without waiting for the device.
-  double* seq_cam = nullptr;
+  // ---- three rows of SL2_SEQ_ARRAYS that are engine state of a sequence, in no sequence blob ----
+  // step_mark (sl2_get_step_stats, sl2_stats.hip): 1 = the sequence took part in the last make_measurements
+  // (k_search_score / k_small_back write it next to m_gate: 1 for an active sequence, 0 for a paused one) and has not been loaded,
+  // copied in or reset since (k_seq_unpack clears it).
+  // seq_time (sl2_set_delta_t): [0] the sequence's nominal time step (params.delta_t after sl2_create), [1] time owed
+  // by predicts a paused sequence skipped (catch-up on only), [2] the step its last predict used (the speed gate of k_map_find
+  // divides by it), [3] the catch-up switch, 0 or 1.  Read and written by predict_body and the paused branch of its two kernels;
+  // the setters write it with kernels on the engine's stream, so a captured step reads it as data.
+  // seq_cam (sl2_set_cameras): fku, fkv, u0, v0, kd1, sd of the sequence (the sl2_create camera's until
+  // sl2_set_cameras), two spare words.  Read through load_cam by every step kernel that projects or unprojects; written only by
+  // the setter's kernel on the engine's stream, so a captured step reads it as data.  A sequence blob RECORDS it (header.camera)
+  // and a load checks it, but nothing but the setter writes it.  cams_host (root only) is the host's copy of what the setters
+  // queued so far: sl2_get_cameras and the checkpoint checks answer from it without waiting for the device.
   std::vector<sl2_camera> cams_host;
   void* stats_host = nullptr;      // pinned + mapped host memory the host form of sl2_get_step_stats fills: [B] records (first use)
   void* stats_host_dev = nullptr;  // its device-side address
@@ -260,6 +253,9 @@ struct sl2_engine : sl2::SeqArrays {
 };
 
 namespace sl2 {
+
+// What a kernel receives of an engine or a group: the table of its per-sequence arrays, by value, beside a struct of scalars.
+inline const SeqArrays& seq_arrays(const sl2_engine* e) { return *e; }
 
 // RAII-less helper: bracket a launch with events when profiling is on.
 struct LaunchScope {

@@ -182,9 +182,6 @@ static int build_groups(sl2_engine* e, int G) {
     g->ppos = e->ppos; g->pcap = e->pcap; g->kpart = e->kpart;
     g->root = e; g->group_first = first;
     static_cast<SeqArrays&>(*g) = seq_arrays_view(*e, dims, first);
-    g->step_mark = e->step_mark + first;       // (not a row of SL2_SEQ_ARRAYS: sl2_common.hpp)
-    g->seq_time = e->seq_time + kSeqTimeDoubles * first;      // (nor is the time record)
-    g->seq_cam = e->seq_cam + kSeqCamDoubles * first;         // (nor the calibration)
     const int rc = [&]() -> int {
       if (G == 1) g->stream = e->stream; else SL2_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
       // the group's list of large search windows: count and counters start at zero and are returned to zero by k_search_score
@@ -482,15 +479,13 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
 #undef X
   }
   SL2_HIP(hipMemset(e->active, 1, B));                               // every sequence takes part until sl2_set_active_sequences says otherwise
-  { const int r = dmalloc(&e->step_mark, B); if (r != SL2_OK) return r; }      // nobody has stepped yet (sl2_get_step_stats)
+  // (step_mark stays zero: nobody has stepped yet - sl2_get_step_stats)
   {   // every sequence starts on the engine's time step: nothing owed, no predict yet, catch-up off (sl2_set_delta_t)
-    const int r = dmalloc(&e->seq_time, B * kSeqTimeDoubles); if (r != SL2_OK) return r;
     std::vector<double> rec(B * kSeqTimeDoubles, 0.0);
     for (size_t b = 0; b < B; ++b) rec[b * kSeqTimeDoubles + kSeqTimeNominal] = e->prm.delta_t;
     SL2_HIP(hipMemcpy(e->seq_time, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
   }
   {   // every sequence starts with the engine's calibration (sl2_set_cameras)
-    const int r = dmalloc(&e->seq_cam, B * kSeqCamDoubles); if (r != SL2_OK) return r;
     std::vector<double> rec(B * kSeqCamDoubles, 0.0);
     for (size_t b = 0; b < B; ++b) {
       double* c = &rec[b * kSeqCamDoubles];
@@ -578,9 +573,6 @@ void sl2_destroy(sl2_engine* e) {
   for (void* p : lazy) if (p) hipFree(p);
   release_checkpoint_staging(e);
   if (e->slots_max_dev) hipFree(e->slots_max_dev);
-  if (e->step_mark) hipFree(e->step_mark);
-  if (e->seq_time) hipFree(e->seq_time);
-  if (e->seq_cam) hipFree(e->seq_cam);
   if (e->stats_host) hipHostFree(e->stats_host);
   if (e->slots_mail) hipHostFree(e->slots_mail);
   if (e->snap_stage) hipFree(e->snap_stage);

@@ -33,6 +33,12 @@ struct MapParams {
   int kpart;      // partial slots per sequence (sl2_engine::kpart)
   // One-sequence engines (launch_mapping): k_map_update reports how many partially initialised features the step leaves, and a
   // step issued while the report says "none" runs without k_map_particles / k_map_me_search / k_me_big.
+  // what the per-sequence kernels take beside the group's SeqArrays (k_map_create, k_map_update, k_map_finish)
+  int N, ld, ppos;          // the engine's shape: feature capacity, leading dimension, first column of the partial features' states
+  int width, height;        // the engine's image geometry (every sequence's calibration: load_cam)
+  int honour_mask;          // 1: the launch of a step, which leaves paused sequences alone (sl2_set_active_sequences); 0: the caller's explicit act on every sequence
+  const uint8_t* frames; size_t seq_stride;
+  unsigned long long* parts_mail;
   int parts_skipped = 0;    // this step runs without them: k_map_create does the one thing k_map_particles does to a feature of this frame
   int publish_parts = 0;    // k_map_update writes (steps completed << 32) | partial features left to parts_mail
 };
@@ -170,38 +176,26 @@ __global__ void __launch_bounds__(kDetThreads) k_map_find(const double* __restri
 }
 
 // ---------------------------------------------------------------------------
-// k_map_create: one wavefront per sequence.  The arguments of the feature-initialisation tail's per-sequence kernels travel
-// in one struct: create_body and update_body run as kernels of their own, or one after the other in k_map_finish.
+// k_map_create: one wavefront per sequence.  The feature-initialisation tail's per-sequence kernels take the group's array
+// table and MapParams: create_body and update_body run as kernels of their own, or one after the other in k_map_finish.
 // ---------------------------------------------------------------------------
-struct MapArrays {
-  double *x, *P;
-  const uint8_t* frames; size_t seq_stride;
-  uint8_t* patch; int* patch_sums; double* xp_org;
-  int *f_flags, *n_slots, *attempted, *successful, *f_label, *next_label, *part_i;
-  double* part_d; int* ps_i; double* ps_d; int *pos_err, *pos_err_any;
-  double *particles, *last_r, *traj; int* traj_count; const int* pos_count; unsigned long long* parts_mail;
-  int N, ld, ppos0;
-  const uint8_t* active;      // the step's mask (sl2_set_active_sequences); nullptr: the caller's explicit act on every sequence
-  const double* seq_cam; int width, height;      // every sequence's calibration (load_cam) and the engine's image geometry
-};
-
-__device__ __forceinline__ void create_body(const MapArrays& a, const MapParams& mp) {
-  double* __restrict__ x = a.x; double* __restrict__ P = a.P; const uint8_t* __restrict__ frames = a.frames;
-  const size_t seq_stride = a.seq_stride;
+__device__ __forceinline__ void create_body(const SeqArrays& a, const MapParams& mp) {
+  double* __restrict__ x = a.x; double* __restrict__ P = a.P; const uint8_t* __restrict__ frames = mp.frames;
+  const size_t seq_stride = mp.seq_stride;
   uint8_t* __restrict__ patch = a.patch; int* __restrict__ patch_sums = a.patch_sums; double* __restrict__ xp_org = a.xp_org;
   int* __restrict__ f_flags = a.f_flags; int* __restrict__ n_slots = a.n_slots; int* __restrict__ attempted = a.attempted;
   int* __restrict__ successful = a.successful; int* __restrict__ f_label = a.f_label; int* __restrict__ next_label = a.next_label;
   int* __restrict__ part_i = a.part_i; double* __restrict__ part_d = a.part_d; int* __restrict__ ps_i = a.ps_i;
   double* __restrict__ ps_d = a.ps_d; int* __restrict__ pos_err = a.pos_err; double* __restrict__ particles = a.particles;
   double* __restrict__ last_r = a.last_r;
-  const int N = a.N, ld = a.ld, ppos0 = a.ppos0;
+  const int N = mp.N, ld = mp.ld, ppos0 = mp.ppos;
   const int b = blockIdx.x, lane = threadIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
   double* pd = part_d + (size_t)b * kPartDoubles;
-  if (a.active && !a.active[b]) return;        // a paused sequence (uniform): its flags of the last frame it saw are not acted on again
+  if (mp.honour_mask && !a.active[b]) return;  // a paused sequence (uniform): its flags of the last frame it saw are not acted on again
   if (!pi[kPartRegionValid]) return;
   if (!(pd[2] > 20000)) return;        // SUITABLE_PATCH_SCORE_THRESHOLD (:837, 850-858)
-  const CameraParams cam = load_cam(a.seq_cam, b, a.width, a.height);
+  const CameraParams cam = load_cam(a.seq_cam, b, mp.width, mp.height);
   // the partial slot this feature takes: the first free one (k_map_find / k_map_manual checked that there is one)
   int* psb = ps_i + (size_t)b * mp.kpart * kPsInts;
   int ks = 0;
@@ -338,7 +332,7 @@ __device__ __forceinline__ void create_body(const MapArrays& a, const MapParams&
   }
 }
 
-__global__ void __launch_bounds__(64) k_map_create(MapArrays a, MapParams mp) { create_body(a, mp); }
+__global__ void __launch_bounds__(64) k_map_create(const SeqArrays a, const MapParams mp) { create_body(a, mp); }
 
 // ---------------------------------------------------------------------------
 // k_map_particles: one workgroup per sequence, one thread per particle.
@@ -451,17 +445,17 @@ __global__ void __launch_bounds__(1024) k_map_me_search(MeJobsEngine J, int* __r
 // decide the bits of the weights, and through them pruning and conversion).  The covariance surgery of a conversion /
 // deletion is done by all lanes.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void update_body(const MapArrays& a, const MapParams& mp, double* s_p /* [number_of_particles][kParticleDoubles] */) {
+__device__ __forceinline__ void update_body(const SeqArrays& a, const MapParams& mp, double* s_p /* [number_of_particles][kParticleDoubles] */) {
   double* __restrict__ x = a.x; double* __restrict__ P = a.P; int* __restrict__ f_flags = a.f_flags;
   const int* __restrict__ n_slots = a.n_slots; int* __restrict__ part_i = a.part_i; int* __restrict__ ps_i = a.ps_i;
   double* __restrict__ ps_d = a.ps_d; int* __restrict__ pos_err = a.pos_err; int* __restrict__ pos_err_any = a.pos_err_any;
   double* __restrict__ particles = a.particles; double* __restrict__ traj = a.traj; int* __restrict__ traj_count = a.traj_count;
   const double* __restrict__ last_r = a.last_r; const int* __restrict__ pos_count = a.pos_count;
-  unsigned long long* __restrict__ parts_mail = a.parts_mail;
-  const int N = a.N, ld = a.ld, ppos0 = a.ppos0;
+  unsigned long long* __restrict__ parts_mail = mp.parts_mail;
+  const int N = mp.N, ld = mp.ld, ppos0 = mp.ppos;
   const int b = blockIdx.x, lane = threadIdx.x;
   int* pi = part_i + (size_t)b * kPartInts;
-  if (a.active && !a.active[b]) {
+  if (mp.honour_mask && !a.active[b]) {
     // a paused sequence (uniform): nothing of it changes, no trajectory push.  A one-sequence engine still reports - the count its
     // partial features stand at, under the step index k_finalize has just counted - so that the host's next step takes the same
     // shortcuts it would have taken (sl2_engine.hip: parts_state_for_step)
@@ -721,14 +715,14 @@ __device__ __forceinline__ void update_body(const MapArrays& a, const MapParams&
   }
 }
 
-__global__ void __launch_bounds__(64) k_map_update(MapArrays a, MapParams mp) {
+__global__ void __launch_bounds__(64) k_map_update(const SeqArrays a, const MapParams mp) {
   extern __shared__ double s_particles[];
   update_body(a, mp, s_particles);
 }
 
 // A step that starts without a partially initialised feature (launch_mapping: parts_none) has nothing between the creation of
 // a feature and the end-of-frame bookkeeping: both in one launch.
-__global__ void __launch_bounds__(64) k_map_finish(MapArrays a, MapParams mp) {
+__global__ void __launch_bounds__(64) k_map_finish(const SeqArrays a, const MapParams mp) {
   extern __shared__ double s_particles[];
   create_body(a, mp);
   __syncthreads();           // what lane 0 wrote about the new feature is read by every lane below
@@ -749,21 +743,13 @@ __global__ void __launch_bounds__(64) k_map_finish(MapArrays a, MapParams mp) {
 // re-based through the map P's columns go through: a squeeze may come between the seams of a step (sl2_add_known_features
 // after sl2_auto_select_n_features or sl2_make_measurements), when those records are live.
 // ---------------------------------------------------------------------------
-struct SlotArrays {
-  double *x, *P, *xp_org, *f_h, *f_Hx, *f_Hy, *f_R, *f_S, *f_score, *f_z, *f_nu, *srch_d;
-  uint8_t* patch;
-  int *patch_sums, *f_flags, *attempted, *successful, *f_label, *srch_i, *sel_idx, *succ_idx, *f_arow, *n_sel, *m_count, *n_slots, *ps_i, *pos_err;
-  int *f_hcol, *srch_sel;
-  int kpart;
-  const uint8_t* active;     // the mask of a step's launch (nullptr: sl2_add_known_features and the "initialise feature" calls, which ignore it)
-};
-__global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, int ld, int ppos, int need) {
+__global__ void __launch_bounds__(256) k_map_compact_slots(const SeqArrays a, int N, int ld, int ppos, int kpart, int need, int honour_mask) {
   extern __shared__ int s_map[];        // [N] new slot -> old slot, then [N] old slot -> new slot (-1: retired)
   int* s_src = s_map;
   int* s_new = s_map + N;
   __shared__ int s_live;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  if (a.active && !a.active[b]) return;                          // a paused sequence of a step (uniform)
+  if (honour_mask && !a.active[b]) return;                       // a paused sequence of a step (uniform; the callers that ignore the mask: sl2_add_known_features, the "initialise feature" calls)
   const int ns = a.n_slots[b];
   if (ns + need <= N) return;                                    // room for what is about to be added: nothing to do
   int* flags = a.f_flags + (size_t)b * N;
@@ -877,8 +863,8 @@ __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, 
   // slot numbers held elsewhere
   for (int k = tid; k < a.n_sel[b]; k += nt) { const int f = a.sel_idx[o + k]; a.sel_idx[o + k] = (f >= 0 && f < ns) ? s_new[f] : -1; }
   for (int k = tid; k < a.m_count[b]; k += nt) { const int f = a.succ_idx[o + k]; a.succ_idx[o + k] = (f >= 0 && f < ns) ? s_new[f] : -1; }
-  if (tid < a.kpart) {
-    int* ps = a.ps_i + ((size_t)b * a.kpart + tid) * kPsInts;
+  if (tid < kpart) {
+    int* ps = a.ps_i + ((size_t)b * kpart + tid) * kPsInts;
     if (ps[kPsActive] && ps[kPsLabel] >= 0 && ps[kPsLabel] < ns) ps[kPsLabel] = s_new[ps[kPsLabel]];
   }
   // ---- P: new index i <- old index src(i); pose rows and the partial feature's six rows / the innovation row stay where
@@ -930,13 +916,8 @@ __global__ void __launch_bounds__(256) k_map_compact_slots(SlotArrays a, int N, 
 int launch_compact_slots(sl2_engine* e, int need, bool honour_mask) {
   if ((size_t)e->ld > 8 * 256) return SL2_OK;                     // (maps beyond 2048 states: slots are not squeezed)
   LaunchScope ls(e, "k_map_compact_slots");
-  SlotArrays a;
-  a.x = e->x; a.P = e->P; a.xp_org = e->xp_org; a.f_h = e->f_h; a.f_Hx = e->f_Hx; a.f_Hy = e->f_Hy; a.f_R = e->f_R; a.f_S = e->f_S;
-  a.f_score = e->f_score; a.f_z = e->f_z; a.f_nu = e->f_nu; a.srch_d = e->srch_d; a.patch = e->patch; a.patch_sums = e->patch_sums;
-  a.f_flags = e->f_flags; a.attempted = e->attempted; a.successful = e->successful; a.f_label = e->f_label; a.srch_i = e->srch_i;
-  a.sel_idx = e->sel_idx; a.succ_idx = e->succ_idx; a.f_arow = e->f_arow; a.n_sel = e->n_sel; a.m_count = e->m_count; a.n_slots = e->n_slots;
-  a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.f_hcol = e->f_hcol; a.srch_sel = e->srch_sel; a.kpart = e->kpart; a.active = honour_mask ? e->active : nullptr;
-  hipLaunchKernelGGL(k_map_compact_slots, dim3(e->B), dim3(256), sizeof(int) * 2 * e->N, e->stream, a, e->N, e->ld, e->ppos, need);
+  hipLaunchKernelGGL(k_map_compact_slots, dim3(e->B), dim3(256), sizeof(int) * 2 * e->N, e->stream, seq_arrays(e), e->N, e->ld, e->ppos,
+                     e->kpart, need, honour_mask ? 1 : 0);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
@@ -962,7 +943,7 @@ __global__ void __launch_bounds__(64) k_map_manual(const int* __restrict__ uv, c
   part_d[(size_t)b * kPartDoubles + 2] = 1.0e300;                      // no score threshold on a manual selection
 }
 
-static MapParams map_params(const sl2_engine* e, int enable_mapping, int save_trajectory, int force) {
+static MapParams map_params(const sl2_engine* e, int enable_mapping, int save_trajectory, int force, bool honour_mask) {
   MapParams mp;
   mp.enable_mapping = enable_mapping; mp.save_trajectory = save_trajectory; mp.force = force;
   mp.keep_visible = e->prm.number_of_features_to_keep_visible;
@@ -973,74 +954,64 @@ static MapParams map_params(const sl2_engine* e, int enable_mapping, int save_tr
   mp.sd_ratio = e->prm.standard_deviation_depth_ratio; mp.prune_threshold = e->prm.prune_probability_threshold;
   mp.pcap = e->root->pcap;
   mp.kpart = e->root->kpart;
+  mp.N = e->N; mp.ld = e->ld; mp.ppos = e->ppos; mp.width = e->cam.width; mp.height = e->cam.height;
+  mp.honour_mask = honour_mask ? 1 : 0;
+  mp.frames = e->cur_frames; mp.seq_stride = e->cur_stride; mp.parts_mail = e->root->parts_mail_dev;
   return mp;
 }
 
-static MapArrays map_arrays(const sl2_engine* e, bool honour_mask) {
-  MapArrays a;
-  a.x = e->x; a.P = e->P; a.frames = e->cur_frames; a.seq_stride = e->cur_stride; a.patch = e->patch; a.patch_sums = e->patch_sums;
-  a.xp_org = e->xp_org; a.f_flags = e->f_flags; a.n_slots = e->n_slots; a.attempted = e->attempted; a.successful = e->successful;
-  a.f_label = e->f_label; a.next_label = e->next_label; a.part_i = e->part_i; a.part_d = e->part_d; a.ps_i = e->ps_i; a.ps_d = e->ps_d;
-  a.pos_err = e->pos_err; a.pos_err_any = e->pos_err_any; a.particles = e->particles; a.last_r = e->last_r; a.traj = e->traj;
-  a.traj_count = e->traj_count; a.pos_count = e->pos_count; a.parts_mail = e->root->parts_mail_dev;
-  a.N = e->N; a.ld = e->ld; a.ppos0 = e->ppos;
-  a.active = honour_mask ? e->active : nullptr;
-  a.seq_cam = e->seq_cam; a.width = e->cam.width; a.height = e->cam.height;
-  return a;
-}
-
-static int launch_create(sl2_engine* e, const MapParams& mp, bool honour_mask) {
+static int launch_create(sl2_engine* e, const MapParams& mp) {
   LaunchScope ls(e, "k_map_create");
-  hipLaunchKernelGGL(k_map_create, dim3(e->B), dim3(64), 0, e->stream, map_arrays(e, honour_mask), mp);
+  hipLaunchKernelGGL(k_map_create, dim3(e->B), dim3(64), 0, e->stream, seq_arrays(e), mp);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 
-static int launch_find(sl2_engine* e, const MapParams& mp, bool honour_mask) {
+static int launch_find(sl2_engine* e, const MapParams& mp) {
   LaunchScope ls(e, "k_map_find");
   hipLaunchKernelGGL(k_map_find, dim3(e->B), dim3(kDetThreads), sizeof(double) * 2 * e->N, e->stream, e->x, e->f_flags, e->n_slots, e->n_vis,
                      e->prev_r, e->seq_time, e->part_i, e->part_d, e->rand48, e->last_r, e->status, e->cur_frames, e->cur_stride,
                      e->seq_cam, e->cam.width, e->cam.height, mp, e->N, e->ld,
-                     honour_mask ? e->active : nullptr);
+                     mp.honour_mask ? e->active : nullptr);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 
 // InitialiseFeature(frame) with (uu_, vv_) = uv[b] (device array [B][2]; u < 0 = skip the sequence)
 int launch_manual_init(sl2_engine* e, const int* d_uv) {
-  const MapParams mp = map_params(e, 1, 0, 1);
+  const MapParams mp = map_params(e, 1, 0, 1, false);      // (the caller's explicit act: the mask is not consulted)
   { int rc = launch_compact_slots(e, 1); if (rc != SL2_OK) return rc; }
   hipLaunchKernelGGL(k_map_manual, dim3((e->B + 63) / 64), dim3(64), 0, e->stream, d_uv, e->n_slots, e->part_i, e->part_d, e->status,
                      e->N, e->cam.width, e->cam.height, e->B, e->kpart);
   SL2_HIP(hipGetLastError());
-  return launch_create(e, mp, false);       // (the caller's explicit act: the mask is not consulted)
+  return launch_create(e, mp);
 }
 
 // InitialiseAutoFeature(frame) = AutoInitialiseFeature(frame, 0) (monoslam.cpp:1535-1541, 823-865): region, detector, creation
 int launch_auto_init(sl2_engine* e) {
-  const MapParams mp = map_params(e, 1, 0, 1);
+  const MapParams mp = map_params(e, 1, 0, 1, false);      // (the caller's explicit act: the mask is not consulted)
   { int rc = launch_compact_slots(e, 1); if (rc != SL2_OK) return rc; }
-  { int rc = launch_find(e, mp, false); if (rc != SL2_OK) return rc; }
-  return launch_create(e, mp, false);
+  { int rc = launch_find(e, mp); if (rc != SL2_OK) return rc; }
+  return launch_create(e, mp);
 }
 
 // The feature-initialisation tail of a step: the launches the plan lists (sl2_step_plan.hpp: TailPlan, where the reasons are).
 int launch_mapping(sl2_engine* e, const TailPlan& tp) {
   const int B = e->B;
-  MapParams mp = map_params(e, tp.enable_mapping, tp.save_trajectory, 0);
+  MapParams mp = map_params(e, tp.enable_mapping, tp.save_trajectory, 0, true);
   mp.parts_skipped = tp.finish ? 1 : 0;
   mp.publish_parts = (e->root->B == 1 && e->root->parts_mail_dev) ? 1 : 0;
   const int W = e->cam.width, H = e->cam.height;
   if (!e->root->score_map) { set_error("launch_mapping: score map not allocated"); return SL2_ERR_INVALID; }
   if (tp.squeeze) { int rc = launch_compact_slots(e, 1, true); if (rc != SL2_OK) return rc; }
-  if (tp.find) { int rc = launch_find(e, mp, true); if (rc != SL2_OK) return rc; }
+  if (tp.find) { int rc = launch_find(e, mp); if (rc != SL2_OK) return rc; }
   const size_t shm_particles = sizeof(double) * kParticleDoubles * (size_t)mp.n_particles;
   if (tp.finish) {
     LaunchScope ls(e, "k_map_finish");
-    hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), mp);
+    hipLaunchKernelGGL(k_map_finish, dim3(B), dim3(64), shm_particles, e->stream, seq_arrays(e), mp);
     SL2_HIP(hipGetLastError());
   }
-  if (tp.create) { int rc = launch_create(e, mp, true); if (rc != SL2_OK) return rc; }
+  if (tp.create) { int rc = launch_create(e, mp); if (rc != SL2_OK) return rc; }
   if (!tp.partials) return SL2_OK;
   {
     LaunchScope ls(e, "k_map_particles");
@@ -1072,7 +1043,7 @@ int launch_mapping(sl2_engine* e, const TailPlan& tp) {
   }
   {
     LaunchScope ls(e, "k_map_update");
-    hipLaunchKernelGGL(k_map_update, dim3(B), dim3(64), shm_particles, e->stream, map_arrays(e, true), mp);
+    hipLaunchKernelGGL(k_map_update, dim3(B), dim3(64), shm_particles, e->stream, seq_arrays(e), mp);
     SL2_HIP(hipGetLastError());
   }
   return SL2_OK;

@@ -15,6 +15,8 @@ constexpr int kPartInts = 16, kPartDoubles = 4;   // part_i / part_d, the per-SE
 constexpr int kPsInts = 8, kPsDoubles = 4;        // ps_i / ps_d, one record per PARTIAL SLOT; ps_d: mean, covariance of lambda
 constexpr int kWorkDoubles = 5;      // per-sequence work counters of a step (work[]): window bytes, searches, candidates, exact
                                      // fallbacks, 16 x 16 candidate tiles of the matrix-core search
+constexpr int kSeqTimeDoubles = 4;   // seq_time, the per-sequence time record (the places of its fields: sl2_common.hpp)
+constexpr int kSeqCamDoubles = 8;    // seq_cam, the per-sequence camera calibration: one 64-byte line (fields: sl2_common.hpp)
 constexpr int kPatchStride = 288;    // bytes per stored template: 121 raw bytes (+7 pad), then at byte
                                      // 128 the packed form: 33 dwords (11 rows x 12 bytes, byte 11 = 0),
                                      // sum g0, sum g0^2, flag (patch sigma >= 10), pad
@@ -99,7 +101,11 @@ struct SeqDims {
   X(double, particles, kpart * pcap * kParticleDoubles)   /* [kpart][pcap][kParticleDoubles] */                                    \
   X(unsigned long long, rand48, 1)        /*             drand48 state (srand48(0) at Init, monoslam.cpp:1968) */                    \
   X(double, prev_r, 3)                    /* [3]         camera position before the prediction (speed estimate, :121-124) */         \
-  X(int, me_desc, kpart * pcap * 8)       /* [kpart][pcap][8]  search ellipses of the particles */
+  X(int, me_desc, kpart * pcap * 8)       /* [kpart][pcap][8]  search ellipses of the particles */                                   \
+  /* ---- engine state of a sequence that no sequence blob carries (sl2_common.hpp says who reads and writes each) ---- */         \
+  X(int, step_mark, 1)                    /*             1 = took part in the last make_measurements (sl2_get_step_stats) */ \
+  X(double, seq_time, kSeqTimeDoubles)    /* [kSeqTimeDoubles]  nominal time step, time owed, step last used, catch-up switch (sl2_set_delta_t) */ \
+  X(double, seq_cam, kSeqCamDoubles)      /* [kSeqCamDoubles]   fku, fkv, u0, v0, kd1, sd, two spare words (sl2_set_cameras) */
 
 // The pointers themselves: sl2_engine derives from this, so that e->x, g->f_hcol and the rest are plain members.
 struct SeqArrays {

@@ -13,13 +13,6 @@
 
 namespace sl2 {
 
-struct SnapArrays {
-  const double *x, *P, *xp_org, *f_h, *f_z, *f_nu, *f_R, *f_S, *f_Hx, *f_Hy, *traj, *ps_d, *particles;
-  const int *f_flags, *f_label, *n_slots, *next_label, *attempted, *successful, *sel_idx, *n_sel, *n_vis, *m_count, *traj_count,
-      *status, *part_i, *ps_i, *pos_err, *pos_count, *seq_age;
-  const uint8_t* patch;
-};
-
 constexpr int kSnapMagic = 0x53324c53;
 constexpr int kSnapThreads = 256;
 constexpr int kFeatureInfoBytes = (int)sizeof(sl2_feature_info);
@@ -31,7 +24,7 @@ __device__ __forceinline__ int up8(int v) { return (v + 7) & ~7; }
 
 // One workgroup.  LDS: per slot flags, label, list index (-1: not in feature_list_), state size, first double of its
 // covariance record, patch index (-1: not included); then the selection's labels.
-__global__ void __launch_bounds__(kSnapThreads) k_snapshot(SnapArrays a, int seq, int N, int ld, int ppos, int pcap, int kpart, int traj_cursor,
+__global__ void __launch_bounds__(kSnapThreads) k_snapshot(const SeqArrays a, int seq, int N, int ld, int ppos, int pcap, int kpart, int traj_cursor,
                                                            int patch_from_label, long long steps_done, unsigned char* __restrict__ stage,
                                                            uint4* __restrict__ host_out, unsigned long long* __restrict__ done_word,
                                                            unsigned long long ticket) {
@@ -264,15 +257,8 @@ extern "C" int sl2_snapshot(sl2_engine* e, int seq, int traj_cursor, int patch_f
   }
   // the groups' streams (sl2_set_groups > 1) join the root stream at the end of every stepping call; the kernel below is
   // queued behind them
-  SnapArrays a;
-  a.x = e->x; a.P = e->P; a.xp_org = e->xp_org; a.f_h = e->f_h; a.f_z = e->f_z; a.f_nu = e->f_nu; a.f_R = e->f_R; a.f_S = e->f_S;
-  a.f_Hx = e->f_Hx; a.f_Hy = e->f_Hy; a.traj = e->traj; a.ps_d = e->ps_d; a.particles = e->particles;
-  a.f_flags = e->f_flags; a.f_label = e->f_label; a.n_slots = e->n_slots; a.next_label = e->next_label; a.attempted = e->attempted;
-  a.successful = e->successful; a.sel_idx = e->sel_idx; a.n_sel = e->n_sel; a.n_vis = e->n_vis; a.m_count = e->m_count;
-  a.traj_count = e->traj_count; a.status = e->status; a.part_i = e->part_i; a.ps_i = e->ps_i; a.pos_err = e->pos_err; a.patch = e->patch;
-  a.pos_count = e->pos_count; a.seq_age = e->seq_age;
-  hipLaunchKernelGGL(k_snapshot, dim3(1), dim3(kSnapThreads), sizeof(int) * 8 * e->N, e->stream, a, seq, e->N, e->ld, e->ppos, e->pcap, e->kpart,
-                     traj_cursor, patch_from_label, e->steps_done, (unsigned char*)e->snap_stage, (uint4*)e->snap_host_dev,
+  hipLaunchKernelGGL(k_snapshot, dim3(1), dim3(kSnapThreads), sizeof(int) * 8 * e->N, e->stream, seq_arrays(e), seq, e->N, e->ld, e->ppos, e->pcap,
+                     e->kpart, traj_cursor, patch_from_label, e->steps_done, (unsigned char*)e->snap_stage, (uint4*)e->snap_host_dev,
                      (unsigned long long*)((char*)e->snap_host_dev + e->snap_cap), ++e->snap_ticket);
   SL2_HIP(hipGetLastError());
   {

@@ -20,18 +20,12 @@ namespace sl2 {
 
 static_assert(sizeof(sl2_step_stats) == 96, "sl2_step_stats is 96 bytes");
 
-struct StatArrays {
-  const double *P, *Vt, *LinvT, *f_nu, *f_S;
-  const int *m_gate, *m_count, *step_mark, *status, *pos_count, *seq_age, *n_slots, *f_flags, *f_label, *part_i, *n_vis, *n_sel,
-      *sel_idx, *succ_idx;
-};
-
 constexpr int kStatThreads = 256;      // four sequences per workgroup, a wavefront each
 
 __device__ __forceinline__ double bfly_f64(double v, int dist) { return __shfl_xor(v, dist, 64); }
 
-__global__ void __launch_bounds__(kStatThreads) k_step_stats(StatArrays a, int seq0, int nseq, int N, int ld, int mld, int nblk_max,
-                                                            sl2_step_stats* __restrict__ out) {
+__global__ void __launch_bounds__(kStatThreads) k_step_stats(const SeqArrays a, int seq0, int nseq, int N, int ld, int mld,
+                                                            int nblk_max, sl2_step_stats* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int s = blockIdx.x * (kStatThreads / 64) + (threadIdx.x >> 6);
   if (s >= nseq) return;                               // (a whole wavefront)
@@ -133,16 +127,11 @@ extern "C" int sl2_get_step_stats(sl2_engine* e, int seq0, int nseq, sl2_step_st
   }
   // on the engine's stream: the groups' streams (sl2_set_groups > 1) join it at the end of every stepping call, and a replayed
   // graph is one more node in front of this launch.  The root's arrays: a record does not know which group stepped its sequence.
-  StatArrays a;
-  a.P = e->P; a.Vt = e->Vt; a.LinvT = e->LinvT; a.f_nu = e->f_nu; a.f_S = e->f_S;
-  a.m_gate = e->m_gate; a.m_count = e->m_count; a.step_mark = e->step_mark; a.status = e->status; a.pos_count = e->pos_count;
-  a.seq_age = e->seq_age; a.n_slots = e->n_slots; a.f_flags = e->f_flags; a.f_label = e->f_label; a.part_i = e->part_i;
-  a.n_vis = e->n_vis; a.n_sel = e->n_sel; a.sel_idx = e->sel_idx; a.succ_idx = e->succ_idx;
   sl2_step_stats* dst = out_on_device ? out : (sl2_step_stats*)e->stats_host_dev;
   {
     LaunchScope ls(e, "k_step_stats");
-    hipLaunchKernelGGL(k_step_stats, dim3((nseq + kStatThreads / 64 - 1) / (kStatThreads / 64)), dim3(kStatThreads), 0, e->stream, a, seq0, nseq,
-                       e->N, e->ld, e->mld, e->nblk_max, dst);
+    hipLaunchKernelGGL(k_step_stats, dim3((nseq + kStatThreads / 64 - 1) / (kStatThreads / 64)), dim3(kStatThreads), 0, e->stream, seq_arrays(e),
+                       seq0, nseq, e->N, e->ld, e->mld, e->nblk_max, dst);
     SL2_HIP(hipGetLastError());
   }
   if (out_on_device) return SL2_OK;

@@ -30,6 +30,9 @@ BUDGET = {
     "k_map_me_search": ("sl2_mapping.hip", ["-ffp-contract=off"], 128, 4, 0),
     "k_map_find": ("sl2_mapping.hip", ["-ffp-contract=off"], 128, 4, 0),      # (region + detector: the detector's 1024 threads)
     "k_map_compact_slots": ("sl2_mapping.hip", ["-ffp-contract=off"], 168, 3, 8),
+    # the fused small-map step's second kernel: three workgroups per CU at large batches, so three wavefronts per SIMD must fit
+    # (149 registers and fourteen parked scalars)
+    "k_small_back": ("sl2_small.hip", ["-ffp-contract=off"], 168, 3, 14),
 }
 
 

@@ -14,8 +14,9 @@ SRC = os.path.join(ROOT, "tests", "seq_arrays_host.cpp")
 
 # (N, ld, mld, nblk_max, kpart, pcap): max_features 16, one partial slot, 10 selected; max_features 100, four partial slots
 DIMS = [(16, 128, 32, 1, 1, 128), (100, 384, 256, 8, 4, 128)]
-# the per-sequence arrays struct sl2_engine held by hand before the table (counted in its allocation, view and release lists)
-N_ARRAYS = 57
+# the per-sequence arrays struct sl2_engine held by hand before the table (counted in its allocation, view and release lists):
+# 57 rows, then the step record, the time record and the camera calibration
+N_ARRAYS = 60
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +54,8 @@ def test_rows_are_the_members_and_their_count(sa):
     assert len(set(names)) == len(names)
     assert sa.sa_struct_pointers() == N_ARRAYS                  # SeqArrays holds one pointer per row and nothing else
     assert sa.sa_name(N_ARRAYS) is None and sa.sa_name(-1) is None
-    assert names[:2] == ["x", "P"] and names[-1] == "me_desc"   # the allocation order starts and ends as sl2_create's did
+    assert names[:2] == ["x", "P"]                              # the allocation order starts and ends as sl2_create's did
+    assert names[-4:] == ["me_desc", "step_mark", "seq_time", "seq_cam"]
     order = [names.index(n) for n in ("P", "At", "Vt", "St")]   # the large matrices, in the order their placement compares
     assert order == sorted(order)
 
@@ -91,7 +93,7 @@ def test_extents_restated(sa, dims):
     N, ld, mld, nblk_max, kpart, pcap = dims
     want = {"x": ld, "P": ld * ld, "At": mld * ld, "Vt": mld * ld, "St": mld * mld, "LinvT": nblk_max * 1024, "patch": N * 288,
             "srch_sel": N * 16, "f_Hx": N * 14, "particles": kpart * pcap * 12, "me_desc": kpart * pcap * 8, "ps_i": kpart * 8,
-            "traj": 3000, "pos_log": 3000, "active": 1}
+            "traj": 3000, "pos_log": 3000, "active": 1, "step_mark": 1, "seq_time": 4, "seq_cam": 8}
     rows = {sa.sa_name(i).decode(): i for i in range(sa.sa_count())}
     for name, elems in want.items():
         assert sa.sa_elems(rows[name], *dims) == elems, name

@@ -67,10 +67,10 @@ def test_the_record_is_one_cache_line_and_the_camera_struct_is_unchanged():
     assert L.sc_record_bytes() == 64
     assert L.sc_camera_bytes() == 56 == C.sizeof(_lib.sl2_camera)          # sizeof(sl2_camera) as before this feature
     assert L.sc_blob_header_bytes() == 256
-    common = open(os.path.join(CSRC, "sl2_common.hpp")).read()
-    m = re.search(r"constexpr int kSeqCamDoubles = (\d+)", common)
+    table = open(os.path.join(CSRC, "sl2_seq_arrays.hpp")).read()      # the extents of the table's rows are declared with it
+    m = re.search(r"constexpr int kSeqCamDoubles = (\d+)", table)
     assert m and int(m.group(1)) * 8 == 64
-    assert common.find("kSeqCamDoubles") > common.find("kSeqTimeDoubles") > 0       # declared beside the time record's
+    assert table.find("kSeqCamDoubles") > table.find("kSeqTimeDoubles") > 0         # declared beside the time record's
 
 
 def test_the_chunk_of_the_host_form_fits_the_kernel_argument_segment():
@@ -131,19 +131,21 @@ def test_no_step_kernel_keeps_a_camera_launch_argument():
         assert re.search(r"\b%s\(const CameraParams& cam," % fn, math), fn
 
 
-def test_the_record_is_engine_state_outside_the_table_and_only_the_setter_writes_it():
-    assert "seq_cam" not in open(os.path.join(CSRC, "sl2_seq_arrays.hpp")).read()
+def test_the_record_is_a_row_of_the_table_and_only_the_setter_writes_it():
+    """Allocation, a group's view (+ kSeqCamDoubles * first) and release are the table's (tests/test_seq_arrays_host.py checks
+    their extents and offsets for every row); nothing in the engine does them by hand."""
+    assert "X(double, seq_cam, kSeqCamDoubles)" in open(os.path.join(CSRC, "sl2_seq_arrays.hpp")).read()
     eng = open(os.path.join(CSRC, "sl2_engine.hip")).read()
-    assert "g->seq_cam = e->seq_cam + kSeqCamDoubles * first;" in eng
-    assert "dmalloc(&e->seq_cam" in eng and "hipFree(e->seq_cam)" in eng
+    assert "g->seq_cam" not in eng and "dmalloc(&e->seq_cam" not in eng and "hipFree(e->seq_cam)" not in eng
+    assert "hipMemcpy(e->seq_cam, rec.data()" in eng          # sl2_create fills it with the engine's calibration
     setter = eng[eng.find("int sl2_set_cameras("):eng.find("int sl2_get_cameras(")]
     getter = eng[eng.find("int sl2_get_cameras("):eng.find("// ---", eng.find("int sl2_get_cameras("))]
     for body in (setter, getter):
         assert "drop_step_graphs" not in body and "sync_all" not in body and "Synchronize" not in body and "hipMemcpy" not in body
     ck = open(os.path.join(CSRC, "sl2_checkpoint.hip")).read()
-    assert "const double* seq_cam;" in ck                     # the pack kernel reads it, nothing there can write it
-    unpack = ck[ck.find("void __launch_bounds__(kCkptThreads) k_seq_unpack"):ck.find("// ----", ck.find("k_seq_unpack(CkptArrays A"))]
-    assert "seq_cam" not in unpack
+    assert ck.count("seq_cam") == 2 and "const double* rec = S.seq_cam +" in ck      # the pack kernel reads it (and a comment names it) ...
+    unpack = ck[ck.find("void __launch_bounds__(kCkptThreads) k_seq_unpack"):ck.find("static CkptParams ckpt_params(")]      # (the whole kernel)
+    assert "k_seq_unpack(const SeqArrays S" in unpack and "S.n_slots[b] = ns" in unpack and "seq_cam" not in unpack      # ... the unpack kernel does not touch it
     assert "cams_host[dst_seq]" in ck and '"camera"' in ck
 
 

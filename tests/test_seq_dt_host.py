@@ -83,13 +83,15 @@ def test_no_kernel_keeps_a_dt_launch_argument():
     assert re.search(r"predict_body\([^)]*double\* __restrict__ seq_time\)", dev, flags=re.S)
 
 
-def test_the_record_is_engine_state_outside_the_table_and_the_blob():
+def test_the_record_is_a_row_of_the_table_outside_the_blob():
+    """Allocation, a group's view (+ kSeqTimeDoubles * first) and release are the table's (tests/test_seq_arrays_host.py checks
+    their extents and offsets for every row); nothing in the engine does them by hand, and no blob carries the record."""
     arrays = open(os.path.join(CSRC, "sl2_seq_arrays.hpp")).read()
-    assert "seq_time" not in arrays
+    assert "X(double, seq_time, kSeqTimeDoubles)" in arrays
     assert "seq_time" not in open(os.path.join(CSRC, "sl2_checkpoint.hip")).read()
     eng = open(os.path.join(CSRC, "sl2_engine.hip")).read()
-    assert "g->seq_time = e->seq_time + kSeqTimeDoubles * first;" in eng
-    assert "dmalloc(&e->seq_time" in eng and "hipFree(e->seq_time)" in eng
+    assert "g->seq_time" not in eng and "dmalloc(&e->seq_time" not in eng and "hipFree(e->seq_time)" not in eng
+    assert "hipMemcpy(e->seq_time, rec.data()" in eng         # sl2_create fills it with params.delta_t
     setter = eng[eng.find("int sl2_set_delta_t("):eng.find("int sl2_get_delta_t(")]
     catch_up = eng[eng.find("int sl2_set_pause_catch_up("):eng.find("// ---", eng.find("int sl2_set_pause_catch_up("))]
     for body in (setter, catch_up):
