@@ -41,7 +41,9 @@ extern "C" {
  * sl2_snapshot_header.sequence_steps (taken from reserved[]); sl2_set_active_sequences, sl2_get_active_sequences,
  * sl2_ingest_frame_counts, sl2_ingest_next_ragged; sl2_get_step_stats (sl2_step_stats); sl2_set_delta_t, sl2_get_delta_t,
  * sl2_set_pause_catch_up (the time step is the sequence's: sl2_params.delta_t is its initial value); sl2_set_cameras,
- * sl2_get_cameras (the calibration is the sequence's: the sl2_create camera is its initial value and the batch's image size). */
+ * sl2_get_cameras (the calibration is the sequence's: the sl2_create camera is its initial value and the batch's image size);
+ * sl2_converter_create, sl2_converter_destroy, sl2_converter_set_sources, sl2_converter_get_sources, sl2_convert_frames,
+ * sl2_convert_frame_host, sl2_scale_camera (raw camera frames of any size and pixel format, in front of the step). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -425,6 +427,62 @@ int sl2_ingest_set_zero_copy(sl2_ingest* g, size_t max_batch_bytes);
 int sl2_ingest_frame_counts(const sl2_ingest* g, int32_t* counts, int capacity);
 int sl2_ingest_next_ragged(sl2_ingest* g, void* stream, const uint8_t** d_frames, size_t* seq_stride, uint8_t* have);
 void sl2_ingest_close(sl2_ingest* g);
+
+/* ------------------------------------------------------------- raw camera frames (live cameras) */
+
+/* UsbCamGrabber::operator() (framegrabber/usbcamgrabber.cpp:75-113) for a batch: whatever the cameras deliver - RGB24 / BGR24 or
+ * packed 4:2:2, any resolution, any row pitch - is reduced to 8-bit grey (cv::cvtColor) and brought to the engine's image size
+ * (cv::resize, INTER_LINEAR), for every sequence in ONE launch on the device, in front of sl2_go_one_step.  The step itself keeps
+ * the one image size of sl2_create; the sequences' SOURCES may all differ.
+ * The arithmetic is OpenCV's 8-bit integer form of the reference's era, defined here (scenelib2_amd/csrc/sl2_convert_dev.hpp):
+ *   grey   GRAY8 the byte; RGB24 / BGR24 (4899 R + 9617 G + 1868 B + 8192) >> 14; UYVY (U Y0 V Y1: the reference's
+ *          CV_YUV2GRAY_Y422) row[2 x + 1]; YUYV (Y0 U Y1 V) row[2 x].  (The colour PNG path of sl2_read_image keeps libpng's
+ *          constants: that is imread(.., 0), another call of the reference.)
+ *   taps   along an axis of S source and D output pixels, for output d: scale = (double)S / D; f = (float)((d + 0.5) * scale - 0.5);
+ *          i = floorf(f); f -= i (float); i < 0: i = 0, f = 0; i >= S - 1: i = S - 1, f = 0; i1 = min(i + 1, S - 1);
+ *          w1 = rintf(f * 2048); w0 = rintf((1 - f) * 2048) (round half to even).
+ *   pixel  with the column taps (x0, x1, a0, a1) and the row taps (y0, y1, b0, b1), in 32-bit integers: H(y) = g[y][x0] a0 + g[y][x1] a1;
+ *          out = (((b0 (H(y0) >> 4)) >> 16) + ((b1 (H(y1) >> 4)) >> 16) + 2) >> 2.
+ * It is the identity where source and output size agree and maps a constant image to itself.  The taps are evaluated on the host
+ * and uploaded as tables: the kernel and sl2_convert_frame_host do integer work on the same tables and agree byte for byte. */
+enum { SL2_PIX_GRAY8 = 0, SL2_PIX_RGB24 = 1, SL2_PIX_BGR24 = 2, SL2_PIX_UYVY = 3, SL2_PIX_YUYV = 4 };
+typedef struct sl2_frame_source {        /* 24 bytes */
+  int32_t width, height;                 /* source pixels: 1 .. 4096 by 1 .. 16384; even width for the 4:2:2 formats */
+  int32_t pitch;                         /* bytes from one source row to the next, >= the row's own bytes */
+  int32_t format;                        /* SL2_PIX_* */
+  uint64_t offset;                       /* of this sequence's first byte inside the raw buffer */
+} sl2_frame_source;
+typedef struct sl2_converter sl2_converter;
+/* A converter for nseq sequences to out_width x out_height (1 .. 4096 each; the engine's image size).  It needs no engine. */
+int sl2_converter_create(int device, int nseq, int out_width, int out_height, sl2_converter** out);
+void sl2_converter_destroy(sl2_converter* c);
+/* The sources of sequences seq0 .. seq0 + nseq - 1.  A setup call: it may wait (for the last conversion queued, which keeps the
+ * tables it was queued with) and takes effect for the sl2_convert_frames calls after it.  Two sequences may name the same bytes
+ * (one camera feeding two filters).  Refused (SL2_ERR_INVALID, nothing changed, the text names the sequence): width or height
+ * below 1 or over the cap, pitch below the bytes of a row, an odd width with a 4:2:2 format, an unknown format.
+ * sl2_converter_get_sources returns what was set (SL2_ERR_INVALID for a sequence never set). */
+int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, const sl2_frame_source* src);
+int sl2_converter_get_sources(const sl2_converter* c, int seq0, int nseq, sl2_frame_source* src);
+/* Converts every sequence: d_frames[s * seq_stride + y * out_width + x], a device buffer of the caller's (sl2_dev_malloc); the
+ * bytes between out_width * out_height and seq_stride are left untouched.  Asynchronous on `stream` (a hipStream_t; the stream
+ * the engine steps on): sl2_go_one_step(.., frames_on_device = 1) queued after it on that stream needs no other ordering.
+ * raw_on_device = 0: raw is host memory; its raw_bytes are first copied, on `stream`, to a staging buffer of the converter's
+ * own, which grows on demand (never in the steady state).  The host buffer may be reused once `stream` has passed the copy
+ * (after sl2_synchronize, say); pageable memory has been read when the call returns, pinned memory has not.
+ * Refused on the host, before anything is queued (SL2_ERR_INVALID, the text names the sequence): a sequence whose source was
+ * never set, a source that reaches past the buffer (offset + (height - 1) * pitch + the bytes of a row > raw_bytes),
+ * seq_stride < out_width * out_height. */
+int sl2_convert_frames(sl2_converter* c, void* stream, const void* raw, size_t raw_bytes, int raw_on_device,
+                       uint8_t* d_frames, size_t seq_stride);
+/* The same arithmetic for one sequence on the host (no GPU needed): out[out_height][out_width].  Same refusals. */
+int sl2_convert_frame_host(const sl2_frame_source* src, const void* raw, size_t raw_bytes, int out_width, int out_height,
+                           uint8_t* out);
+/* The calibration of the resized image from that of the source image (in->width, in->height = the source size): with
+ * s = in->width / out_width, fku' = fku / s, fkv' = fkv / s, u0' = (u0 + 0.5) / s - 0.5, v0' likewise, kd1' = kd1 s s; sd is
+ * unchanged (the measurement noise in output pixels is the caller's choice).  The radial term lives in centred pixels and
+ * survives a uniform scale only: in->width * out_height != in->height * out_width is refused (SL2_ERR_INVALID) - the
+ * conversion itself accepts any aspect ratio.  Host only. */
+int sl2_scale_camera(const sl2_camera* in, int out_width, int out_height, sl2_camera* out);
 
 /* ----------------------------------------------------------------- state access */
 

@@ -90,7 +90,11 @@ struct FeatureInitInfo {       // feature_init_info.h:77-118
 class MonoSLAM {
  public:
   explicit MonoSLAM(int max_features = 128, int device = 0) : max_features_(max_features), device_(device) {}
-  ~MonoSLAM() { if (eng_) sl2_destroy(eng_); }
+  ~MonoSLAM() {
+    if (converter_) sl2_converter_destroy(converter_);
+    if (frame_dev_) sl2_dev_free(device_, frame_dev_);
+    if (eng_) sl2_destroy(eng_);
+  }
   MonoSLAM(const MonoSLAM&) = delete;
   MonoSLAM& operator=(const MonoSLAM&) = delete;
 
@@ -135,6 +139,8 @@ class MonoSLAM {
     prm.minimum_attempted_measurements_of_feature = minimum_attempted_measurements_of_feature_;
     prm.successful_match_fraction = successful_match_fraction_;
     if (sl2_device_count() < 1) throw std::runtime_error("MonoSLAM::Init: no HIP device (the engine has no CPU path)");
+    if (converter_) { sl2_converter_destroy(converter_); converter_ = nullptr; }      // (sized by the camera of the last Init)
+    if (frame_dev_) { sl2_dev_free(device_, frame_dev_); frame_dev_ = nullptr; }
     if (eng_) { sl2_destroy(eng_); eng_ = nullptr; }
     traj_seen_ = 0; patch_seen_ = 0; patch_cache_.clear(); feature_list_.clear(); trajectory_store_.clear();
     check(sl2_create(&cam, &prm, 1, max_features_, device_, nullptr, &eng_), "sl2_create");
@@ -208,6 +214,34 @@ class MonoSLAM {
                                  "initialise no features until one is deleted; construct MonoSLAM with a larger max_features");
     }
     return true;
+  }
+
+  // What the camera delivers (UsbCamGrabber::operator(), usbcamgrabber.cpp:75-113): its size, the bytes from one row to the next and
+  // the pixel format (SL2_PIX_*).  GoOneStepRaw then takes such frames.  The converter and the device frame are created on the
+  // first call; a later call names another source (a camera that changed its mode).
+  void SetFrameSource(int width, int height, int pitch, int format) {
+    if (!eng_) throw std::runtime_error("MonoSLAM::SetFrameSource: call Init first");
+    if (!converter_) {
+      check(sl2_converter_create(device_, 1, camera_->width_, camera_->height_, &converter_), "sl2_converter_create");
+      void* p = nullptr;
+      check(sl2_dev_malloc(device_, (size_t)camera_->width_ * camera_->height_, &p), "sl2_dev_malloc");
+      frame_dev_ = (uint8_t*)p;
+    }
+    sl2_frame_source src;
+    src.width = width; src.height = height; src.pitch = pitch; src.format = format; src.offset = 0;
+    check(sl2_converter_set_sources(converter_, 0, 1, &src), "sl2_converter_set_sources");
+  }
+
+  // The reference's camera loop in one call: cvtColor + resize (sl2_convert_frames, on the engine's stream), then GoOneStep on the
+  // converted device frame.  raw: `bytes` bytes as SetFrameSource described them; host memory is read before the call returns.
+  bool GoOneStepRaw(const void* raw, size_t bytes, bool on_device, bool save_trajectory, bool enable_mapping) {
+    if (!eng_ || !converter_) throw std::runtime_error("MonoSLAM::GoOneStepRaw: call SetFrameSource first");
+    check(sl2_convert_frames(converter_, sl2_get_stream(eng_), raw, bytes, on_device ? 1 : 0, frame_dev_,
+                             (size_t)camera_->width_ * camera_->height_),
+          "sl2_convert_frames");
+    Frame frame;
+    frame.data = frame_dev_; frame.cols = camera_->width_; frame.rows = camera_->height_; frame.on_device = true;
+    return GoOneStep(frame, save_trajectory, enable_mapping);      // (its read-back waits for the stream: the copy of `raw` is done)
   }
 
   // The seams of GoOneStep, callable one by one like the reference's public members (monoslam.cpp:118-177; kalman.h:51-52
@@ -534,6 +568,8 @@ class MonoSLAM {
   int max_features_, device_;
   bool map_full_ = false;
   sl2_engine* eng_ = nullptr;
+  sl2_converter* converter_ = nullptr;   // SetFrameSource: raw camera frames in front of GoOneStep
+  uint8_t* frame_dev_ = nullptr;         // the converted frame, camera_->width_ x camera_->height_, device memory
 };
 
 // Kalman (kalman.h:51-52): the reference's filter object works on the MonoSLAM it is handed; so does this one.

@@ -93,6 +93,13 @@ class sl2_step_stats(C.Structure):
         [("reserved", C.c_int32 * 2)]
 
 
+class sl2_frame_source(C.Structure):
+    """Where one sequence's raw camera frame lies in the raw buffer, and what it is (FrameConverter.set_sources)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("format", C.c_int32), ("offset", C.c_uint64)]
+
+
+SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_BGR24, SL2_PIX_UYVY, SL2_PIX_YUYV = range(5)
+
 # the same 96 bytes as a NumPy structured dtype (what Engine.step_stats returns)
 STEP_STATS_DTYPE = np.dtype([(n, np.int32) for n in ("stepped", "status_flags", "sequence_steps", "n_features", "n_partial",
                                                      "n_visible", "n_selected", "n_matched", "dof", "worst_label")] +
@@ -105,6 +112,7 @@ SL2_BLOB_LAYOUT_OFFSETS = 7 + SL2_BLOB_SLOT_ARRAYS
 
 assert C.sizeof(sl2_snapshot_header) == 256 and C.sizeof(sl2_partial_info) == 32 and C.sizeof(sl2_sequence_blob_header) == 256
 assert C.sizeof(sl2_step_stats) == 96 and STEP_STATS_DTYPE.itemsize == 96
+assert C.sizeof(sl2_frame_source) == 24
 
 # every symbol include/scenelib2_amd.h declares (tests check the .so exports all of them)
 EXPORTED_SYMBOLS = [
@@ -125,6 +133,8 @@ EXPORTED_SYMBOLS = [
     "sl2_get_step_stats",
     "sl2_set_delta_t", "sl2_get_delta_t", "sl2_set_pause_catch_up",
     "sl2_set_cameras", "sl2_get_cameras",
+    "sl2_converter_create", "sl2_converter_destroy", "sl2_converter_set_sources", "sl2_converter_get_sources",
+    "sl2_convert_frames", "sl2_convert_frame_host", "sl2_scale_camera",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -249,6 +259,15 @@ def _bind(L):
     if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_set_cameras"):      # (an older build under test, scripts/ab_libs.sh)
         L.sl2_set_cameras.argtypes = [vp, C.c_int, C.c_int, vp]
         L.sl2_get_cameras.argtypes = [vp, C.c_int, C.c_int, vp]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_convert_frames"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_converter_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sl2_converter_destroy.argtypes = [vp]
+        L.sl2_converter_destroy.restype = None
+        L.sl2_converter_set_sources.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sl2_frame_source)]
+        L.sl2_converter_get_sources.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sl2_frame_source)]
+        L.sl2_convert_frames.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t]
+        L.sl2_convert_frame_host.argtypes = [C.POINTER(sl2_frame_source), vp, C.c_size_t, C.c_int, C.c_int, c_u8p]
+        L.sl2_scale_camera.argtypes = [C.POINTER(sl2_camera), C.c_int, C.c_int, C.POINTER(sl2_camera)]
     return L
 
 

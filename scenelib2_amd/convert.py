@@ -1,0 +1,110 @@
+"""Raw camera frames -> the engine's grey images (include/scenelib2_amd.h, "raw camera frames").
+
+The reference's UsbCamGrabber reduces whatever the camera delivers to 8-bit grey and resizes it to the filter's image size
+before GoOneStep sees it.  FrameConverter does that for a whole batch in one launch on the device: every sequence has its own
+source size, row pitch and pixel format.  convert_frame_host is the same arithmetic for one sequence on the host, and
+scale_camera the calibration that goes with the resized image.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import SL2_PIX_BGR24, SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_UYVY, SL2_PIX_YUYV  # noqa: F401
+
+FORMATS = {"gray8": SL2_PIX_GRAY8, "rgb24": SL2_PIX_RGB24, "bgr24": SL2_PIX_BGR24, "uyvy": SL2_PIX_UYVY, "yuyv": SL2_PIX_YUYV}
+BYTES_PER_PIXEL = {SL2_PIX_GRAY8: 1, SL2_PIX_RGB24: 3, SL2_PIX_BGR24: 3, SL2_PIX_UYVY: 2, SL2_PIX_YUYV: 2}
+
+
+def _format(f):
+    return FORMATS[f.lower()] if isinstance(f, str) else int(f)
+
+
+def make_source(src):
+    """dict(width, height, format[, pitch, offset]) -> sl2_frame_source; pitch defaults to the bytes of a row, offset to 0."""
+    if isinstance(src, _lib.sl2_frame_source):
+        return src
+    fmt = _format(src["format"])
+    pitch = src.get("pitch")
+    if pitch is None:
+        pitch = int(src["width"]) * BYTES_PER_PIXEL.get(fmt, 1)
+    return _lib.sl2_frame_source(int(src["width"]), int(src["height"]), int(pitch), fmt, int(src.get("offset", 0)))
+
+
+def source_bytes(src):
+    """Bytes of the raw buffer a source reaches: offset + (height - 1) * pitch + the bytes of a row."""
+    s = make_source(src)
+    return s.offset + (s.height - 1) * s.pitch + s.width * BYTES_PER_PIXEL[s.format]
+
+
+class FrameConverter:
+    """nseq sequences' raw frames -> [nseq][out_height][out_width] grey on the device, one launch per call."""
+
+    def __init__(self, device, nseq, out_width, out_height, lib=None):
+        self.L = lib or _lib.load()
+        self.device, self.nseq = int(device), int(nseq)
+        self.out_width, self.out_height = int(out_width), int(out_height)
+        self.frame_bytes = self.out_width * self.out_height
+        h = _lib.vp()
+        _lib.check(self.L.sl2_converter_create(self.device, self.nseq, self.out_width, self.out_height, C.byref(h)), self.L)
+        self.h = h
+
+    def set_sources(self, sources, seq0=0):
+        """sources: a list of dicts (make_source) or sl2_frame_source, for sequences seq0 ...  A setup call: it may wait."""
+        arr = (_lib.sl2_frame_source * len(sources))(*[make_source(s) for s in sources])
+        _lib.check(self.L.sl2_converter_set_sources(self.h, int(seq0), len(sources), arr), self.L)
+
+    def get_sources(self, seq0=0, nseq=None):
+        nseq = self.nseq - seq0 if nseq is None else int(nseq)
+        arr = (_lib.sl2_frame_source * nseq)()
+        _lib.check(self.L.sl2_converter_get_sources(self.h, int(seq0), nseq, arr), self.L)
+        return [dict(width=s.width, height=s.height, pitch=s.pitch, format=s.format, offset=s.offset) for s in arr]
+
+    def convert(self, raw, d_frames, seq_stride=0, stream=None, raw_bytes=None):
+        """raw: a uint8 array in host memory (copied to the converter's staging buffer on `stream`; keep it alive and
+        unchanged until the stream has passed the copy), or a (device pointer, bytes) pair.  d_frames: a device pointer
+        (or a DeviceBuffer) of nseq * seq_stride bytes; seq_stride defaults to out_width * out_height.  Asynchronous."""
+        stride = int(seq_stride) if seq_stride else self.frame_bytes
+        dst = d_frames.ptr if isinstance(d_frames, _lib.DeviceBuffer) else int(d_frames)
+        st = _lib.vp(stream) if stream else None
+        if isinstance(raw, tuple):
+            ptr, n = raw
+            _lib.check(self.L.sl2_convert_frames(self.h, st, _lib.vp(int(ptr)), int(n), 1, _lib.vp(dst), stride), self.L)
+            return None
+        a = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+        n = a.size if raw_bytes is None else int(raw_bytes)
+        assert n <= a.size
+        _lib.check(self.L.sl2_convert_frames(self.h, st, a.ctypes.data_as(_lib.vp), n, 0, _lib.vp(dst), stride), self.L)
+        return a
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sl2_converter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def convert_frame_host(src, raw, out_width, out_height, raw_bytes=None):
+    """One sequence on the host (no GPU needed): uint8 [out_height][out_width]."""
+    L = _lib.load()
+    a = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+    n = a.size if raw_bytes is None else int(raw_bytes)
+    out = np.zeros((int(out_height), int(out_width)), np.uint8)
+    s = make_source(src)
+    _lib.check(L.sl2_convert_frame_host(C.byref(s), a.ctypes.data_as(_lib.vp), n, int(out_width), int(out_height), _lib.u8p(out)), L)
+    return out
+
+
+def scale_camera(cam, out_width, out_height):
+    """The calibration of the image resized to out_width x out_height, from the source image's (cam: a dict as for Engine;
+    its width / height are the source size).  A resize that changes the aspect ratio is refused."""
+    L = _lib.load()
+    src = _lib.make_camera(cam)
+    out = _lib.sl2_camera()
+    _lib.check(L.sl2_scale_camera(C.byref(src), int(out_width), int(out_height), C.byref(out)), L)
+    return dict(width=out.width, height=out.height, fku=out.fku, fkv=out.fkv, u0=out.u0, v0=out.v0, kd1=out.kd1, sd=out.sd)

@@ -1,0 +1,369 @@
+// Raw camera frames of a whole batch -> the engine's grey images, in one launch (the arithmetic:
+// sl2_convert_dev.hpp).  In front of the step, like the reference's UsbCamGrabber in front of GoOneStep - not part of it.
+//
+// k_convert_frames: a workgroup of 256 threads owns one sequence and a band of kConvBandRows output rows.  It lists the source
+// rows the band's row taps name (each once; rows no tap names are never read), streams them in with 16-byte loads - a scalar
+// head and tail where the row's address or length breaks the alignment -, reduces them to grey in LDS, forms the outputs from
+// LDS and stores four output bytes per lane.  Sequences of any source size and format share the launch: the grid is sized by
+// the OUTPUT rows, which are the same for all of them.
+#include "sl2_common.hpp"
+#include "sl2_convert_dev.hpp"
+
+namespace sl2 {
+
+constexpr int kConvThreads = 256;
+constexpr int kConvBandRows = 8;                              // output rows per workgroup
+constexpr int kConvSlots = 2 * kConvBandRows;                 // source rows staged at once, at most
+// LDS of the staged grey rows: four rows at the width cap (a staged row is shifted by up to 15 bytes so that its 16-byte
+// stores are aligned: kConvertMaxWidth + 16 each), all sixteen of a band up to 1000 pixels.  16.1 KB: the registers, not the
+// LDS, bound the workgroups a CU takes (eight: the launch bound holds the kernel to 64 registers; at 32 KB and four
+// workgroups it was 1.2 to 1.45 times slower, a workgroup's life being a chain of dependent round trips to memory that only
+// other workgroups hide).
+constexpr int kConvLdsBytes = 4 * (kConvertMaxWidth + 16);
+
+struct ConvArgs {
+  const sl2_frame_source* src;   // [nseq]
+  const uint32_t* taps;          // [nseq][tap_stride]: col_taps column taps (out_w rounded up to 4, the rest 0), then out_h row taps
+  const uint8_t* raw;
+  uint8_t* out;
+  unsigned long long seq_stride;
+  int out_w, out_h, col_taps, tap_stride, bands;
+};
+
+template <int FMT> struct ConvFmt;
+template <> struct ConvFmt<SL2_PIX_GRAY8> { static constexpr int kGroup = 16, kBytes = 16; };
+template <> struct ConvFmt<SL2_PIX_RGB24> { static constexpr int kGroup = 16, kBytes = 48; };
+template <> struct ConvFmt<SL2_PIX_BGR24> { static constexpr int kGroup = 16, kBytes = 48; };
+template <> struct ConvFmt<SL2_PIX_UYVY> { static constexpr int kGroup = 8, kBytes = 16; };
+template <> struct ConvFmt<SL2_PIX_YUYV> { static constexpr int kGroup = 8, kBytes = 16; };
+
+struct ConvShared {
+  alignas(16) uint8_t grey[kConvLdsBytes];
+  int row[kConvSlots];      // the source row a slot holds
+  int head[kConvSlots];     // pixels before the first aligned group (scalar)
+  int first[kConvSlots];    // byte offset of the first aligned group in the row
+  int groups[kConvSlots];   // aligned groups (one lane each)
+  int shift[kConvSlots];    // where the row's pixel 0 sits in its slot: head + shift is a multiple of the group
+  int slot0[kConvBandRows], slot1[kConvBandRows];
+  uint32_t rtap[kConvBandRows];   // the band's row taps
+  int nslots;
+};
+
+__device__ __forceinline__ uint32_t conv_byte(const uint32_t* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
+
+// Stage the listed source rows as grey bytes: slot k of sh.grey holds row sh.row[k] from byte sh.shift[k] on.
+template <int FMT>
+__device__ __forceinline__ void conv_stage(ConvShared& sh, const uint8_t* __restrict__ base, int pitch, int W, int wpad) {
+  constexpr int G = ConvFmt<FMT>::kGroup, VB = ConvFmt<FMT>::kBytes;
+  const int tid = threadIdx.x;
+  const int nslots = sh.nslots;
+  const int row_bytes = W * convert_bpp(FMT);
+  if (tid < nslots) {
+    const unsigned a = (unsigned)(uintptr_t)(base + (size_t)sh.row[tid] * (size_t)pitch);
+    int head, first, groups;
+    if (FMT == SL2_PIX_GRAY8) {
+      head = (int)((0u - a) & 15u); first = head;
+    } else if (FMT == SL2_PIX_RGB24 || FMT == SL2_PIX_BGR24) {
+      head = (int)(((0u - a) * 11u) & 15u); first = 3 * head;      // a + 3 head = 0 mod 16 (3 * 11 = 1 mod 16)
+    } else {
+      first = (int)((0u - a) & 15u);
+      head = (first - (FMT == SL2_PIX_UYVY ? 1 : 0) + 1) >> 1;     // pixels whose Y byte lies before `first`
+    }
+    if (head >= W) { head = W; groups = 0; }
+    else if (convert_is_422(FMT)) groups = row_bytes > first ? (row_bytes - first) / 16 : 0;
+    else groups = (W - head) / G;
+    sh.head[tid] = head; sh.first[tid] = first; sh.groups[tid] = groups; sh.shift[tid] = (G - head % G) % G;
+  }
+  __syncthreads();
+  // the aligned middle: one group per lane
+  const int gmax = row_bytes / VB + 1;      // groups of a row, at most
+  for (int idx = tid; idx < nslots * gmax; idx += kConvThreads) {
+    const int k = idx / gmax, c = idx - k * gmax;
+    if (c >= sh.groups[k]) continue;
+    const uint8_t* rp = base + (size_t)sh.row[k] * (size_t)pitch + sh.first[k] + c * VB;
+    uint8_t* dst = sh.grey + k * wpad + sh.shift[k] + sh.head[k] + c * G;
+    if (FMT == SL2_PIX_GRAY8) {
+      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(rp);
+    } else if (FMT == SL2_PIX_UYVY || FMT == SL2_PIX_YUYV) {
+      const uint4 v = *reinterpret_cast<const uint4*>(rp);
+      // Y sits at the odd bytes of the ROW for UYVY, at the even ones for YUYV: in the chunk, at byte (ypos ^ first) & 1 of every pair
+      const int s8 = 8 * (((FMT == SL2_PIX_UYVY ? 1 : 0) ^ sh.first[k]) & 1);
+      const uint32_t t0 = v.x >> s8, t1 = v.y >> s8, t2 = v.z >> s8, t3 = v.w >> s8;
+      uint2 o;
+      o.x = (t0 & 255u) | ((t0 >> 8) & 0xff00u) | ((t1 & 255u) << 16) | ((t1 << 8) & 0xff000000u);
+      o.y = (t2 & 255u) | ((t2 >> 8) & 0xff00u) | ((t3 & 255u) << 16) | ((t3 << 8) & 0xff000000u);
+      *reinterpret_cast<uint2*>(dst) = o;
+    } else {
+      uint32_t w[12];
+      const uint4 v0 = reinterpret_cast<const uint4*>(rp)[0], v1 = reinterpret_cast<const uint4*>(rp)[1], v2 = reinterpret_cast<const uint4*>(rp)[2];
+      w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w; w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
+      w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
+      uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int c0 = (int)conv_byte(w, 3 * i), c1 = (int)conv_byte(w, 3 * i + 1), c2 = (int)conv_byte(w, 3 * i + 2);
+        const int g = FMT == SL2_PIX_RGB24 ? convert_rgb_grey(c0, c1, c2) : convert_rgb_grey(c2, c1, c0);
+        o[i >> 2] |= (uint32_t)g << (8 * (i & 3));
+      }
+      *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+  }
+  // head and tail, a pixel per lane: at most 15 pixels each
+  for (int idx = tid; idx < nslots * 32; idx += kConvThreads) {
+    const int k = idx >> 5, j = idx & 31;
+    const int p = j < 16 ? j : sh.head[k] + sh.groups[k] * G + (j - 16);
+    if (j < 16 ? p >= sh.head[k] : p >= W) continue;
+    const uint8_t* rp = base + (size_t)sh.row[k] * (size_t)pitch;
+    sh.grey[k * wpad + sh.shift[k] + p] = (uint8_t)convert_grey(FMT, rp, p);
+  }
+}
+
+__global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvArgs A) {
+  __shared__ ConvShared sh;
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x / A.bands, band = blockIdx.x - s * A.bands;
+  const uint32_t* __restrict__ ctab = A.taps + (size_t)s * A.tap_stride;
+  const uint32_t* __restrict__ rtab = ctab + A.col_taps;
+  const int band0 = band * kConvBandRows;
+  const int band_end = band0 + kConvBandRows < A.out_h ? band0 + kConvBandRows : A.out_h;
+  const int nq = (A.out_w + 3) >> 2;                                           // four output pixels per lane
+  const int qs = nq < kConvThreads ? nq : kConvThreads;
+  const int rl = kConvThreads / qs;                                            // output rows formed side by side
+  const int tq = tid % qs, tr = tid / qs;
+  // everything that does not depend on the source goes out in ONE round trip to memory, beside the source's record: the band's
+  // row taps (to LDS) and this lane's first column taps
+  if (tid < band_end - band0) sh.rtap[tid] = rtab[band0 + tid];
+  uint4 ct_first = make_uint4(0, 0, 0, 0);
+  if (tr < rl) ct_first = *reinterpret_cast<const uint4*>(ctab + 4 * tq);
+  const sl2_frame_source src = A.src[s];
+  const int W = src.width, H = src.height, pitch = src.pitch, fmt = src.format;
+  const uint8_t* __restrict__ base = A.raw + src.offset;
+  uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
+  const int wpad = (W + 15 + 15) & ~15;
+  const int cap = kConvLdsBytes / wpad;                                        // rows the LDS holds: at least 4
+  const int rmax = cap / 2 < kConvBandRows ? cap / 2 : kConvBandRows;          // output rows per pass: at least 2
+  __syncthreads();
+
+  for (int d0 = band0; d0 < band_end; d0 += rmax) {
+    const int rr = band_end - d0 < rmax ? band_end - d0 : rmax;
+    // the source rows this pass needs, each once.  The rows the taps name only ever move forward by whole rows, so a row is
+    // either one of the two listed last or a new one.
+    if (tid == 0) {
+      int n = 0, ra = -1, rb = -1, sa = 0, sb = 0;
+      for (int dl = 0; dl < rr; ++dl) {
+        int y0, b0, b1;
+        convert_unpack_tap(sh.rtap[d0 - band0 + dl], &y0, &b0, &b1);
+        const int y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+        int s0, s1;
+        if (y0 == ra) s0 = sa; else if (y0 == rb) s0 = sb; else { s0 = n; sh.row[n++] = y0; ra = rb; sa = sb; rb = y0; sb = s0; }
+        if (y1 == ra) s1 = sa; else if (y1 == rb) s1 = sb; else { s1 = n; sh.row[n++] = y1; ra = rb; sa = sb; rb = y1; sb = s1; }
+        sh.slot0[dl] = s0; sh.slot1[dl] = s1;
+      }
+      sh.nslots = n;
+    }
+    __syncthreads();
+    switch (fmt) {
+      case SL2_PIX_GRAY8: conv_stage<SL2_PIX_GRAY8>(sh, base, pitch, W, wpad); break;
+      case SL2_PIX_RGB24: conv_stage<SL2_PIX_RGB24>(sh, base, pitch, W, wpad); break;
+      case SL2_PIX_BGR24: conv_stage<SL2_PIX_BGR24>(sh, base, pitch, W, wpad); break;
+      case SL2_PIX_UYVY: conv_stage<SL2_PIX_UYVY>(sh, base, pitch, W, wpad); break;
+      default: conv_stage<SL2_PIX_YUYV>(sh, base, pitch, W, wpad); break;
+    }
+    __syncthreads();
+    if (tr < rl) {
+      for (int q = tq; q < nq; q += qs) {
+        const uint4 ct = q == tq ? ct_first : *reinterpret_cast<const uint4*>(ctab + 4 * q);
+        const uint32_t cw[4] = {ct.x, ct.y, ct.z, ct.w};
+        int x0[4], x1[4], a0[4], a1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          convert_unpack_tap(cw[i], &x0[i], &a0[i], &a1[i]);
+          x1[i] = x0[i] + 1 < W ? x0[i] + 1 : W - 1;
+        }
+        for (int dl = tr; dl < rr; dl += rl) {
+          int y0, b0, b1;
+          convert_unpack_tap(sh.rtap[d0 - band0 + dl], &y0, &b0, &b1);
+          const int k0 = sh.slot0[dl], k1 = sh.slot1[dl];
+          const uint8_t* g0 = sh.grey + k0 * wpad + sh.shift[k0];
+          const uint8_t* g1 = sh.grey + k1 * wpad + sh.shift[k1];
+          uint32_t packed = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int h0 = convert_hpass(g0[x0[i]], g0[x1[i]], a0[i], a1[i]);
+            const int h1 = convert_hpass(g1[x0[i]], g1[x1[i]], a0[i], a1[i]);
+            packed |= (uint32_t)convert_vpass(h0, h1, b0, b1) << (8 * i);
+          }
+          uint8_t* op = out + (size_t)(d0 + dl) * A.out_w + 4 * q;
+          const int left = A.out_w - 4 * q;
+          if (left >= 4 && ((uintptr_t)op & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(op) = packed;
+          } else {
+            for (int i = 0; i < 4 && i < left; ++i) op[i] = (uint8_t)(packed >> (8 * i));
+          }
+        }
+      }
+    }
+    __syncthreads();      // the next pass overwrites the slots
+  }
+}
+
+static std::string seq_text(int seq, const char* what) {
+  char buf[160];
+  snprintf(buf, sizeof(buf), "sequence %d: %s", seq, what);
+  return buf;
+}
+
+}  // namespace sl2
+
+using namespace sl2;
+
+// The opaque converter of the C ABI: the sources of its sequences, their tap tables on the device, a staging buffer for raw
+// frames that arrive in host memory.
+struct sl2_converter {
+  int device = 0, nseq = 0, out_w = 0, out_h = 0;
+  int col_taps = 0, tap_stride = 0;
+  std::vector<sl2_frame_source> src;
+  std::vector<uint8_t> have;
+  std::vector<uint32_t> taps;            // host copy of one sequence's table while it is built
+  sl2_frame_source* d_src = nullptr;
+  uint32_t* d_taps = nullptr;
+  uint8_t* stage = nullptr;              // raw frames from host memory land here (grown on demand)
+  size_t stage_bytes = 0;
+  hipEvent_t done = nullptr;             // the last conversion queued: sl2_converter_set_sources and a growing stage wait for it
+  bool queued = false;
+};
+
+extern "C" int sl2_converter_create(int device, int nseq, int out_width, int out_height, sl2_converter** out) {
+  if (!out || nseq < 1 || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+    set_error("sl2_converter_create: nseq >= 1 and an output size of 1 .. 4096 per axis are required");
+    return SL2_ERR_INVALID;
+  }
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device"); return SL2_ERR_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { set_error("sl2_converter_create: no such device"); return SL2_ERR_INVALID; }
+  SL2_HIP(hipSetDevice(device));
+  sl2_converter* c = new sl2_converter;
+  c->device = device; c->nseq = nseq; c->out_w = out_width; c->out_h = out_height;
+  c->col_taps = round_up(out_width, 4);
+  c->tap_stride = round_up(c->col_taps + out_height, 4);      // every table starts on a 16-byte boundary
+  c->src.resize(nseq); c->have.assign(nseq, 0); c->taps.assign(c->tap_stride, 0);
+  hipError_t e = hipMalloc(&c->d_src, (size_t)nseq * sizeof(sl2_frame_source));
+  if (e == hipSuccess) e = hipMalloc(&c->d_taps, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(c->d_taps, 0, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    set_error(std::string("sl2_converter_create: ") + hipGetErrorString(e));
+    sl2_converter_destroy(c);
+    return SL2_ERR_HIP;
+  }
+  *out = c;
+  return SL2_OK;
+}
+
+extern "C" void sl2_converter_destroy(sl2_converter* c) {
+  if (!c) return;
+  hipSetDevice(c->device);
+  if (c->queued) hipEventSynchronize(c->done);
+  if (c->done) hipEventDestroy(c->done);
+  if (c->d_src) hipFree(c->d_src);
+  if (c->d_taps) hipFree(c->d_taps);
+  if (c->stage) hipFree(c->stage);
+  delete c;
+}
+
+extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, const sl2_frame_source* src) {
+  if (!c || !src || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_set_sources: bad arguments"); return SL2_ERR_INVALID; }
+  for (int i = 0; i < nseq; ++i) {
+    const char* why = convert_source_fault(src[i], 0, false);
+    if (why) { set_error("sl2_converter_set_sources: " + seq_text(seq0 + i, why)); return SL2_ERR_INVALID; }
+  }
+  if (nseq == 0) return SL2_OK;
+  SL2_HIP(hipSetDevice(c->device));
+  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its tables
+  for (int i = 0; i < nseq; ++i) {
+    if (!convert_tap_table(src[i].width, src[i].height, c->out_w, c->out_h, c->taps.data(), c->taps.data() + c->col_taps)) {
+      set_error("sl2_converter_set_sources: " + seq_text(seq0 + i, "a tap does not fit its packed form"));
+      return SL2_ERR_INVALID;
+    }
+    SL2_HIP(hipMemcpy(c->d_taps + (size_t)(seq0 + i) * c->tap_stride, c->taps.data(), (size_t)c->tap_stride * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->src[seq0 + i] = src[i];
+    c->have[seq0 + i] = 1;
+  }
+  SL2_HIP(hipMemcpy(c->d_src + seq0, src, (size_t)nseq * sizeof(sl2_frame_source), hipMemcpyHostToDevice));
+  return SL2_OK;
+}
+
+extern "C" int sl2_converter_get_sources(const sl2_converter* c, int seq0, int nseq, sl2_frame_source* src) {
+  if (!c || !src || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_get_sources: bad arguments"); return SL2_ERR_INVALID; }
+  for (int i = 0; i < nseq; ++i) {
+    if (!c->have[seq0 + i]) { set_error("sl2_converter_get_sources: " + seq_text(seq0 + i, "its source was never set")); return SL2_ERR_INVALID; }
+    src[i] = c->src[seq0 + i];
+  }
+  return SL2_OK;
+}
+
+extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* raw, size_t raw_bytes, int raw_on_device,
+                                  uint8_t* d_frames, size_t seq_stride) {
+  if (!c || !raw || !d_frames) { set_error("sl2_convert_frames: bad arguments"); return SL2_ERR_INVALID; }
+  if (seq_stride < (size_t)c->out_w * c->out_h) { set_error("sl2_convert_frames: seq_stride is below out_width * out_height"); return SL2_ERR_INVALID; }
+  for (int s = 0; s < c->nseq; ++s) {
+    if (!c->have[s]) { set_error("sl2_convert_frames: " + seq_text(s, "its source was never set")); return SL2_ERR_INVALID; }
+    const char* why = convert_source_fault(c->src[s], raw_bytes, true);
+    if (why) { set_error("sl2_convert_frames: " + seq_text(s, why)); return SL2_ERR_INVALID; }
+  }
+  SL2_HIP(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint8_t* d_raw = (const uint8_t*)raw;
+  if (!raw_on_device) {
+    if (raw_bytes > c->stage_bytes) {
+      if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion may still read the old one
+      if (c->stage) { SL2_HIP(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
+      SL2_HIP(hipMalloc(&c->stage, raw_bytes));
+      c->stage_bytes = raw_bytes;
+    }
+    SL2_HIP(hipMemcpyAsync(c->stage, raw, raw_bytes, hipMemcpyHostToDevice, st));
+    d_raw = c->stage;
+  }
+  ConvArgs A;
+  A.src = c->d_src; A.taps = c->d_taps; A.raw = d_raw; A.out = d_frames; A.seq_stride = seq_stride;
+  A.out_w = c->out_w; A.out_h = c->out_h; A.col_taps = c->col_taps; A.tap_stride = c->tap_stride;
+  A.bands = (c->out_h + kConvBandRows - 1) / kConvBandRows;
+  hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
+  SL2_HIP(hipGetLastError());
+  SL2_HIP(hipEventRecord(c->done, st));
+  c->queued = true;
+  return SL2_OK;
+}
+
+extern "C" int sl2_convert_frame_host(const sl2_frame_source* src, const void* raw, size_t raw_bytes, int out_width, int out_height,
+                                      uint8_t* out) {
+  if (!src || !raw || !out || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+    set_error("sl2_convert_frame_host: bad arguments");
+    return SL2_ERR_INVALID;
+  }
+  const char* why = convert_source_fault(*src, raw_bytes, true);
+  if (why) { set_error("sl2_convert_frame_host: " + seq_text(0, why)); return SL2_ERR_INVALID; }
+  std::vector<uint32_t> taps((size_t)out_width + out_height);
+  if (!convert_frame_host_body(*src, (const uint8_t*)raw, out_width, out_height, taps.data(), taps.data() + out_width, out)) {
+    set_error("sl2_convert_frame_host: a tap does not fit its packed form");
+    return SL2_ERR_INVALID;
+  }
+  return SL2_OK;
+}
+
+extern "C" int sl2_scale_camera(const sl2_camera* in, int out_width, int out_height, sl2_camera* out) {
+  if (!in || !out || in->width < 1 || in->height < 1 || out_width < 1 || out_height < 1) { set_error("sl2_scale_camera: bad arguments"); return SL2_ERR_INVALID; }
+  if ((long long)in->width * out_height != (long long)in->height * out_width) {
+    set_error("sl2_scale_camera: the resize changes the aspect ratio; the radial distortion term survives a uniform scale only");
+    return SL2_ERR_INVALID;
+  }
+  const double s = (double)in->width / (double)out_width;
+  sl2_camera r = *in;
+  r.width = out_width; r.height = out_height;
+  r.fku = in->fku / s; r.fkv = in->fkv / s;
+  r.u0 = (in->u0 + 0.5) / s - 0.5; r.v0 = (in->v0 + 0.5) / s - 0.5;
+  r.kd1 = in->kd1 * s * s;
+  *out = r;
+  return SL2_OK;
+}

@@ -513,6 +513,8 @@ class MonoSLAM:
         self.uu_, self.vv_ = 0, 0                   # image selection (set by the GUI's mouse handler in the reference)
         self.location_selected_flag_ = False
         self.marked_feature_label_ = -1             # monoslam.h:171
+        self._converter = None                      # SetFrameSource: raw camera frames in front of GoOneStep
+        self._frame_dev = None
 
     # MonoSLAM::Init(config_path) — monoslam.cpp:1574-1969
     def Init(self, config_path, template_dirs=()):
@@ -560,6 +562,9 @@ class MonoSLAM:
         if f.size != self._engine.frame_bytes:
             raise ValueError("frame must be %d x %d 8-bit single channel" % (self.camera_["width"], self.camera_["height"]))
         self._engine.go_one_step(f.reshape(1, -1), save_trajectory, enable_mapping)
+        return self._after_step(enable_mapping)
+
+    def _after_step(self, enable_mapping):
         # the reference's feature_list_ is unbounded; the engine holds at most max_features LIVE features per sequence
         # (deleted ones give their slots back): a full map must not pass silently (SL2_STATUS_LABELS_EXHAUSTED)
         if enable_mapping:
@@ -570,6 +575,27 @@ class MonoSLAM:
                                    "initialise features until one is deleted - create the engine with a larger max_features"
                                    % self._max_features)
         return True  # the reference always returns true (monoslam.cpp:179)
+
+    def SetFrameSource(self, width, height, pitch, format):
+        """What the camera delivers (UsbCamGrabber, usbcamgrabber.cpp:75-113): its size, row pitch in bytes and pixel format
+        (convert.SL2_PIX_* or "uyvy", "rgb24" ...).  GoOneStepRaw converts such frames to the engine's grey image on the
+        device.  The converter and the device frame are created on the first call."""
+        from . import convert
+        if self._converter is None:
+            self._converter = convert.FrameConverter(self._device, 1, self.camera_["width"], self.camera_["height"])
+            self._frame_dev = _lib.DeviceBuffer(self._engine.frame_bytes, self._device)
+        self._converter.set_sources([dict(width=width, height=height, pitch=pitch, format=format)])
+
+    def GoOneStepRaw(self, raw, save_trajectory=False, enable_mapping=False, on_device=False):
+        """sl2_convert_frames, then GoOneStep on the converted device frame.  raw: the camera's bytes as a uint8 array, or with
+        on_device=True a (device pointer, bytes) pair."""
+        if self._converter is None:
+            raise RuntimeError("MonoSLAM.GoOneStepRaw: call SetFrameSource first")
+        keep = self._converter.convert(raw if not on_device else tuple(raw), self._frame_dev, stream=self._engine.stream)
+        self._engine.go_one_step(self._frame_dev.ptr, save_trajectory, enable_mapping, on_device=True)
+        if keep is not None:
+            self._engine.synchronize()  # the host buffer must outlive the copy queued in front of the step
+        return self._after_step(enable_mapping)
 
     def _frame(self, frame):
         f = np.ascontiguousarray(frame, dtype=np.uint8)

@@ -1,0 +1,127 @@
+#!/usr/bin/env python
+"""Speed of sl2_convert_frames (k_convert_frames) for 1024 sequences to 320 x 240, written to profiles/frame_convert_bench.json.
+
+Four sources, every sequence of a run the same: 640 x 480 UYVY, 640 x 480 RGB24, 960 x 720 RGB24 and the native grey copy.
+Per source, timed with device events on one stream, after a warm-up, median of --reps launches:
+  (a) the conversion (one launch; the raw frames are device memory),
+  (b) hipMemcpyAsync device-to-device in the same process - the yardstick, there being no earlier build - of as many bytes as
+      the kernel must touch (memcpy_touched: it reads AND writes that many, twice the kernel's traffic) and of half as many
+      (memcpy_same_traffic: its reads plus writes equal the kernel's bytes).
+"Must touch" is computed here from the shapes: the source rows that some row tap names, at the bytes of a row each, plus the
+output.  Rates are those bytes over the time.  The result is checked against sl2_convert_frame_host on a few sequences first.
+
+    python scripts/bench_frame_convert.py [--batch 1024] [--reps 30] [--out profiles/frame_convert_bench.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch          # before scenelib2_amd: one HIP runtime
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from scenelib2_amd import _lib, convert  # noqa: E402
+
+SOURCES = [("640x480 UYVY", 640, 480, "uyvy"), ("640x480 RGB24", 640, 480, "rgb24"), ("960x720 RGB24", 960, 720, "rgb24"),
+           ("320x240 GRAY8 (native copy)", 320, 240, "gray8")]
+STEP_MS = 1.45          # the headline step (README) the conversion sits in front of
+
+
+def commit():
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], text=True, stderr=subprocess.DEVNULL).strip()
+    except Exception:
+        p = os.path.join(ROOT, ".build_git")
+        return open(p).read().strip() if os.path.exists(p) else "unknown"
+
+
+def rows_read(src_h, out_h):
+    """Source rows that some row tap names (the definition of include/scenelib2_amd.h, in float32 like it)."""
+    d = np.arange(out_h, dtype=np.float64)
+    f = ((d + 0.5) * (np.float64(src_h) / np.float64(out_h)) - 0.5).astype(np.float32)
+    i = np.clip(np.floor(f).astype(np.int64), 0, src_h - 1)
+    return int(np.unique(np.concatenate([i, np.minimum(i + 1, src_h - 1)])).size)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frame_convert_bench.json"))
+    args = ap.parse_args()
+    if _lib.device_count() < 1:
+        raise SystemExit("bench_frame_convert: no HIP device (there is no CPU fallback)")
+    B, ow, oh = args.batch, 320, 240
+    stream = torch.cuda.Stream()
+    out = torch.empty(B * ow * oh, dtype=torch.uint8, device="cuda")
+
+    def timed(fn):
+        ms = []
+        for i in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                a.record(stream)
+                fn()
+                b.record(stream)
+            b.synchronize()
+            if i >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return ms
+
+    med = lambda v: float(np.median(np.asarray(v)))
+    runs = []
+    for name, w, h, fmt in SOURCES:
+        bpp = convert.BYTES_PER_PIXEL[convert.FORMATS[fmt]]
+        frame = w * h * bpp
+        g = torch.Generator(device="cuda")
+        g.manual_seed(w * 31 + bpp)
+        raw = torch.randint(0, 256, (B * frame,), dtype=torch.uint8, device="cuda", generator=g)
+        cv = convert.FrameConverter(0, B, ow, oh)
+        cv.set_sources([dict(width=w, height=h, format=fmt, offset=s * frame) for s in range(B)])
+        go = lambda: cv.convert((raw.data_ptr(), raw.numel()), out.data_ptr(), stream=stream.cuda_stream)
+        go()
+        stream.synchronize()
+        for s in (0, B // 2, B - 1):          # the bytes are right before their time is worth anything
+            want = convert.convert_frame_host(dict(width=w, height=h, format=fmt), raw[s * frame:(s + 1) * frame].cpu().numpy(), ow, oh)
+            assert np.array_equal(out[s * ow * oh:(s + 1) * ow * oh].cpu().numpy().reshape(oh, ow), want), (name, s)
+        read = B * rows_read(h, oh) * w * bpp
+        touched = read + B * ow * oh
+        conv_ms = timed(go)
+        scratch_a = torch.empty(touched, dtype=torch.uint8, device="cuda")
+        scratch_b = torch.empty(touched, dtype=torch.uint8, device="cuda")
+
+        def d2d(n):
+            def fn():
+                with torch.cuda.stream(stream):
+                    scratch_b[:n].copy_(scratch_a[:n], non_blocking=True)
+            return fn
+
+        full_ms, half_ms = timed(d2d(touched)), timed(d2d(touched // 2))
+        runs.append(dict(source=name, raw_bytes=B * frame, bytes_read=read, bytes_written=B * ow * oh, bytes_touched=touched,
+                         source_rows_read=rows_read(h, oh), convert_ms=med(conv_ms), convert_TBps=touched / med(conv_ms) / 1e9,
+                         memcpy_touched_ms=med(full_ms), memcpy_same_traffic_ms=med(half_ms),
+                         memcpy_same_traffic_TBps=touched / med(half_ms) / 1e9,
+                         convert_over_memcpy_same_traffic=med(conv_ms) / med(half_ms),
+                         convert_over_memcpy_touched=med(conv_ms) / med(full_ms),
+                         convert_over_step=med(conv_ms) / STEP_MS,
+                         spread_ms=dict(convert=[min(conv_ms), max(conv_ms)], memcpy_same_traffic=[min(half_ms), max(half_ms)])))
+        cv.close()
+        del raw, scratch_a, scratch_b
+        torch.cuda.empty_cache()
+    res = dict(commit=commit(), device=torch.cuda.get_device_name(0), batch=B, out_width=ow, out_height=oh, reps=args.reps,
+               headline_step_ms=STEP_MS, runs=runs,
+               note="bytes_touched below 256 MiB (the native copy) can live in the Infinity Cache between repeats: for the "
+                    "conversion and for the copy alike")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

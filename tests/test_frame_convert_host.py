@@ -1,0 +1,199 @@
+"""Raw camera frames, host side: sl2_convert_frame_host against a NumPy restatement of the definition (frame_convert_cases.py,
+written from the header's text; it calls nothing of the library), the exact anchors, the refusals, sl2_scale_camera, and the
+stand-alone bounds program under AddressSanitizer.  (The kernel: tests/test_gpu_frame_convert.py.)"""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+import frame_convert_cases as fc
+
+from scenelib2_amd import _lib, convert
+
+
+def _cases():
+    n, used = 0, dict.fromkeys(fc.FORMATS, 0)
+    for ow, oh in fc.OUT_SIZES:
+        for sw, sh in fc.SRC_SIZES:
+            for fmt in fc.FORMATS:
+                if fc.allowed(fmt, sw):
+                    k = used[fmt]          # every format walks through the nine (pitch, offset) pairs on its own count
+                    yield ow, oh, sw, sh, fmt, fc.PITCH_PADS[k % 3], fc.OFFSETS[(k // 3) % 3], n
+                    used[fmt] += 1
+                    n += 1
+
+
+CASES = list(_cases())
+
+
+def test_case_list_covers_every_format_pitch_and_offset():
+    assert len(CASES) == 4 * (6 * 5 + 5 * 3)          # six even widths take every format, five odd ones the three unpacked
+    assert {(c[4], c[5], c[6]) for c in CASES} == {(f, p, o) for f in fc.FORMATS for p in fc.PITCH_PADS for o in fc.OFFSETS}
+
+
+def test_host_form_equals_the_definition_and_stays_within_one_level_of_exact_bilinear():
+    worst = 0.0
+    for ow, oh, sw, sh, fmt, pad, off, n in CASES:
+        s = fc.source(sw, sh, fmt, pad, off)
+        raw = fc.random_raw(s, 1000 + n)
+        got = convert.convert_frame_host(s, raw, ow, oh)
+        want = fc.reference(s, raw, ow, oh)
+        assert got.shape == (oh, ow) and np.array_equal(got, want), (ow, oh, s, int(np.abs(got.astype(int) - want).max()))
+        err = float(np.abs(got.astype(np.float64) - fc.exact_bilinear(s, raw, ow, oh)).max())
+        worst = max(worst, err)
+        assert err < 1.0, (ow, oh, s, err)
+    print("worst |out - exact bilinear| = %.4f grey levels" % worst)
+
+
+@pytest.mark.parametrize("fmt", fc.FORMATS)
+def test_identity_size_reproduces_the_grey_plane(fmt):
+    for (w, h), pad, off in (((320, 240), 13, 7), ((2, 2), 1, 1), ((322, 242), 0, 0)):
+        s = fc.source(w, h, fmt, pad, off)
+        raw = fc.random_raw(s, 7 + fmt)
+        assert np.array_equal(convert.convert_frame_host(s, raw, w, h), fc.grey_plane(s, raw).astype(np.uint8))
+
+
+@pytest.mark.parametrize("fmt", fc.FORMATS)
+def test_a_constant_image_stays_constant(fmt):
+    for value in (0, 1, 127, 254, 255):
+        for (sw, sh), (ow, oh) in (((640, 480), (320, 240)), ((31, 17), (33, 17)), ((160, 120), (320, 240)), ((961, 3), (7, 5))):
+            if not fc.allowed(fmt, sw):
+                continue
+            s, raw = fc.pack_grey(np.full((sh, sw), value, np.uint8), fmt, pad=1, offset=1, seed=value)
+            out = convert.convert_frame_host(s, raw, ow, oh)
+            assert (out == value).all(), (fmt, value, sw, sh, ow, oh)
+
+
+def test_packed_422_picks_the_luma_bytes_of_a_ramp():
+    w, h = 64, 3
+    ramp = (np.arange(2 * w * h) % 256).astype(np.uint8)
+    uyvy = convert.convert_frame_host(fc.source(w, h, fc.UYVY), ramp, w, h)
+    yuyv = convert.convert_frame_host(fc.source(w, h, fc.YUYV), ramp, w, h)
+    rows = ramp.reshape(h, 2 * w)
+    assert np.array_equal(uyvy, rows[:, 1::2]) and np.array_equal(yuyv, rows[:, 0::2])
+    assert uyvy[0, 0] == 1 and yuyv[0, 0] == 0 and uyvy[0, 1] == 3 and yuyv[0, 1] == 2
+
+
+def test_rgb_primaries():
+    px = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 255]], np.uint8).reshape(-1)
+    assert convert.convert_frame_host(fc.source(4, 1, fc.RGB24), px, 4, 1).tolist() == [[76, 150, 29, 255]]
+    assert convert.convert_frame_host(fc.source(4, 1, fc.BGR24), px, 4, 1).tolist() == [[29, 150, 76, 255]]
+
+
+def _rc(s, raw_bytes, ow=8, oh=8, nbuf=None):
+    L = _lib.load()
+    buf = np.zeros(nbuf if nbuf is not None else max(int(raw_bytes), 1), np.uint8)
+    out = np.zeros(ow * oh, np.uint8)
+    src = _lib.sl2_frame_source(s["width"], s["height"], s["pitch"], s["format"], s["offset"])
+    return L.sl2_convert_frame_host(C.byref(src), buf.ctypes.data_as(_lib.vp), int(raw_bytes), ow, oh, _lib.u8p(out))
+
+
+def test_refusals():
+    good = fc.source(16, 9, fc.RGB24, pad=5, offset=3)
+    need = fc.source_bytes(good)
+    assert need == 3 + 8 * 53 + 48
+    assert _rc(good, need) == _lib.SL2_OK                                 # the exact size is accepted
+    assert _rc(good, need - 1, nbuf=need) == _lib.SL2_ERR_INVALID         # one byte short is not
+    assert "sequence 0" in _lib.load().sl2_last_error().decode()
+    bad = [dict(good, pitch=47), dict(good, width=0), dict(good, height=0), dict(good, width=-3), dict(good, width=4097, pitch=3 * 4097),
+           dict(good, height=16385), dict(good, format=5), dict(good, format=-1),
+           dict(good, format=fc.UYVY, width=15, pitch=64), dict(good, format=fc.YUYV, width=15, pitch=64),
+           dict(good, offset=1 << 62)]
+    for s in bad:
+        assert _rc(s, 1 << 20, nbuf=16) == _lib.SL2_ERR_INVALID, s
+    assert _rc(dict(good, width=4096, height=2, pitch=3 * 4096, offset=0), 2 * 3 * 4096) == _lib.SL2_OK      # the caps themselves pass
+    assert _rc(fc.source(4, 16384, fc.GRAY8), 4 * 16384) == _lib.SL2_OK
+    with pytest.raises(_lib.Sl2Error) as ei:
+        convert.convert_frame_host(dict(good, pitch=47), np.zeros(need, np.uint8), 8, 8)
+    assert ei.value.code == _lib.SL2_ERR_INVALID
+
+
+def _project(cam, rays):
+    """Camera::Project (camera.cpp; sl2_math.hpp measurement_model): a point of the camera frame to pixels."""
+    ic0 = -cam["fku"] * rays[:, 0] / rays[:, 2]
+    ic1 = -cam["fkv"] * rays[:, 1] / rays[:, 2]
+    factor = np.sqrt(1 + 2 * cam["kd1"] * (ic0 * ic0 + ic1 * ic1))
+    return np.stack([ic0 / factor + cam["u0"], ic1 / factor + cam["v0"]], axis=1)
+
+
+@pytest.mark.parametrize("s", [2.0, 3.0, 0.5, 1.0])
+def test_scale_camera_commutes_with_projection(s):
+    ow, oh = 320, 240
+    src = dict(width=int(ow * s), height=int(oh * s), fku=195.0 * s + 0.25, fkv=193.5 * s, u0=162.0 * s + 0.3, v0=125.0 * s - 0.7,
+               kd1=9e-06 / (s * s), sd=2)
+    rng = np.random.default_rng(5)
+    rays = np.stack([rng.uniform(-0.5, 0.5, 200), rng.uniform(-0.4, 0.4, 200), rng.uniform(0.6, 2.0, 200)], axis=1)
+    out = convert.scale_camera(src, ow, oh)
+    assert (out["width"], out["height"], out["sd"]) == (ow, oh, 2)
+    want = (_project(src, rays) + 0.5) / s - 0.5
+    assert np.abs(_project(out, rays) - want).max() <= 1e-9
+    assert out["fku"] == src["fku"] / s and out["kd1"] == src["kd1"] * s * s and out["v0"] == (src["v0"] + 0.5) / s - 0.5
+
+
+def test_scale_camera_refuses_a_change_of_aspect():
+    src = dict(width=640, height=480, fku=390.0, fkv=390.0, u0=324.0, v0=250.0, kd1=2e-06, sd=1)
+    for ow, oh in ((320, 200), (320, 241), (639, 480)):
+        with pytest.raises(_lib.Sl2Error) as ei:
+            convert.scale_camera(src, ow, oh)
+        assert ei.value.code == _lib.SL2_ERR_INVALID
+    assert convert.scale_camera(src, 1280, 960)["fku"] == 780.0
+
+
+def test_bindings_and_adapters_know_the_feature():
+    import inspect
+    import scenelib2_amd
+    assert C.sizeof(_lib.sl2_frame_source) == 24 and _lib.sl2_frame_source.offset.offset == 16
+    for name in ("FrameConverter", "convert_frame_host", "scale_camera"):
+        assert hasattr(scenelib2_amd, name)
+    assert list(inspect.signature(scenelib2_amd.MonoSLAM.SetFrameSource).parameters) == ["self", "width", "height", "pitch", "format"]
+    assert "GoOneStepRaw" in dir(scenelib2_amd.MonoSLAM)
+    hpp = open(os.path.join(ROOT, "include", "scenelib2_amd_monoslam.hpp")).read()
+    assert "void SetFrameSource(" in hpp and "bool GoOneStepRaw(" in hpp and "sl2_convert_frames" in hpp
+    mk = open(os.path.join(ROOT, "scenelib2_amd", "csrc", "Makefile")).read()
+    assert mk.count("sl2_convert.hip") == 1 and "sl2_convert_dev.hpp" in mk and "sl2_convert.o" in mk
+
+
+def test_host_body_stays_inside_exactly_sized_blocks_under_asan(tmp_path):
+    """tests/frame_convert_host.cpp: a program of its own (nothing loaded into Python), built with the address and
+    undefined-behaviour sanitizers, over the same edge shapes with exactly sized heap blocks."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    exe = os.path.join(str(tmp_path), "frame_convert_host")
+    src = os.path.join(ROOT, "tests", "frame_convert_host.cpp")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, src])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert res.stdout.startswith("ok ")
+
+
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+def test_kernel_leaves_room_for_two_workgroups_per_cu_and_does_not_spill(tmp_path):
+    """k_convert_frames' descriptor: its static LDS (the staged grey rows and the slot lists) fits a CU's 160 KB eight times, the width cap fits a pass of two output rows, and nothing spills."""
+    import re
+    csrc = os.path.join(ROOT, "scenelib2_amd", "csrc")
+    out = os.path.join(str(tmp_path), "sl2_convert.s")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wno-unused-value",
+                    "-Wno-unused-result", "--cuda-device-only", "-S", os.path.join(csrc, "sl2_convert.hip"), "-o", out],
+                   check=True, capture_output=True, timeout=900)
+    text = open(out).read()
+    m = re.search(r"\.name:\s+\S*k_convert_frames\S*\n", text)
+    assert m
+    block = text[text.rfind("- .agpr_count", 0, m.start()):]
+    lds = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
+    assert lds <= 160 * 1024 // 8, lds          # eight workgroups a CU (the issue asks for two at least)
+    assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1)) == 0
+    assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", block).group(1)) <= 8          # scalars parked in vector lanes, no memory
+    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)) == 0
+    assert int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1)) <= 64           # eight wavefronts per SIMD: eight workgroups of four a CU
+    hdr = open(os.path.join(csrc, "sl2_convert_dev.hpp")).read()
+    cap = int(re.search(r"constexpr int kConvertMaxWidth = (\d+);", hdr).group(1))
+    assert cap >= 4096 and int(re.search(r"constexpr int kConvertMaxHeight = (\d+);", hdr).group(1)) == 16384
+    assert lds >= 4 * (cap + 16)          # four staged rows at the cap: a pass of two output rows
