@@ -43,7 +43,9 @@ extern "C" {
  * sl2_set_pause_catch_up (the time step is the sequence's: sl2_params.delta_t is its initial value); sl2_set_cameras,
  * sl2_get_cameras (the calibration is the sequence's: the sl2_create camera is its initial value and the batch's image size);
  * sl2_converter_create, sl2_converter_destroy, sl2_converter_set_sources, sl2_converter_get_sources, sl2_convert_frames,
- * sl2_convert_frame_host, sl2_scale_camera (raw camera frames of any size and pixel format, in front of the step). */
+ * sl2_convert_frame_host, sl2_scale_camera (raw camera frames of any size and pixel format, in front of the step);
+ * sl2_converter_set_filters, sl2_converter_get_filters, sl2_convert_frame_host_filtered (SL2_RESIZE_AREA: the exact box average
+ * for cameras much larger than the engine's image). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -477,6 +479,33 @@ int sl2_convert_frames(sl2_converter* c, void* stream, const void* raw, size_t r
 /* The same arithmetic for one sequence on the host (no GPU needed): out[out_height][out_width].  Same refusals. */
 int sl2_convert_frame_host(const sl2_frame_source* src, const void* raw, size_t raw_bytes, int out_width, int out_height,
                            uint8_t* out);
+/* The resize filter, per sequence.  SL2_RESIZE_LINEAR (the default) is the two-tap form above: right for the reference's 640 x 480
+ * webcam, but it reads two source rows and two source columns per output pixel whatever the reduction, and what lies between them
+ * aliases.  SL2_RESIZE_AREA is the exact box average: every source pixel under an output pixel, weighted by the area they share.
+ * Integers only, no tables (scenelib2_amd/csrc/sl2_convert_dev.hpp):
+ *   grey    g[y][x] as above, all five formats.
+ *   weights along an axis of S source and D output pixels, S >= D, in units of 1/D of a source pixel: output d covers
+ *           [d S, (d + 1) S), source i covers [i D, (i + 1) D).  The taps of d are i = floor(d S / D) .. floor(((d + 1) S - 1) / D) and
+ *           w(d, i) = min((i + 1) D, (d + 1) S) - max(i D, d S): 1 .. D each, summing to S over one output and to D over one source.
+ *   pixel   acc = sum_y sum_x wy(dy, y) wx(dx, x) g[y][x], exact (at most 255 Sx Sy < 2^34 at the caps);
+ *           out = floor((2 acc + Sx Sy) / (2 Sx Sy)): the exact mean, halves rounded up.
+ * It is the identity where source and output size agree and maps a constant image to itself.  It only reduces: a source narrower
+ * or lower than the output is refused under SL2_RESIZE_AREA (no per-axis fallback).
+ * Planar and semi-planar 4:2:0 frames (NV12, NV21, I420, YV12) need no format of their own: their luma plane is a SL2_PIX_GRAY8
+ * source of `height` rows with the plane's pitch, and the chroma that follows is never reached.
+ * sl2_converter_set_filters: a setup call like sl2_converter_set_sources (it may wait for the last conversion queued, which keeps
+ * the filters it was queued with), before or after the sequence's source is set.  Refused (SL2_ERR_INVALID, no sequence of the
+ * range changes, the text names the sequence): a filter id other than these two; SL2_RESIZE_AREA for a sequence whose source is
+ * set and is smaller than the output on an axis.  sl2_converter_set_sources refuses such a source for a sequence whose filter is
+ * SL2_RESIZE_AREA.  sl2_converter_get_filters works for any sequence, its source set or not.
+ * sl2_convert_frames then issues one more launch (k_convert_area) for the SL2_RESIZE_AREA sequences; with none it is unchanged.
+ * sl2_convert_frame_host_filtered: the host form; with SL2_RESIZE_LINEAR the bytes of sl2_convert_frame_host.  Its refusals, plus
+ * an unknown filter and a source smaller than the output under SL2_RESIZE_AREA. */
+enum { SL2_RESIZE_LINEAR = 0, SL2_RESIZE_AREA = 1 };
+int sl2_converter_set_filters(sl2_converter* c, int seq0, int nseq, const int32_t* filters);
+int sl2_converter_get_filters(const sl2_converter* c, int seq0, int nseq, int32_t* filters);
+int sl2_convert_frame_host_filtered(const sl2_frame_source* src, int filter, const void* raw, size_t raw_bytes,
+                                    int out_width, int out_height, uint8_t* out);
 /* The calibration of the resized image from that of the source image (in->width, in->height = the source size): with
  * s = in->width / out_width, fku' = fku / s, fkv' = fkv / s, u0' = (u0 + 0.5) / s - 0.5, v0' likewise, kd1' = kd1 s s; sd is
  * unchanged (the measurement noise in output pixels is the caller's choice).  The radial term lives in centred pixels and

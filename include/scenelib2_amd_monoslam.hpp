@@ -226,10 +226,24 @@ class MonoSLAM {
       void* p = nullptr;
       check(sl2_dev_malloc(device_, (size_t)camera_->width_ * camera_->height_, &p), "sl2_dev_malloc");
       frame_dev_ = (uint8_t*)p;
+      const int32_t f = frame_filter_;
+      check(sl2_converter_set_filters(converter_, 0, 1, &f), "sl2_converter_set_filters");
     }
     sl2_frame_source src;
     src.width = width; src.height = height; src.pitch = pitch; src.format = format; src.offset = 0;
     check(sl2_converter_set_sources(converter_, 0, 1, &src), "sl2_converter_set_sources");
+  }
+
+  // How GoOneStepRaw brings the camera's frame to the engine's size: SL2_RESIZE_LINEAR (the reference's plain INTER_LINEAR, the
+  // default) or SL2_RESIZE_AREA, the exact box average for cameras much larger than the engine's image.  Before or after
+  // SetFrameSource; SL2_RESIZE_AREA with a source smaller than the engine's image is refused by whichever call comes second.
+  void SetFrameFilter(int filter) {
+    if (filter != SL2_RESIZE_LINEAR && filter != SL2_RESIZE_AREA) throw std::runtime_error("MonoSLAM::SetFrameFilter: unknown filter");
+    if (converter_) {
+      const int32_t f = filter;
+      check(sl2_converter_set_filters(converter_, 0, 1, &f), "sl2_converter_set_filters");
+    }
+    frame_filter_ = filter;
   }
 
   // The reference's camera loop in one call: cvtColor + resize (sl2_convert_frames, on the engine's stream), then GoOneStep on the
@@ -570,6 +584,7 @@ class MonoSLAM {
   sl2_engine* eng_ = nullptr;
   sl2_converter* converter_ = nullptr;   // SetFrameSource: raw camera frames in front of GoOneStep
   uint8_t* frame_dev_ = nullptr;         // the converted frame, camera_->width_ x camera_->height_, device memory
+  int frame_filter_ = SL2_RESIZE_LINEAR; // SetFrameFilter
 };
 
 // Kalman (kalman.h:51-52): the reference's filter object works on the MonoSLAM it is handed; so does this one.

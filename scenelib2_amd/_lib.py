@@ -99,6 +99,7 @@ class sl2_frame_source(C.Structure):
 
 
 SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_BGR24, SL2_PIX_UYVY, SL2_PIX_YUYV = range(5)
+SL2_RESIZE_LINEAR, SL2_RESIZE_AREA = 0, 1
 
 # the same 96 bytes as a NumPy structured dtype (what Engine.step_stats returns)
 STEP_STATS_DTYPE = np.dtype([(n, np.int32) for n in ("stepped", "status_flags", "sequence_steps", "n_features", "n_partial",
@@ -135,6 +136,7 @@ EXPORTED_SYMBOLS = [
     "sl2_set_cameras", "sl2_get_cameras",
     "sl2_converter_create", "sl2_converter_destroy", "sl2_converter_set_sources", "sl2_converter_get_sources",
     "sl2_convert_frames", "sl2_convert_frame_host", "sl2_scale_camera",
+    "sl2_converter_set_filters", "sl2_converter_get_filters", "sl2_convert_frame_host_filtered",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -267,6 +269,10 @@ def _bind(L):
         L.sl2_converter_get_sources.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sl2_frame_source)]
         L.sl2_convert_frames.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t]
         L.sl2_convert_frame_host.argtypes = [C.POINTER(sl2_frame_source), vp, C.c_size_t, C.c_int, C.c_int, c_u8p]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_converter_set_filters"):
+        L.sl2_converter_set_filters.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.sl2_converter_get_filters.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.sl2_convert_frame_host_filtered.argtypes = [C.POINTER(sl2_frame_source), C.c_int, vp, C.c_size_t, C.c_int, C.c_int, c_u8p]
         L.sl2_scale_camera.argtypes = [C.POINTER(sl2_camera), C.c_int, C.c_int, C.POINTER(sl2_camera)]
     return L
 

@@ -13,11 +13,16 @@ from . import _lib
 from ._lib import SL2_PIX_BGR24, SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_UYVY, SL2_PIX_YUYV  # noqa: F401
 
 FORMATS = {"gray8": SL2_PIX_GRAY8, "rgb24": SL2_PIX_RGB24, "bgr24": SL2_PIX_BGR24, "uyvy": SL2_PIX_UYVY, "yuyv": SL2_PIX_YUYV}
+FILTERS = {"linear": _lib.SL2_RESIZE_LINEAR, "area": _lib.SL2_RESIZE_AREA}
 BYTES_PER_PIXEL = {SL2_PIX_GRAY8: 1, SL2_PIX_RGB24: 3, SL2_PIX_BGR24: 3, SL2_PIX_UYVY: 2, SL2_PIX_YUYV: 2}
 
 
 def _format(f):
     return FORMATS[f.lower()] if isinstance(f, str) else int(f)
+
+
+def _filter(f):
+    return FILTERS[f.lower()] if isinstance(f, str) else int(f)
 
 
 def make_source(src):
@@ -60,6 +65,20 @@ class FrameConverter:
         _lib.check(self.L.sl2_converter_get_sources(self.h, int(seq0), nseq, arr), self.L)
         return [dict(width=s.width, height=s.height, pitch=s.pitch, format=s.format, offset=s.offset) for s in arr]
 
+    def set_filters(self, filters, seq0=0):
+        """filters: "linear" / "area" (or SL2_RESIZE_*) for sequences seq0 ...; one value stands for a list of one.  A setup call
+        like set_sources, before or after it.  "area", the exact box average, only reduces: a smaller source is refused."""
+        if isinstance(filters, (str, int)):
+            filters = [filters]
+        arr = (C.c_int32 * len(filters))(*[_filter(f) for f in filters])
+        _lib.check(self.L.sl2_converter_set_filters(self.h, int(seq0), len(filters), arr), self.L)
+
+    def get_filters(self, seq0=0, nseq=None):
+        nseq = self.nseq - seq0 if nseq is None else int(nseq)
+        arr = (C.c_int32 * nseq)()
+        _lib.check(self.L.sl2_converter_get_filters(self.h, int(seq0), nseq, arr), self.L)
+        return list(arr)
+
     def convert(self, raw, d_frames, seq_stride=0, stream=None, raw_bytes=None):
         """raw: a uint8 array in host memory (copied to the converter's staging buffer on `stream`; keep it alive and
         unchanged until the stream has passed the copy), or a (device pointer, bytes) pair.  d_frames: a device pointer
@@ -89,14 +108,19 @@ class FrameConverter:
             pass
 
 
-def convert_frame_host(src, raw, out_width, out_height, raw_bytes=None):
-    """One sequence on the host (no GPU needed): uint8 [out_height][out_width]."""
+def convert_frame_host(src, raw, out_width, out_height, raw_bytes=None, filter="linear"):
+    """One sequence on the host (no GPU needed): uint8 [out_height][out_width].  filter: "linear" or "area" (FILTERS)."""
     L = _lib.load()
     a = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
     n = a.size if raw_bytes is None else int(raw_bytes)
     out = np.zeros((int(out_height), int(out_width)), np.uint8)
     s = make_source(src)
-    _lib.check(L.sl2_convert_frame_host(C.byref(s), a.ctypes.data_as(_lib.vp), n, int(out_width), int(out_height), _lib.u8p(out)), L)
+    f = _filter(filter)
+    if f == _lib.SL2_RESIZE_LINEAR:
+        _lib.check(L.sl2_convert_frame_host(C.byref(s), a.ctypes.data_as(_lib.vp), n, int(out_width), int(out_height), _lib.u8p(out)), L)
+    else:
+        _lib.check(L.sl2_convert_frame_host_filtered(C.byref(s), f, a.ctypes.data_as(_lib.vp), n, int(out_width), int(out_height),
+                                                     _lib.u8p(out)), L)
     return out
 
 

@@ -21,6 +21,9 @@ constexpr int kConvSlots = 2 * kConvBandRows;                 // source rows sta
 // other workgroups hide).
 constexpr int kConvLdsBytes = 4 * (kConvertMaxWidth + 16);
 
+// The device copy of a source carries its sequence's filter in its format word (the host copy and the C ABI never see it)
+constexpr int kConvAreaBit = 0x100;
+
 struct ConvArgs {
   const sl2_frame_source* src;   // [nseq]
   const uint32_t* taps;          // [nseq][tap_stride]: col_taps column taps (out_w rounded up to 4, the rest 0), then out_h row taps
@@ -137,6 +140,7 @@ __global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvAr
   if (tr < rl) ct_first = *reinterpret_cast<const uint4*>(ctab + 4 * tq);
   const sl2_frame_source src = A.src[s];
   const int W = src.width, H = src.height, pitch = src.pitch, fmt = src.format;
+  if (fmt & kConvAreaBit) return;                                              // k_convert_area's sequence (uniform: a scalar branch)
   const uint8_t* __restrict__ base = A.raw + src.offset;
   uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
   const int wpad = (W + 15 + 15) & ~15;
@@ -207,6 +211,149 @@ __global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvAr
   }
 }
 
+// k_convert_area: SL2_RESIZE_AREA.  A workgroup owns one sequence of the area list and a band of kConvBandRows output rows, and
+// streams the band's source rows ONCE, from the first row tap to the last, through the same LDS staging (conv_stage: 16-byte
+// loads, scalar head and tail) in passes of as many rows as the LDS holds (four at the width cap, sixteen at most).  Only a
+// source row that straddles two bands is read by both.  The sum is separable and exact in any order, so the vertical pass comes
+// first: for the output row at hand every lane owns source columns and adds wy g over the staged rows of that output row into
+// colsum[x] (32 bits: at most 255 Sy), conflict-free byte reads of LDS with a uniform weight per row; a source row that
+// straddles two output rows is read for both with its two weights, an output row that straddles two passes keeps its colsum.
+// Once the output row's last source row has been staged a lane forms one output from colsum - a loop over the footprint: first
+// and last column with their weights, D times the sum between -, in 32 bits, or 64 where 511 Sx Sy does not fit (decided per
+// sequence), and rounds; every fourth lane gathers its three neighbours' bytes and stores four.  So the horizontal pass runs once per OUTPUT row, not per source row.
+// Nothing is shared between workgroups: no atomics, no order.  Outputs wider than 1024 go through in panels of 1024 columns,
+// each staging only the source columns its taps name.
+// Budget: 16.5 KB of static LDS (the linear kernel's ConvShared) plus colsum, 4 bytes per source column of the widest AREA
+// source (dynamic: 7.7 KB at 1920, 16.4 KB at the cap), and at most 80 registers: six workgroups a CU up to 2400 columns, four
+// at the cap.  Compiled: 73 registers, no scratch.  (At the linear kernel's bound of 64 registers it spilled to scratch.)
+struct AreaArgs {
+  const sl2_frame_source* src;   // [nseq of the converter]
+  const int32_t* list;           // the sequences whose filter is SL2_RESIZE_AREA
+  const uint8_t* raw;
+  uint8_t* out;
+  unsigned long long seq_stride;
+  int out_w, out_h, bands;
+};
+
+constexpr int kAreaPanel = 4 * kConvThreads;      // output columns a panel forms: four per lane
+
+// colsum[x] = (fresh ? 0 : colsum[x]) + sum_j wy[j] grey[off[j] + x] for R staged rows
+template <int R>
+__device__ __forceinline__ void area_vertical(const uint8_t* __restrict__ grey, uint32_t* __restrict__ colsum, const int (&off)[4],
+                                              const uint32_t (&wy)[4], int Wp, bool fresh) {
+  for (int x = threadIdx.x; x < Wp; x += kConvThreads) {
+    uint32_t v = fresh ? 0u : colsum[x];
+#pragma unroll
+    for (int j = 0; j < R; ++j) v += wy[j] * grey[off[j] + x];
+    colsum[x] = v;
+  }
+}
+
+template <typename ACC>
+__device__ __forceinline__ void area_band(ConvShared& sh, uint32_t* __restrict__ colsum, const AreaArgs& A, const sl2_frame_source& src, int fmt,
+                                          uint8_t* __restrict__ out, int band0, int band_end) {
+  const int tid = threadIdx.x;
+  const int W = src.width, H = src.height, pitch = src.pitch;
+  const int bpp = convert_bpp(fmt);
+  const uint32_t n = (uint32_t)W * (uint32_t)H;
+  const int y_first = convert_area_first(H, A.out_h, band0), y_last = convert_area_last(H, A.out_h, band_end - 1);
+  for (int p0 = 0; p0 < A.out_w; p0 += kAreaPanel) {
+    const int p1 = p0 + kAreaPanel < A.out_w ? p0 + kAreaPanel : A.out_w;
+    const int xs = convert_area_first(W, A.out_w, p0), xe = convert_area_last(W, A.out_w, p1 - 1);
+    const int Wp = xe - xs + 1;                                                // source columns this panel's taps name
+    const uint8_t* __restrict__ base = A.raw + src.offset + (size_t)xs * bpp;
+    const int wpad = (Wp + 15 + 15) & ~15;
+    const int fit = kConvLdsBytes / wpad;                                      // rows the LDS holds: at least 4
+    const int cap = fit < kConvSlots ? fit : kConvSlots;
+    // this lane's output columns p0 + tid and p0 + 256 + tid: their taps, once for all rows (further columns, of outputs wider
+    // than 512, are worked out again row by row)
+    AreaCol col0 = {xs, xs, 0, 0}, col1 = {xs, xs, 0, 0};
+    if (p0 + tid < p1) col0 = convert_area_col(W, A.out_w, p0 + tid);
+    if (p0 + kConvThreads + tid < p1) col1 = convert_area_col(W, A.out_w, p0 + kConvThreads + tid);
+    int cur = band0;                                                           // the output row at hand (uniform)
+    for (int c0 = y_first; c0 <= y_last; c0 += cap) {
+      const int nrows = y_last - c0 + 1 < cap ? y_last - c0 + 1 : cap;
+      const int c1 = c0 + nrows - 1;
+      if (tid < nrows) sh.row[tid] = c0 + tid;
+      if (tid == 0) sh.nslots = nrows;
+      __syncthreads();
+      switch (fmt) {
+        case SL2_PIX_GRAY8: conv_stage<SL2_PIX_GRAY8>(sh, base, pitch, Wp, wpad); break;
+        case SL2_PIX_RGB24: conv_stage<SL2_PIX_RGB24>(sh, base, pitch, Wp, wpad); break;
+        case SL2_PIX_BGR24: conv_stage<SL2_PIX_BGR24>(sh, base, pitch, Wp, wpad); break;
+        case SL2_PIX_UYVY: conv_stage<SL2_PIX_UYVY>(sh, base, pitch, Wp, wpad); break;
+        default: conv_stage<SL2_PIX_YUYV>(sh, base, pitch, Wp, wpad); break;
+      }
+      __syncthreads();
+      while (cur < band_end) {
+        const int fy = convert_area_first(H, A.out_h, cur), ly = convert_area_last(H, A.out_h, cur);
+        if (fy > c1) break;
+        const int ya = fy > c0 ? fy : c0, yb = ly < c1 ? ly : c1;
+        // vertical: colsum[x] (+)= sum_y wy g[y][x] over the staged rows of this output row, four rows at a time (their LDS
+        // offsets and weights are uniform and stay in scalars); column x stays with its lane
+        for (int y0 = ya; y0 <= yb; y0 += 4) {
+          const bool fresh = y0 == fy;                                         // nothing of this output row is in colsum yet
+          int off[4];
+          uint32_t wy[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int y = y0 + j <= yb ? y0 + j : yb, k = y - c0;
+            off[j] = k * wpad + sh.shift[k];
+            wy[j] = (uint32_t)convert_area_weight(H, A.out_h, cur, y);
+          }
+          switch (yb - y0 + 1 < 4 ? yb - y0 + 1 : 4) {
+            case 1: area_vertical<1>(sh.grey, colsum, off, wy, Wp, fresh); break;
+            case 2: area_vertical<2>(sh.grey, colsum, off, wy, Wp, fresh); break;
+            case 3: area_vertical<3>(sh.grey, colsum, off, wy, Wp, fresh); break;
+            default: area_vertical<4>(sh.grey, colsum, off, wy, Wp, fresh); break;
+          }
+        }
+        if (ly > c1) break;                                                    // the next pass brings the rest of this output row
+        __syncthreads();
+        // horizontal: a lane forms ONE output of the row from colsum (neighbouring lanes, neighbouring footprints), four
+        // neighbours are gathered into the lane whose column is a multiple of four, which stores them as one word
+        for (int cb = p0; cb < p1; cb += kConvThreads) {
+          const int dx = cb + tid;
+          uint32_t px = 0;
+          if (dx < p1) {
+            const AreaCol col = cb == p0 ? col0 : cb == p0 + kConvThreads ? col1 : convert_area_col(W, A.out_w, dx);
+            px = convert_area_round(convert_area_hsum<ACC>(colsum, xs, col, A.out_w), n);
+          }
+          const uint32_t b1 = __shfl_down(px, 1), b2 = __shfl_down(px, 2), b3 = __shfl_down(px, 3);
+          if ((tid & 3) == 0 && dx < p1) {
+            const uint32_t packed = px | (b1 << 8) | (b2 << 16) | (b3 << 24);
+            uint8_t* op = out + (size_t)cur * A.out_w + dx;
+            const int left = A.out_w - dx;
+            if (left >= 4 && ((uintptr_t)op & 3) == 0) {
+              *reinterpret_cast<uint32_t*>(op) = packed;
+            } else {
+              for (int i = 0; i < 4 && i < left; ++i) op[i] = (uint8_t)(packed >> (8 * i));
+            }
+          }
+        }
+        __syncthreads();                                                       // colsum is the next output row's from here
+        ++cur;
+      }
+      __syncthreads();      // the next pass overwrites the slots
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kConvThreads, 6) k_convert_area(const AreaArgs A) {
+  __shared__ ConvShared sh;
+  extern __shared__ uint32_t area_colsum[];      // one word per source column of a panel
+  const int li = blockIdx.x / A.bands, band = blockIdx.x - li * A.bands;
+  const int s = A.list[li];
+  const sl2_frame_source src = A.src[s];
+  if (!(src.format & kConvAreaBit) || src.width < A.out_w || src.height < A.out_h) return;      // never listed (the host refuses such sources)
+  const int fmt = src.format & (kConvAreaBit - 1);
+  uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
+  const int band0 = band * kConvBandRows;
+  const int band_end = band0 + kConvBandRows < A.out_h ? band0 + kConvBandRows : A.out_h;
+  if (convert_area_wide(src.width, src.height)) area_band<uint64_t>(sh, area_colsum, A, src, fmt, out, band0, band_end);
+  else area_band<uint32_t>(sh, area_colsum, A, src, fmt, out, band0, band_end);
+}
+
 static std::string seq_text(int seq, const char* what) {
   char buf[160];
   snprintf(buf, sizeof(buf), "sequence %d: %s", seq, what);
@@ -224,6 +371,10 @@ struct sl2_converter {
   int col_taps = 0, tap_stride = 0;
   std::vector<sl2_frame_source> src;
   std::vector<uint8_t> have;
+  std::vector<int32_t> filter;           // SL2_RESIZE_* of every sequence
+  std::vector<int32_t> area;             // the sequences with a source and SL2_RESIZE_AREA: k_convert_area's list
+  int32_t* d_area = nullptr;             // [nseq]
+  size_t area_lds = 0;                   // k_convert_area's dynamic LDS: a word per source column of the widest listed source
   std::vector<uint32_t> taps;            // host copy of one sequence's table while it is built
   sl2_frame_source* d_src = nullptr;
   uint32_t* d_taps = nullptr;
@@ -247,8 +398,9 @@ extern "C" int sl2_converter_create(int device, int nseq, int out_width, int out
   c->device = device; c->nseq = nseq; c->out_w = out_width; c->out_h = out_height;
   c->col_taps = round_up(out_width, 4);
   c->tap_stride = round_up(c->col_taps + out_height, 4);      // every table starts on a 16-byte boundary
-  c->src.resize(nseq); c->have.assign(nseq, 0); c->taps.assign(c->tap_stride, 0);
+  c->src.resize(nseq); c->have.assign(nseq, 0); c->taps.assign(c->tap_stride, 0); c->filter.assign(nseq, SL2_RESIZE_LINEAR);
   hipError_t e = hipMalloc(&c->d_src, (size_t)nseq * sizeof(sl2_frame_source));
+  if (e == hipSuccess) e = hipMalloc(&c->d_area, (size_t)nseq * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc(&c->d_taps, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->d_taps, 0, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
@@ -268,14 +420,40 @@ extern "C" void sl2_converter_destroy(sl2_converter* c) {
   if (c->done) hipEventDestroy(c->done);
   if (c->d_src) hipFree(c->d_src);
   if (c->d_taps) hipFree(c->d_taps);
+  if (c->d_area) hipFree(c->d_area);
   if (c->stage) hipFree(c->stage);
   delete c;
+}
+
+// The device copies of sequences seq0 .. seq0 + nseq - 1 (the filter rides in the format word) and the area list.  No
+// conversion is queued when this runs.
+static int converter_upload(sl2_converter* c, int seq0, int nseq) {
+  std::vector<sl2_frame_source> dev;
+  int first = -1;
+  for (int s = seq0; s < seq0 + nseq; ++s) {
+    if (!c->have[s]) {
+      if (first >= 0) { SL2_HIP(hipMemcpy(c->d_src + first, dev.data(), dev.size() * sizeof(sl2_frame_source), hipMemcpyHostToDevice)); dev.clear(); first = -1; }
+      continue;
+    }
+    if (first < 0) first = s;
+    dev.push_back(c->src[s]);
+    if (c->filter[s] == SL2_RESIZE_AREA) dev.back().format |= kConvAreaBit;
+  }
+  if (first >= 0) SL2_HIP(hipMemcpy(c->d_src + first, dev.data(), dev.size() * sizeof(sl2_frame_source), hipMemcpyHostToDevice));
+  c->area.clear();
+  int widest = 0;
+  for (int s = 0; s < c->nseq; ++s)
+    if (c->have[s] && c->filter[s] == SL2_RESIZE_AREA) { c->area.push_back(s); if (c->src[s].width > widest) widest = c->src[s].width; }
+  c->area_lds = sizeof(uint32_t) * (size_t)round_up(widest, 4);
+  if (!c->area.empty()) SL2_HIP(hipMemcpy(c->d_area, c->area.data(), c->area.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return SL2_OK;
 }
 
 extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, const sl2_frame_source* src) {
   if (!c || !src || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_set_sources: bad arguments"); return SL2_ERR_INVALID; }
   for (int i = 0; i < nseq; ++i) {
     const char* why = convert_source_fault(src[i], 0, false);
+    if (!why && c->filter[seq0 + i] == SL2_RESIZE_AREA) why = convert_area_fault(src[i], c->out_w, c->out_h);
     if (why) { set_error("sl2_converter_set_sources: " + seq_text(seq0 + i, why)); return SL2_ERR_INVALID; }
   }
   if (nseq == 0) return SL2_OK;
@@ -290,7 +468,31 @@ extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, c
     c->src[seq0 + i] = src[i];
     c->have[seq0 + i] = 1;
   }
-  SL2_HIP(hipMemcpy(c->d_src + seq0, src, (size_t)nseq * sizeof(sl2_frame_source), hipMemcpyHostToDevice));
+  return converter_upload(c, seq0, nseq);
+}
+
+extern "C" int sl2_converter_set_filters(sl2_converter* c, int seq0, int nseq, const int32_t* filters) {
+  if (!c || !filters) { set_error("sl2_converter_set_filters: bad arguments"); return SL2_ERR_INVALID; }
+  if (seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) {
+    set_error("sl2_converter_set_filters: " + seq_text(seq0 < 0 ? seq0 : c->nseq, "outside the converter"));
+    return SL2_ERR_INVALID;
+  }
+  for (int i = 0; i < nseq; ++i) {
+    const char* why = nullptr;
+    if (filters[i] != SL2_RESIZE_LINEAR && filters[i] != SL2_RESIZE_AREA) why = "unknown resize filter";
+    else if (filters[i] == SL2_RESIZE_AREA && c->have[seq0 + i]) why = convert_area_fault(c->src[seq0 + i], c->out_w, c->out_h);
+    if (why) { set_error("sl2_converter_set_filters: " + seq_text(seq0 + i, why)); return SL2_ERR_INVALID; }
+  }
+  if (nseq == 0) return SL2_OK;
+  SL2_HIP(hipSetDevice(c->device));
+  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its filters
+  for (int i = 0; i < nseq; ++i) c->filter[seq0 + i] = filters[i];
+  return converter_upload(c, seq0, nseq);
+}
+
+extern "C" int sl2_converter_get_filters(const sl2_converter* c, int seq0, int nseq, int32_t* filters) {
+  if (!c || !filters || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_get_filters: bad arguments"); return SL2_ERR_INVALID; }
+  for (int i = 0; i < nseq; ++i) filters[i] = c->filter[seq0 + i];
   return SL2_OK;
 }
 
@@ -329,7 +531,13 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
   A.src = c->d_src; A.taps = c->d_taps; A.raw = d_raw; A.out = d_frames; A.seq_stride = seq_stride;
   A.out_w = c->out_w; A.out_h = c->out_h; A.col_taps = c->col_taps; A.tap_stride = c->tap_stride;
   A.bands = (c->out_h + kConvBandRows - 1) / kConvBandRows;
-  hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
+  if ((int)c->area.size() < c->nseq) hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
+  if (!c->area.empty()) {
+    AreaArgs B;
+    B.src = c->d_src; B.list = c->d_area; B.raw = d_raw; B.out = d_frames; B.seq_stride = seq_stride;
+    B.out_w = c->out_w; B.out_h = c->out_h; B.bands = A.bands;
+    hipLaunchKernelGGL(k_convert_area, dim3((unsigned)(B.bands * (int)c->area.size())), dim3(kConvThreads), c->area_lds, st, B);
+  }
   SL2_HIP(hipGetLastError());
   SL2_HIP(hipEventRecord(c->done, st));
   c->queued = true;
@@ -349,6 +557,24 @@ extern "C" int sl2_convert_frame_host(const sl2_frame_source* src, const void* r
     set_error("sl2_convert_frame_host: a tap does not fit its packed form");
     return SL2_ERR_INVALID;
   }
+  return SL2_OK;
+}
+
+extern "C" int sl2_convert_frame_host_filtered(const sl2_frame_source* src, int filter, const void* raw, size_t raw_bytes, int out_width,
+                                               int out_height, uint8_t* out) {
+  if (filter == SL2_RESIZE_LINEAR) return sl2_convert_frame_host(src, raw, raw_bytes, out_width, out_height, out);
+  if (filter != SL2_RESIZE_AREA) { set_error("sl2_convert_frame_host_filtered: unknown resize filter"); return SL2_ERR_INVALID; }
+  if (!src || !raw || !out || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+    set_error("sl2_convert_frame_host_filtered: bad arguments");
+    return SL2_ERR_INVALID;
+  }
+  const char* why = convert_source_fault(*src, raw_bytes, true);
+  if (!why) why = convert_area_fault(*src, out_width, out_height);
+  if (why) { set_error("sl2_convert_frame_host_filtered: " + seq_text(0, why)); return SL2_ERR_INVALID; }
+  std::vector<uint8_t> grey((size_t)src->width);
+  std::vector<AreaCol> cols((size_t)out_width);
+  std::vector<uint64_t> acc((size_t)out_width);
+  convert_frame_host_area_body(*src, (const uint8_t*)raw, out_width, out_height, grey.data(), cols.data(), acc.data(), out);
   return SL2_OK;
 }
 

@@ -3,6 +3,8 @@
 // cv::resize INTER_LINEAR with 11-bit coefficients).  SL2_HD: the same source is the body of k_convert_frames
 // (sl2_convert.hip) and of sl2_convert_frame_host, and a stand-alone host program can include it (tests/frame_convert_host.cpp).
 //
+// SL2_RESIZE_AREA, the exact box average for large reductions, is at the end of the file: integers only, no tables.
+//
 // Floating point enters only through convert_taps, which the HOST evaluates (sl2_converter_set_sources uploads its tables):
 // the kernel and the host form then run the same integer arithmetic on the same tables, so their bytes agree by construction.
 #pragma once
@@ -117,6 +119,72 @@ inline bool convert_frame_host_body(const sl2_frame_source& s, const uint8_t* ra
     for (int x = 0; x < out_w; ++x)
       out[(size_t)y * out_w + x] = convert_pixel(s.format, base, s.pitch, s.width, s.height, col[x], row[y]);
   return true;
+}
+
+// ---- SL2_RESIZE_AREA: the exact box average (scenelib2_amd.h, "raw camera frames"), integers only, no tables.
+// Along an axis of S source and D output pixels, S >= D, in units of 1/D of a source pixel: output d covers [d S, (d + 1) S),
+// source i covers [i D, (i + 1) D).  All products stay below 16384 * 4096 = 2^26.
+SL2_HD int convert_area_first(int S, int D, int d) { return (int)(((uint32_t)d * (uint32_t)S) / (uint32_t)D); }
+SL2_HD int convert_area_last(int S, int D, int d) { return (int)((((uint32_t)d + 1u) * (uint32_t)S - 1u) / (uint32_t)D); }
+SL2_HD int convert_area_weight(int S, int D, int d, int i) {
+  const int hi = (i + 1) * D < (d + 1) * S ? (i + 1) * D : (d + 1) * S;
+  const int lo = i * D > d * S ? i * D : d * S;
+  return hi - lo;
+}
+
+// The taps of one output column, as the horizontal pass wants them: first and last source column, their two weights; every
+// column between them weighs D.  (One tap: x1 == x0 and w0 is its weight.)
+struct AreaCol { int x0, x1, w0, w1; };
+SL2_HD AreaCol convert_area_col(int S, int D, int d) {
+  AreaCol c;
+  c.x0 = convert_area_first(S, D, d); c.x1 = convert_area_last(S, D, d);
+  c.w0 = convert_area_weight(S, D, d, c.x0); c.w1 = convert_area_weight(S, D, d, c.x1);
+  return c;
+}
+
+// sum_x wx(d, x) g[x] over one row of values (g[0] is source column `origin`).  Of grey bytes it is at most 255 S < 2^20; of
+// column sums (sum_y wy g <= 255 Sy) it is the pixel's acc, and ACC is as wide as that needs.
+template <typename ACC, typename T>
+SL2_HD ACC convert_area_hsum(const T* g, int origin, const AreaCol& c, int D) {
+  ACC h = (ACC)c.w0 * (ACC)g[c.x0 - origin];
+  if (c.x1 > c.x0) {
+    ACC mid = 0;
+    for (int x = c.x0 + 1; x < c.x1; ++x) mid += (ACC)g[x - origin];
+    h += (ACC)D * mid + (ACC)c.w1 * (ACC)g[c.x1 - origin];
+  }
+  return h;
+}
+
+// Whether acc <= 255 n (n = Sx Sy source pixels) needs 64 bits: the rounding forms 2 acc + n
+SL2_HD bool convert_area_wide(int src_w, int src_h) { return 511ull * (uint64_t)src_w * (uint64_t)src_h > 0xffffffffull; }
+
+// floor((2 acc + n) / (2 n)): the exact mean, halves rounded up
+SL2_HD uint8_t convert_area_round(uint64_t acc, uint32_t n) { return (uint8_t)((2ull * acc + n) / (2ull * n)); }
+SL2_HD uint8_t convert_area_round(uint32_t acc, uint32_t n) { return (uint8_t)((2u * acc + n) / (2u * n)); }
+
+// Why a source cannot be reduced to out_w x out_h with the area filter (nullptr: it can)
+inline const char* convert_area_fault(const sl2_frame_source& s, int out_w, int out_h) {
+  if (s.width < out_w || s.height < out_h) return "the area filter only reduces: its source is smaller than the output";
+  return nullptr;
+}
+
+// The host form's body under SL2_RESIZE_AREA.  grey: scratch of s.width bytes; cols: out_w entries; acc: out_w entries.
+inline void convert_frame_host_area_body(const sl2_frame_source& s, const uint8_t* raw, int out_w, int out_h, uint8_t* grey, AreaCol* cols,
+                                         uint64_t* acc, uint8_t* out) {
+  const uint8_t* base = raw + s.offset;
+  const uint32_t n = (uint32_t)s.width * (uint32_t)s.height;
+  for (int x = 0; x < out_w; ++x) cols[x] = convert_area_col(s.width, out_w, x);
+  for (int dy = 0; dy < out_h; ++dy) {
+    for (int x = 0; x < out_w; ++x) acc[x] = 0;
+    const int y0 = convert_area_first(s.height, out_h, dy), y1 = convert_area_last(s.height, out_h, dy);
+    for (int y = y0; y <= y1; ++y) {
+      const uint8_t* row = base + (size_t)y * (size_t)s.pitch;
+      for (int x = 0; x < s.width; ++x) grey[x] = (uint8_t)convert_grey(s.format, row, x);
+      const uint32_t wy = (uint32_t)convert_area_weight(s.height, out_h, dy, y);
+      for (int x = 0; x < out_w; ++x) acc[x] += (uint64_t)(wy * convert_area_hsum<uint32_t>(grey, 0, cols[x], out_w));      // wy h < 2^32
+    }
+    for (int x = 0; x < out_w; ++x) out[(size_t)dy * out_w + x] = convert_area_round(acc[x], n);
+  }
 }
 
 }  // namespace sl2

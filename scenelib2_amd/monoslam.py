@@ -515,6 +515,7 @@ class MonoSLAM:
         self.marked_feature_label_ = -1             # monoslam.h:171
         self._converter = None                      # SetFrameSource: raw camera frames in front of GoOneStep
         self._frame_dev = None
+        self._frame_filter = "linear"               # SetFrameFilter
 
     # MonoSLAM::Init(config_path) — monoslam.cpp:1574-1969
     def Init(self, config_path, template_dirs=()):
@@ -584,7 +585,20 @@ class MonoSLAM:
         if self._converter is None:
             self._converter = convert.FrameConverter(self._device, 1, self.camera_["width"], self.camera_["height"])
             self._frame_dev = _lib.DeviceBuffer(self._engine.frame_bytes, self._device)
+            self._converter.set_filters([self._frame_filter])
         self._converter.set_sources([dict(width=width, height=height, pitch=pitch, format=format)])
+
+    def SetFrameFilter(self, filter):
+        """How GoOneStepRaw brings the camera's frame to the engine's size: "linear" (the reference's plain INTER_LINEAR, the
+        default) or "area", the exact box average for cameras much larger than the engine's image (convert.FILTERS or
+        SL2_RESIZE_*).  Before or after SetFrameSource; "area" with a source smaller than the engine's image is refused by
+        whichever call comes second."""
+        from . import convert
+        if (filter.lower() if isinstance(filter, str) else filter) not in list(convert.FILTERS) + list(convert.FILTERS.values()):
+            raise ValueError("MonoSLAM.SetFrameFilter: unknown filter %r" % (filter,))
+        if self._converter is not None:
+            self._converter.set_filters([filter])
+        self._frame_filter = filter
 
     def GoOneStepRaw(self, raw, save_trajectory=False, enable_mapping=False, on_device=False):
         """sl2_convert_frames, then GoOneStep on the converted device frame.  raw: the camera's bytes as a uint8 array, or with

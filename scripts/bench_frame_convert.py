@@ -11,6 +11,12 @@ Per source, timed with device events on one stream, after a warm-up, median of -
 output.  Rates are those bytes over the time.  The result is checked against sl2_convert_frame_host on a few sequences first.
 
     python scripts/bench_frame_convert.py [--batch 1024] [--reps 30] [--out profiles/frame_convert_bench.json]
+
+--filter area times k_convert_area (SL2_RESIZE_AREA) instead, from 640 x 480 UYVY, 1280 x 960 GRAY8, 1920 x 1080 YUYV and
+960 x 720 RGB24, and writes profiles/frame_convert_area_bench.json.  The area filter reads every source byte, so bytes_read is the
+whole source.  --linear-json / --linear-parent-json name the results of two --filter linear runs of the same session, this
+commit's library and its parent's (SL2_LIB_PATH): they are recorded beside the area runs, with whether every convert_ms of this
+commit lies inside the parent's spread_ms.
 """
 import argparse
 import json
@@ -27,6 +33,8 @@ from scenelib2_amd import _lib, convert  # noqa: E402
 
 SOURCES = [("640x480 UYVY", 640, 480, "uyvy"), ("640x480 RGB24", 640, 480, "rgb24"), ("960x720 RGB24", 960, 720, "rgb24"),
            ("320x240 GRAY8 (native copy)", 320, 240, "gray8")]
+AREA_SOURCES = [("640x480 UYVY", 640, 480, "uyvy"), ("1280x960 GRAY8", 1280, 960, "gray8"), ("1920x1080 YUYV", 1920, 1080, "yuyv"),
+                ("960x720 RGB24", 960, 720, "rgb24")]
 STEP_MS = 1.45          # the headline step (README) the conversion sits in front of
 
 
@@ -51,8 +59,14 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frame_convert_bench.json"))
+    ap.add_argument("--filter", choices=("linear", "area"), default="linear")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--linear-json", default=None)
+    ap.add_argument("--linear-parent-json", default=None)
     args = ap.parse_args()
+    area = args.filter == "area"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "frame_convert_area_bench.json" if area else "frame_convert_bench.json")
     if _lib.device_count() < 1:
         raise SystemExit("bench_frame_convert: no HIP device (there is no CPU fallback)")
     B, ow, oh = args.batch, 320, 240
@@ -74,7 +88,7 @@ def main():
 
     med = lambda v: float(np.median(np.asarray(v)))
     runs = []
-    for name, w, h, fmt in SOURCES:
+    for name, w, h, fmt in (AREA_SOURCES if area else SOURCES):
         bpp = convert.BYTES_PER_PIXEL[convert.FORMATS[fmt]]
         frame = w * h * bpp
         g = torch.Generator(device="cuda")
@@ -82,13 +96,17 @@ def main():
         raw = torch.randint(0, 256, (B * frame,), dtype=torch.uint8, device="cuda", generator=g)
         cv = convert.FrameConverter(0, B, ow, oh)
         cv.set_sources([dict(width=w, height=h, format=fmt, offset=s * frame) for s in range(B)])
+        if area:
+            cv.set_filters(["area"] * B)
         go = lambda: cv.convert((raw.data_ptr(), raw.numel()), out.data_ptr(), stream=stream.cuda_stream)
         go()
         stream.synchronize()
         for s in (0, B // 2, B - 1):          # the bytes are right before their time is worth anything
-            want = convert.convert_frame_host(dict(width=w, height=h, format=fmt), raw[s * frame:(s + 1) * frame].cpu().numpy(), ow, oh)
+            want = convert.convert_frame_host(dict(width=w, height=h, format=fmt), raw[s * frame:(s + 1) * frame].cpu().numpy(), ow, oh,
+                                              **(dict(filter="area") if area else {}))
             assert np.array_equal(out[s * ow * oh:(s + 1) * ow * oh].cpu().numpy().reshape(oh, ow), want), (name, s)
-        read = B * rows_read(h, oh) * w * bpp
+        src_rows = h if area else rows_read(h, oh)          # the area filter reads every source byte
+        read = B * src_rows * w * bpp
         touched = read + B * ow * oh
         conv_ms = timed(go)
         scratch_a = torch.empty(touched, dtype=torch.uint8, device="cuda")
@@ -102,7 +120,7 @@ def main():
 
         full_ms, half_ms = timed(d2d(touched)), timed(d2d(touched // 2))
         runs.append(dict(source=name, raw_bytes=B * frame, bytes_read=read, bytes_written=B * ow * oh, bytes_touched=touched,
-                         source_rows_read=rows_read(h, oh), convert_ms=med(conv_ms), convert_TBps=touched / med(conv_ms) / 1e9,
+                         source_rows_read=src_rows, convert_ms=med(conv_ms), convert_TBps=touched / med(conv_ms) / 1e9,
                          memcpy_touched_ms=med(full_ms), memcpy_same_traffic_ms=med(half_ms),
                          memcpy_same_traffic_TBps=touched / med(half_ms) / 1e9,
                          convert_over_memcpy_same_traffic=med(conv_ms) / med(half_ms),
@@ -112,11 +130,21 @@ def main():
         cv.close()
         del raw, scratch_a, scratch_b
         torch.cuda.empty_cache()
-    res = dict(commit=commit(), device=torch.cuda.get_device_name(0), batch=B, out_width=ow, out_height=oh, reps=args.reps,
+    res = dict(commit=commit(), library="another build (SL2_LIB_PATH)" if os.environ.get("SL2_LIB_PATH") else "this build", filter=args.filter,
+               device=torch.cuda.get_device_name(0), batch=B, out_width=ow, out_height=oh, reps=args.reps,
                headline_step_ms=STEP_MS, runs=runs,
                note="bytes_touched below 256 MiB (the native copy) can live in the Infinity Cache between repeats: for the "
                     "conversion and for the copy alike")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.linear_json and args.linear_parent_json:
+        this, parent = json.load(open(args.linear_json)), json.load(open(args.linear_parent_json))
+        pick = lambda r: dict(source=r["source"], convert_ms=r["convert_ms"], spread_ms=r["spread_ms"]["convert"],
+                              convert_over_memcpy_same_traffic=r["convert_over_memcpy_same_traffic"])
+        rows = [dict(this_commit=pick(a), parent=pick(b), inside_parent_spread=b["spread_ms"]["convert"][0] <= a["convert_ms"] <= b["spread_ms"]["convert"][1],
+                     at_most_parent_slowest=a["convert_ms"] <= b["spread_ms"]["convert"][1])
+                for a, b in zip(this["runs"], parent["runs"])]
+        res["linear_unchanged"] = dict(parent_library=parent.get("library"), runs=rows, all_inside=all(r["inside_parent_spread"] for r in rows),
+                                       none_slower=all(r["at_most_parent_slowest"] for r in rows))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
