@@ -496,18 +496,21 @@ __device__ __forceinline__ void finalize_body(const int b, double* __restrict__ 
   }
   __syncthreads();
   // The reference walks feature_list_ and, after erasing a feature, skips the one that follows it (Q27: the iterator is
-  // advanced before vector::erase): among the ACTIVE features in list order, del(k) = scheduled(k) && !del(k - 1) - in a
+  // advanced before vector::erase): among the features PRESENT in list order, del(k) = scheduled(k) && !del(k - 1) - in a
   // run of consecutive scheduled features the 1st, 3rd, 5th ... go.  Every thread decides its own feature from the length
   // of the scheduled run that ends just before it (runs are a few features at most); walked by one thread over LDS the
-  // list cost 6 us of a single-sequence step.
+  // list cost 6 us of a single-sequence step.  Present = ACTIVE, or PARTIAL: a partially initialised feature is an element
+  // of feature_list_ too (never scheduled: it is not measured this way), so it ends a run - it is the element that absorbs
+  // the skip after an erase.  Only a retired slot (neither bit) is not in the list.
   if (tid == 0) s_ndel = 0;
   __syncthreads();
   for (int i = tid; i < ns; i += blockDim.x) {
     const int fl = s_del[N + i];
     if ((fl & FF_ACTIVE) && (fl & FF_SCHEDULED)) {
-      int run = 0;                                   // scheduled active features directly before i (inactive slots do not count)
+      int run = 0;                                   // scheduled active features directly before i (retired slots do not count)
       for (int j = i - 1; j >= 0; --j) {
         const int fj = s_del[N + j];
+        if (fj & FF_PARTIAL) break;                  // in the list, unscheduled
         if (!(fj & FF_ACTIVE)) continue;
         if (!(fj & FF_SCHEDULED)) break;
         ++run;
