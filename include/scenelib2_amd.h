@@ -45,7 +45,8 @@ extern "C" {
  * sl2_converter_create, sl2_converter_destroy, sl2_converter_set_sources, sl2_converter_get_sources, sl2_convert_frames,
  * sl2_convert_frame_host, sl2_scale_camera (raw camera frames of any size and pixel format, in front of the step);
  * sl2_converter_set_filters, sl2_converter_get_filters, sl2_convert_frame_host_filtered (SL2_RESIZE_AREA: the exact box average
- * for cameras much larger than the engine's image). */
+ * for cameras much larger than the engine's image); sl2_snapshot_batch, sl2_snapshot_bound, SL2_SNAP_*,
+ * sl2_snapshot_header.omitted_sections (taken from reserved[]: the public state of a range of sequences in one call). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -588,7 +589,8 @@ typedef struct sl2_snapshot_header {
   int32_t steps_done;                          /* GoOneStep calls so far (low 31 bits) */
   int32_t sequence_steps;                      /* steps this SEQUENCE has taken (low 31 bits): differs from steps_done once the
                                                   sequence was loaded, copied in or reset (sl2_load_sequences below) */
-  int32_t reserved[30];
+  int32_t omitted_sections;                    /* SL2_SNAP_* bits of the sections this blob does not carry (sl2_snapshot: 0) */
+  int32_t reserved[29];
 } sl2_snapshot_header;                         /* 256 bytes */
 typedef struct sl2_partial_info {              /* FeatureInitInfo, feature_init_info.h:77-118 */
   int32_t label;                               /* fp_->label_ */
@@ -600,6 +602,49 @@ typedef struct sl2_partial_info {              /* FeatureInitInfo, feature_init_
 /* Upper bound of a blob of this engine in bytes. */
 size_t sl2_snapshot_capacity(const sl2_engine* e);
 int sl2_snapshot(sl2_engine* e, int seq, int traj_cursor, int patch_from_label, const void** blob, size_t* bytes);
+
+/* ---- the same read for a RANGE of sequences in one call (additions within SL2_API_VERSION 5) ----
+ *
+ * sl2_snapshot serves one sequence per launch and wait; a caller that publishes every sequence of a large batch after every frame
+ * pays that B times.  sl2_snapshot_batch packs the blobs of sequences seq0 .. seq0 + nseq - 1 back to back in three launches on
+ * the engine's stream (sizes, their exclusive scan, one workgroup per blob), carries only the sections asked for, and either hands
+ * the packed bytes to the host in one copy or leaves them in the caller's device memory without waiting at all.
+ *
+ *   sections  SL2_SNAP_* bits.  The header, xv_ and Pxx_ are always present (SL2_SNAP_POSE = 0 names that choice).  An omitted
+ *             section has length 0 and its off_* is the running offset (off_next - off_this == 0); header.omitted_sections =
+ *             SL2_SNAP_ALL & ~sections.  Counts that describe the SEQUENCE stay true whatever is omitted (n_features,
+ *             total_state_size, n_selected, n_partial, traj_total, next_free_label ...); counts that describe what the BLOB
+ *             carries follow the blob: without SL2_SNAP_TRAJ traj_count = 0 and traj_first = traj_total, without SL2_SNAP_PATCHES
+ *             n_patches = 0.  SL2_SNAP_COV without SL2_SNAP_FEATURES is refused: the covariance records cannot be walked without
+ *             each feature's state_size.
+ *   cursors   [nseq][2] = (traj_cursor, patch_from_label) per sequence, with sl2_snapshot's meaning; NULL = (0, 0) for all.
+ *   blobs     blob i is the sl2_snapshot blob of sequence seq0 + i restricted to `sections`; with SL2_SNAP_ALL it is byte for
+ *             byte what sl2_snapshot(e, seq0 + i, cursors[i][0], cursors[i][1], ..) returns at that point of the stream.
+ *   packing   offsets [nseq + 1]: offsets[0] = 0, offsets[i + 1] - offsets[i] = header.bytes of blob i rounded up to 16,
+ *             offsets[nseq] = the total.  Blob i starts at out + offsets[i]; the bytes between header.bytes and the next start
+ *             are zero; nothing at or beyond out + offsets[nseq] is written.
+ *
+ * Host form (on_device == 0): out, offsets and cursors are host memory of any kind; cursors is consumed before the call returns.
+ * The blobs are packed into device staging owned by the engine (sized sl2_snapshot_bound x nseq on first use, grown on demand,
+ * never in the steady state); the offset table comes back first (a small copy and the call's one wait for the device), then
+ * exactly offsets[nseq] bytes in one copy.  If offsets[nseq] > out_bytes the call returns SL2_ERR_CAPACITY with offsets filled -
+ * the caller learns the size it needs - and out untouched.
+ * Device form (on_device != 0): out (16-byte aligned), offsets and cursors are device pointers; the call is the three launches
+ * and never waits.  If the total exceeds out_bytes no blob is written (the pack kernel checks that itself); offsets is written
+ * either way.  A consumer on the engine's stream needs no other ordering.
+ * Both forms drop no captured step, change nothing in the engine, work with sequence groups (as sl2_snapshot) and treat a paused
+ * sequence like any other.
+ * Refused (SL2_ERR_INVALID, nothing queued): a null engine, out or offsets; a range outside the batch or nseq < 1; sections with
+ * bits outside SL2_SNAP_ALL; SL2_SNAP_COV without SL2_SNAP_FEATURES; a device `out` that is not 16-byte aligned; host form only:
+ * a negative traj_cursor (the device form cannot look: it takes a negative cursor as 0). */
+enum { SL2_SNAP_POSE = 0, SL2_SNAP_FEATURES = 1, SL2_SNAP_COV = 2, SL2_SNAP_SELECTION = 4, SL2_SNAP_TRAJ = 8,
+       SL2_SNAP_PARTIAL = 16, SL2_SNAP_PATCHES = 32, SL2_SNAP_ALL = 63 };
+/* Host only, no device: upper bound in bytes (a multiple of 16) of ONE blob of an engine of this shape (sl2_create's max_features;
+ * params.max_features_to_init_at_once; params.number_of_particles rounded up to 64) restricted to `sections`; with SL2_SNAP_ALL
+ * it equals sl2_snapshot_capacity of such an engine.  0 for a bad argument (a negative one, section bits outside SL2_SNAP_ALL). */
+size_t sl2_snapshot_bound(int max_features, int partial_slots, int particle_capacity, int sections);
+int sl2_snapshot_batch(sl2_engine* e, int seq0, int nseq, int sections, const int32_t* cursors,
+                       void* out, size_t out_bytes, uint64_t* offsets, int on_device);
 
 /* selected_feature_list_ (labels, selection order) and per-step counters:
  * counters[0] = number_of_visible_features_, [1] = #selected,

@@ -7,9 +7,9 @@ reference's interface plus the synthetic-input generator used by tests and bench
 """
 from . import _lib  # noqa: F401
 from .config import load_config, parse_vars_file, read_pgm  # noqa: F401
-from .monoslam import Engine, Feature, MonoSLAM  # noqa: F401
+from .monoslam import Engine, Feature, MonoSLAM, decode_snapshot  # noqa: F401
 from . import improc  # noqa: F401
 from .convert import FrameConverter, convert_frame_host, scale_camera  # noqa: F401
 
 __all__ = ["Engine", "MonoSLAM", "Feature", "load_config", "parse_vars_file", "read_pgm", "FrameConverter",
-           "convert_frame_host", "scale_camera"]
+           "convert_frame_host", "scale_camera", "decode_snapshot"]

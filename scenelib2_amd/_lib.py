@@ -67,7 +67,7 @@ class sl2_snapshot_header(C.Structure):
         "n_partial", "n_patches", "uu", "vv", "location_selected_flag", "init_feature_search_region_defined_flag")] + \
         [("init_feature_search_region", C.c_int32 * 4)] + \
         [(n, C.c_int32) for n in ("off_xv", "off_Pxx", "off_features", "off_cov", "off_selection", "off_traj", "off_partial",
-                                  "off_patches", "steps_done", "sequence_steps")] + [("reserved", C.c_int32 * 30)]
+                                  "off_patches", "steps_done", "sequence_steps", "omitted_sections")] + [("reserved", C.c_int32 * 29)]
 
 
 class sl2_partial_info(C.Structure):
@@ -100,6 +100,9 @@ class sl2_frame_source(C.Structure):
 
 SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_BGR24, SL2_PIX_UYVY, SL2_PIX_YUYV = range(5)
 SL2_RESIZE_LINEAR, SL2_RESIZE_AREA = 0, 1
+# sections of a snapshot blob (sl2_snapshot_batch); the header, xv_ and Pxx_ are always present
+SL2_SNAP_POSE, SL2_SNAP_FEATURES, SL2_SNAP_COV, SL2_SNAP_SELECTION, SL2_SNAP_TRAJ, SL2_SNAP_PARTIAL, SL2_SNAP_PATCHES = 0, 1, 2, 4, 8, 16, 32
+SL2_SNAP_ALL = 63
 
 # the same 96 bytes as a NumPy structured dtype (what Engine.step_stats returns)
 STEP_STATS_DTYPE = np.dtype([(n, np.int32) for n in ("stepped", "status_flags", "sequence_steps", "n_features", "n_partial",
@@ -137,6 +140,7 @@ EXPORTED_SYMBOLS = [
     "sl2_converter_create", "sl2_converter_destroy", "sl2_converter_set_sources", "sl2_converter_get_sources",
     "sl2_convert_frames", "sl2_convert_frame_host", "sl2_scale_camera",
     "sl2_converter_set_filters", "sl2_converter_get_filters", "sl2_convert_frame_host_filtered",
+    "sl2_snapshot_bound", "sl2_snapshot_batch",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -274,6 +278,10 @@ def _bind(L):
         L.sl2_converter_get_filters.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         L.sl2_convert_frame_host_filtered.argtypes = [C.POINTER(sl2_frame_source), C.c_int, vp, C.c_size_t, C.c_int, C.c_int, c_u8p]
         L.sl2_scale_camera.argtypes = [C.POINTER(sl2_camera), C.c_int, C.c_int, C.POINTER(sl2_camera)]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_snapshot_batch"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_snapshot_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.sl2_snapshot_bound.restype = C.c_size_t
+        L.sl2_snapshot_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, C.c_int]
     return L
 
 

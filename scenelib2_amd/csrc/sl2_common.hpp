@@ -216,6 +216,10 @@ struct sl2_engine : sl2::SeqArrays {
   void* snap_host_dev = nullptr;  // its device-side address
   size_t snap_cap = 0;            // bytes of the blob area; the completion word the kernel writes last sits right behind it
   unsigned long long snap_ticket = 0;
+  void* snapb_stage = nullptr;    // device: the packed blobs of the host form of sl2_snapshot_batch (first use: bound x nseq; grown on demand)
+  size_t snapb_stage_bytes = 0;
+  void* snapb_aux = nullptr;      // device: its offsets [B + 1] (uint64), then its cursors [B][2] (int32)
+  void* snapb_aux_host = nullptr; // pinned host memory of the same layout: the cursors on their way in, the offsets on their way out
   void* acc_dev = nullptr;        // device scratch of the get / set accessors (grown on demand)
   size_t acc_dev_bytes = 0;
   void* acc_host = nullptr;       // pinned host scratch of the same calls

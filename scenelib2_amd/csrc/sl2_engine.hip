@@ -577,6 +577,9 @@ void sl2_destroy(sl2_engine* e) {
   if (e->slots_mail) hipHostFree(e->slots_mail);
   if (e->snap_stage) hipFree(e->snap_stage);
   if (e->snap_host) hipHostFree(e->snap_host);
+  if (e->snapb_stage) hipFree(e->snapb_stage);
+  if (e->snapb_aux) hipFree(e->snapb_aux);
+  if (e->snapb_aux_host) hipHostFree(e->snapb_aux_host);
   if (e->acc_dev) hipFree(e->acc_dev);
   if (e->acc_host) hipHostFree(e->acc_host);
   for (auto& pe : e->pending) { hipEventDestroy(pe.start); hipEventDestroy(pe.stop); }

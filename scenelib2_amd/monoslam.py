@@ -20,6 +20,42 @@ from . import _lib
 from .config import load_config, read_pgm, resolve_identifier
 
 
+def decode_snapshot(raw):
+    """One snapshot blob (sl2_snapshot, or one blob of sl2_snapshot_batch; bytes-like, the blob at its start) as a dict of numpy
+    arrays / python values.  A section the blob does not carry (header.omitted_sections) decodes as empty: no features, an empty
+    selection ...; without SL2_SNAP_COV a feature's Pxy / Pyy are None."""
+    h = _lib.sl2_snapshot_header.from_buffer_copy(raw[:256])
+    assert h.magic == 0x53324C53 and 256 <= h.bytes <= len(raw)
+    has = lambda bit: not (h.omitted_sections & bit)
+    f64 = lambda off, n: np.frombuffer(raw, dtype=np.float64, count=n, offset=off).copy()
+    out = dict(header=h, xv=f64(h.off_xv, 13), Pxx=f64(h.off_Pxx, 169).reshape(13, 13), features=[], partial=[], patches={})
+    fsz = C.sizeof(_lib.sl2_feature_info)
+    cov = h.off_cov
+    for i in range(h.n_features if has(_lib.SL2_SNAP_FEATURES) else 0):
+        f = _lib.sl2_feature_info.from_buffer_copy(raw[h.off_features + i * fsz: h.off_features + (i + 1) * fsz])
+        d = f.state_size
+        Pxy = Pyy = None
+        if has(_lib.SL2_SNAP_COV):
+            Pxy = f64(cov, 13 * d).reshape(13, d)
+            Pyy = f64(cov + 13 * d * 8, d * d).reshape(d, d)
+            cov += (13 * d + d * d) * 8
+        out["features"].append(dict(info=f, label=f.label, Pxy=Pxy, Pyy=Pyy))
+    n_sel = h.n_selected if has(_lib.SL2_SNAP_SELECTION) else 0
+    out["selection"] = np.frombuffer(raw, dtype=np.int32, count=n_sel, offset=h.off_selection).copy()
+    out["trajectory"] = f64(h.off_traj, 3 * h.traj_count).reshape(-1, 3)
+    off = h.off_partial
+    for _ in range(h.n_partial if has(_lib.SL2_SNAP_PARTIAL) else 0):
+        pi = _lib.sl2_partial_info.from_buffer_copy(raw[off: off + 32])
+        parts = f64(off + 32, 12 * pi.n_particles).reshape(-1, 12)
+        out["partial"].append(dict(info=pi, particles=parts))
+        off += 32 + 96 * pi.n_particles
+    for k in range(h.n_patches):
+        o = h.off_patches + 128 * k
+        lab = int(np.frombuffer(raw, dtype=np.int32, count=1, offset=o)[0])
+        out["patches"][lab] = np.frombuffer(raw, dtype=np.uint8, count=121, offset=o + 4).reshape(11, 11).copy()
+    return out
+
+
 class Engine:
     """B independent MonoSLAM instances on one GPU (one HIP stream)."""
 
@@ -225,32 +261,50 @@ class Engine:
         blob, nbytes = _lib.vp(), C.c_size_t(0)
         self._ck(self.L.sl2_snapshot(self.h, int(seq), int(traj_cursor), int(patch_from_label), C.byref(blob), C.byref(nbytes)))
         raw = C.string_at(blob.value, nbytes.value)      # the engine's pinned buffer is reused by the next call: copy out
-        h = _lib.sl2_snapshot_header.from_buffer_copy(raw[:256])
-        assert h.magic == 0x53324C53 and h.bytes == nbytes.value
-        f64 = lambda off, n: np.frombuffer(raw, dtype=np.float64, count=n, offset=off).copy()
-        out = dict(header=h, xv=f64(h.off_xv, 13), Pxx=f64(h.off_Pxx, 169).reshape(13, 13), features=[], partial=[], patches={})
-        fsz = C.sizeof(_lib.sl2_feature_info)
-        cov = h.off_cov
-        for i in range(h.n_features):
-            f = _lib.sl2_feature_info.from_buffer_copy(raw[h.off_features + i * fsz: h.off_features + (i + 1) * fsz])
-            d = f.state_size
-            Pxy = f64(cov, 13 * d).reshape(13, d)
-            Pyy = f64(cov + 13 * d * 8, d * d).reshape(d, d)
-            cov += (13 * d + d * d) * 8
-            out["features"].append(dict(info=f, label=f.label, Pxy=Pxy, Pyy=Pyy))
-        out["selection"] = np.frombuffer(raw, dtype=np.int32, count=h.n_selected, offset=h.off_selection).copy()
-        out["trajectory"] = f64(h.off_traj, 3 * h.traj_count).reshape(-1, 3)
-        off = h.off_partial
-        for _ in range(h.n_partial):
-            pi = _lib.sl2_partial_info.from_buffer_copy(raw[off: off + 32])
-            parts = f64(off + 32, 12 * pi.n_particles).reshape(-1, 12)
-            out["partial"].append(dict(info=pi, particles=parts))
-            off += 32 + 96 * pi.n_particles
-        for k in range(h.n_patches):
-            o = h.off_patches + 128 * k
-            lab = int(np.frombuffer(raw, dtype=np.int32, count=1, offset=o)[0])
-            out["patches"][lab] = np.frombuffer(raw, dtype=np.uint8, count=121, offset=o + 4).reshape(11, 11).copy()
+        out = decode_snapshot(raw)
+        assert out["header"].bytes == nbytes.value
         return out
+
+    def snapshot_batch(self, seq0=0, nseq=None, sections=_lib.SL2_SNAP_ALL, cursors=None):
+        """sl2_snapshot_batch, host form: the blobs of sequences seq0 .. seq0 + nseq - 1 in one call (three launches, one wait,
+        one copy of exactly the packed bytes).  sections: SL2_SNAP_* bits (header, xv and Pxx always come); cursors: None or
+        [nseq][2] = (traj_cursor, patch_from_label) per sequence.  Returns (snaps, offsets): a list of the dicts Engine.snapshot
+        returns - an omitted section decodes as empty and the Pxy / Pyy of a feature as None without SL2_SNAP_COV - and the
+        uint64 [nseq + 1] offsets of the blobs in the packed buffer."""
+        raw, offsets = self.snapshot_batch_raw(seq0, nseq, sections, cursors)
+        return [decode_snapshot(raw[int(offsets[i]):int(offsets[i + 1])]) for i in range(len(offsets) - 1)], offsets
+
+    def snapshot_bound(self, sections=_lib.SL2_SNAP_ALL):
+        """sl2_snapshot_bound for this engine's shape: no blob restricted to `sections` is larger (the partial slots and the
+        particle capacity as sl2_create derives them from the parameters)."""
+        kpart = max(1, min(4, self._prm.max_features_to_init_at_once))
+        pcap = (max(1, min(1024, self._prm.number_of_particles)) + 63) // 64 * 64
+        return self.L.sl2_snapshot_bound(self.max_features, kpart, pcap, int(sections))
+
+    def snapshot_batch_raw(self, seq0=0, nseq=None, sections=_lib.SL2_SNAP_ALL, cursors=None):
+        """The packed bytes of Engine.snapshot_batch undecoded: (bytes, offsets)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        cur = None if cursors is None else np.ascontiguousarray(cursors, dtype=np.int32).reshape(nseq, 2)
+        buf = np.empty(max(self.snapshot_bound(sections), 16) * max(nseq, 1), dtype=np.uint8)
+        offsets = np.zeros(max(nseq, 0) + 1, dtype=np.uint64)
+        rc = self.L.sl2_snapshot_batch(self.h, int(seq0), nseq, int(sections), None if cur is None else cur.ctypes.data_as(_lib.vp),
+                                       buf.ctypes.data_as(_lib.vp), buf.nbytes, offsets.ctypes.data_as(_lib.vp), 0)
+        if rc == _lib.SL2_ERR_CAPACITY:      # (the shape the bound was taken for is not the engine's: ask again with the size it names)
+            buf = np.empty(int(offsets[nseq]), dtype=np.uint8)
+            rc = self.L.sl2_snapshot_batch(self.h, int(seq0), nseq, int(sections), None if cur is None else cur.ctypes.data_as(_lib.vp),
+                                           buf.ctypes.data_as(_lib.vp), buf.nbytes, offsets.ctypes.data_as(_lib.vp), 0)
+        self._ck(rc)
+        return buf[:int(offsets[nseq])].tobytes(), offsets
+
+    def snapshot_batch_device(self, out_ptr, out_bytes, offsets_ptr, seq0=0, nseq=None, sections=_lib.SL2_SNAP_ALL, cursors_ptr=None):
+        """sl2_snapshot_batch, device form, for callers that hold device memory: out_ptr (16-byte aligned, out_bytes long),
+        offsets_ptr (uint64 [nseq + 1]) and cursors_ptr (int32 [nseq][2] or None) are device pointers as integers.  Three launches
+        on the engine's stream and no wait: a consumer on that stream (Engine.stream) needs no other ordering; if the blobs need
+        more than out_bytes none is written and offsets[nseq] says how much.  Returns (out_ptr, offsets_ptr)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        self._ck(self.L.sl2_snapshot_batch(self.h, int(seq0), nseq, int(sections), _lib.vp(int(cursors_ptr)) if cursors_ptr else None,
+                                           _lib.vp(int(out_ptr)), int(out_bytes), _lib.vp(int(offsets_ptr)), 1))
+        return out_ptr, offsets_ptr
 
     def features(self, seq, include_deleted=False):
         arr = (_lib.sl2_feature_info * self.max_features)()
