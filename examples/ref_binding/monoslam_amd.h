@@ -102,6 +102,14 @@ class MonoSLAM {             // monoslam.h:69-219
     impl_.SetCameraParameters(camera_width, camera_height, fku, fkv, u0, v0, kd1, sd);
     refresh();
   }
+  // GraphicTool::DrawRawAR (graphictool.cpp:285-364) with the reference's three check boxes: out_rgb becomes the annotated frame,
+  // CV_8UC3 in R, G, B order, drawn on the device
+  void DrawRawAR(cv::Mat frame, cv::Mat& out_rgb, const bool& chk_display_2d_descriptors, const bool& chk_display_2d_search_regions,
+                 const bool& chk_display_initialisation) {
+    out_rgb.create(frame.rows, frame.cols, CV_8UC3);
+    impl_.marked_feature_label_ = marked_feature_label_;
+    impl_.DrawRawAR(view(frame), out_rgb.data, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation);
+  }
   void InitialiseFeature(cv::Mat frame) {                                  // monoslam.cpp:1211-1235: at the clicked (uu_, vv_)
     impl_.uu_ = uu_; impl_.vv_ = vv_;
     impl_.InitialiseFeature(view(frame));

@@ -46,7 +46,9 @@ extern "C" {
  * sl2_convert_frame_host, sl2_scale_camera (raw camera frames of any size and pixel format, in front of the step);
  * sl2_converter_set_filters, sl2_converter_get_filters, sl2_convert_frame_host_filtered (SL2_RESIZE_AREA: the exact box average
  * for cameras much larger than the engine's image); sl2_snapshot_batch, sl2_snapshot_bound, SL2_SNAP_*,
- * sl2_snapshot_header.omitted_sections (taken from reserved[]: the public state of a range of sequences in one call). */
+ * sl2_snapshot_header.omitted_sections (taken from reserved[]: the public state of a range of sequences in one call); sl2_overlay_items,
+ * sl2_draw_overlays, sl2_draw_items_batch, sl2_draw_items_host, sl2_overlay_item_bound, sl2_overlay_item, SL2_ITEM_*,
+ * SL2_OVERLAY_* (annotated frames: the raw-image display of GraphicTool::DrawRawAR as a draw list and a rasteriser). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -645,6 +647,110 @@ enum { SL2_SNAP_POSE = 0, SL2_SNAP_FEATURES = 1, SL2_SNAP_COV = 2, SL2_SNAP_SELE
 size_t sl2_snapshot_bound(int max_features, int partial_slots, int particle_capacity, int sections);
 int sl2_snapshot_batch(sl2_engine* e, int seq0, int nseq, int sections, const int32_t* cursors,
                        void* out, size_t out_bytes, uint64_t* offsets, int on_device);
+
+/* ---- annotated frames: the reference's raw-image display for a range of sequences (additions within SL2_API_VERSION 5) ----
+ *
+ * GraphicTool::DrawRawAR (graphic/graphictool.cpp:285-364) draws, over the camera frame, the 3-sigma search ellipse of every
+ * selected feature, each feature's 11 x 11 template where it was matched or is now predicted, the ellipses of a partially
+ * initialised feature's particles and the initialisation boxes.  Its numerical half is a DRAW LIST per sequence and a RASTERISER;
+ * both run on the device for a whole batch (k_overlay_list, k_overlay_draw: sl2_overlay.hip).
+ *
+ * THE ITEM, 64 bytes:
+ *   kind    SL2_ITEM_RING, SL2_ITEM_PATCH or SL2_ITEM_RECT
+ *   label   the feature's label; -1 for a box
+ *   a[4]    RING, PATCH: the centre (a[0], a[1]), the rest 0.  RECT: the inclusive corners x0, y0, x1, y1.
+ *   patch   PATCH: index into the call's `patches` array, entry k at patches + k * patch_stride, 121 bytes of it used
+ *           (row-major 11 x 11); else -1
+ *   rgb     the colour;  pad  0
+ *   q[4]    RING: A, B, C, rhs; else 0
+ *
+ * THE PIXEL RULES.  The output is RGB24, [image][height][width][3].  Its base is the grey frame replicated (R = G = B).  A pixel
+ * takes the colour of the LAST item in list order that covers it (painter's order: the reference's draw order).  Everything is
+ * clipped to the image.  An item of unknown kind, or with a patch index outside the array, draws nothing.
+ *   RING   inside(du, dv) := ((A*du)*du + (B*du)*dv) + (C*dv)*dv < rhs, evaluated in FP64 in exactly this order, without
+ *          contraction into fused multiply-adds, du and dv being integers converted to double.  The item covers
+ *          (a[0] + du, a[1] + dv) iff inside(du, dv) holds and not all of inside(du-1, dv), inside(du+1, dv), inside(du, dv-1),
+ *          inside(du, dv+1) hold: the one-pixel rim of the ellipse's interior.  The neighbours are evaluated arithmetically, off
+ *          the image too (an ellipse that leaves the image is not closed along the border).  A ring is drawn only if all four q
+ *          are finite and A > 0, C > 0, (4.0*A)*C - B*B > 0, rhs > 0.  (The implementation walks a bounding box; the box is
+ *          conservative - the set above is the contract, not the box.)
+ *   PATCH  with du = x - a[0], dv = y - a[1]: |du| <= 5 and |dv| <= 5: grey patch[(dv+5)*11 + du+5] as R = G = B;
+ *          max(|du|, |dv|) == 6: rgb (a frame around the template).
+ *   RECT   the one-pixel outline of [x0, x1] x [y0, y1].  An inverted rectangle (x0 > x1 or y0 > y1) draws nothing.
+ *   Coordinates are meant to lie within +-32767 (what the list below produces).  Beyond +-2^20 a rectangle's corner counts as
+ *   +-2^20 (it clips the same) and a ring or patch centred there draws nothing.  Images are at most 32768 pixels a side.
+ *
+ * THE DRAW LIST OF A SEQUENCE, in feature_list_ order (DrawRawAR's loop), from the sequence's CURRENT state.  `layers` holds the
+ * example's three checkboxes as bits.  Colour (SetFeatureColour, graphictool.cpp:1344): label == marked: green (0,255,0); else
+ * selected and matched: red (255,0,0); selected, not matched: blue (0,0,255); otherwise yellow (255,255,0).
+ *   fully initialised live feature: zeroedyi and the projection hi are taken from the current xv_, y_ and the sequence's own
+ *     camera (sl2_set_cameras).  Only if zeroedyi[2] > 0 (the reference's test against features behind the camera):
+ *       SL2_OVERLAY_SEARCH_REGIONS and selected_flag_: a RING at (int(h_[0] + 0.5), int(h_[1] + 0.5)) - the stored h_ and S_ of
+ *         the last measurement, C truncation as in elliptical_search - with A = S11, B = -(S01 + S10), C = S00,
+ *         rhs = 9.0 * (S00*S11 - S01*S10): the 3-sigma ellipse nu^T S^-1 nu < 9 multiplied through by det S, no division.
+ *       SL2_OVERLAY_DESCRIPTORS: a PATCH at (int(x + 0.5), int(y + 0.5)), (x, y) = z_ if selected and matched, else hi.
+ *   partially initialised feature, SL2_OVERLAY_SEARCH_REGIONS: the reference's counter (graphictool.cpp:716-733) picks the
+ *     particles: step = max(n / 10, 1), particle k (from 0) is drawn iff (k + 1) % step == 0 - at most 19 of them.  Each is a
+ *     yellow RING (green if the label is the marked one) at int(m_h_ + 0.5) with A = m_SInv00, B = 2.0 * m_SInv01, C = m_SInv11, rhs = 9.0.  These are the
+ *     records of the last MatchPartiallyInitialisedFeatures: the reference recomputes h and S of every drawn particle from the
+ *     updated state; this list draws what was SEARCHED.  A particle never predicted carries zeros: its ring is listed and draws
+ *     nothing.
+ *   SL2_OVERLAY_INITIALISATION, after the features: location_selected_flag_: a green RECT (uu-6, vv-6, uu+6, vv+6);
+ *     init_feature_search_region_defined_flag_: a green RECT of the region's four numbers (ustart, vstart, ufinish, vfinish).
+ *   A centre that is not finite, or that rounds outside +-32767, omits its item.  Deleted and retired slots yield nothing.
+ *   An item's `patch` is (seq - seq0) * max_features + k, k = the feature's index in sl2_get_features order: a client that fills
+ *   patches[nseq * max_features][patch_stride] from sl2_get_feature_patch can hand list and array to sl2_draw_items_batch.
+ *   No list is longer than sl2_overlay_item_bound(max_features, partial_slots) = 2 max_features + 19 partial_slots + 2.
+ *
+ * sl2_overlay_items   the lists themselves, for clients that draw vectors: list i (sequence seq0 + i) at items + i * item_stride
+ *   (item_stride in items, at least the bound), its length in counts[i].  marked: [nseq] labels, NULL = none marked.
+ *   on_device == 0: items, counts, marked are host memory; engine-owned staging (grown on first use), one wait.
+ *   on_device != 0: all three are device pointers (items 8-byte aligned); one launch on the engine's stream, no wait.
+ * sl2_draw_overlays   list and draw in one call with no host round trip; the templates are the engine's own.  frames: one grey
+ *   image per sequence of the range at frames + i * seq_stride (host or device: frames_on_device), engine geometry.  out: RGB24
+ *   image i at out + i * out_stride (bytes).  out_on_device == 0: out and marked are host memory; the images are drawn into
+ *   engine-owned staging that grows on first use, then one wait and one copy of exactly 3 width height bytes per image.
+ *   out_on_device != 0: out and marked are device pointers; two launches on the engine's stream.  With device frames the call
+ *   never waits for the device.  With HOST frames (frames_on_device == 0) it waits once, before the launches, until the frames
+ *   have been copied into staging - the stream's earlier work included - so that the caller's buffer, which may be pageable, is
+ *   free when the call returns; what is drawn afterwards is still not waited for.  Hand over device frames to avoid the wait.
+ * Both drop no captured step, change nothing in the engine, do not consult the active mask (a paused sequence is drawn like any
+ * other) and work with sequence groups (sl2_set_groups > 1).
+ * sl2_draw_items_batch   the stateless rasteriser: `nimages` frames and lists, any mix of host and device residency (patches
+ *   lives where the lists live).  Everything on the device: one launch on `stream`, no wait.  Otherwise host inputs are copied
+ *   to temporaries and the call waits for `stream` before it returns; that form allocates and frees its temporaries on every
+ *   call (tests, tools, a frame now and then).  Only the all-device form is meant for per-frame use.
+ * sl2_draw_items_host    the plain C++ form of one image, built from the same source as the kernel: byte for byte its output.
+ * Refused (SL2_ERR_INVALID, nothing queued, sl2_last_error() names the sequence or image, or the range where all share the fault): null pointers, ranges outside the
+ * batch, nseq or nimages < 1, width or height outside 1 .. 32768, layers with unknown bits, out_stride < 3 width height,
+ * seq_stride < width height, item_stride below the bound (sl2_overlay_items) or negative, patch_stride < 121 with npatches > 0;
+ * in the HOST-resident lists of sl2_draw_items_batch counts[i] < 0 or > item_stride, an item of unknown kind, a PATCH whose index
+ * is outside the array.  A device-resident list cannot be looked at: the kernel clamps its count to 0 .. item_stride and skips
+ * such items (they draw nothing, as the pixel rules say, and so they do in sl2_draw_items_host, which is the kernel's arithmetic
+ * on the host); every loop is bounded by the clamped count and the image. */
+enum { SL2_ITEM_RING = 1, SL2_ITEM_PATCH = 2, SL2_ITEM_RECT = 3 };
+enum { SL2_OVERLAY_SEARCH_REGIONS = 1, SL2_OVERLAY_DESCRIPTORS = 2, SL2_OVERLAY_INITIALISATION = 4, SL2_OVERLAY_ALL = 7 };
+typedef struct sl2_overlay_item {
+  int32_t kind;
+  int32_t label;
+  int32_t a[4];
+  int32_t patch;
+  uint8_t rgb[3];
+  uint8_t pad;
+  double q[4];
+} sl2_overlay_item;                            /* 64 bytes */
+/* Host only, no device: the longest list of a sequence of an engine of this shape; 0 for a negative argument. */
+size_t sl2_overlay_item_bound(int max_features, int partial_slots);
+int sl2_overlay_items(sl2_engine* e, int seq0, int nseq, int layers, const int32_t* marked /* [nseq] labels, NULL = none */,
+                      sl2_overlay_item* items, int item_stride, int32_t* counts, int on_device);
+int sl2_draw_items_batch(int device, void* stream, const uint8_t* frames, int frames_on_device, int nimages, int width, int height,
+                         size_t seq_stride, const sl2_overlay_item* items, int item_stride, const int32_t* counts,
+                         int items_on_device, const uint8_t* patches, size_t patch_stride, int npatches, uint8_t* out,
+                         size_t out_stride, int out_on_device);
+int sl2_draw_overlays(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device,
+                      int layers, const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device);
+int sl2_draw_items_host(const uint8_t* frame, int width, int height, const sl2_overlay_item* items, int count,
+                        const uint8_t* patches, size_t patch_stride, int npatches, uint8_t* out);
 
 /* selected_feature_list_ (labels, selection order) and per-step counters:
  * counters[0] = number_of_visible_features_, [1] = #selected,

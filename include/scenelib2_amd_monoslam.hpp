@@ -258,6 +258,21 @@ class MonoSLAM {
     return GoOneStep(frame, save_trajectory, enable_mapping);      // (its read-back waits for the stream: the copy of `raw` is done)
   }
 
+  // GraphicTool::DrawRawAR (graphic/graphictool.cpp:285-364) without OpenGL: the frame annotated with the search ellipses, the
+  // templates, the particle ellipses of a partially initialised feature and the initialisation boxes, drawn on the device
+  // (sl2_draw_overlays) into out_rgb, RGB24 [height][width][3] in host memory.  The three arguments are the example's check
+  // boxes; marked_feature_label_ is drawn green.  From the state as the last call left it.
+  void DrawRawAR(const Frame& frame, uint8_t* out_rgb, bool chk_display_2d_descriptors, bool chk_display_2d_search_regions,
+                 bool chk_display_initialisation) {
+    if (!eng_ || !frame.data || !out_rgb || frame.cols != camera_->width_ || frame.rows != camera_->height_)
+      throw std::runtime_error("MonoSLAM::DrawRawAR: frame does not match the camera");
+    const int layers = (chk_display_2d_search_regions ? SL2_OVERLAY_SEARCH_REGIONS : 0) | (chk_display_2d_descriptors ? SL2_OVERLAY_DESCRIPTORS : 0) |
+                       (chk_display_initialisation ? SL2_OVERLAY_INITIALISATION : 0);
+    const int32_t marked = marked_feature_label_;
+    const size_t px = (size_t)frame.cols * frame.rows;
+    check(sl2_draw_overlays(eng_, 0, 1, frame.data, px, frame.on_device ? 1 : 0, layers, &marked, out_rgb, 3 * px, 0), "sl2_draw_overlays");
+  }
+
   // The seams of GoOneStep, callable one by one like the reference's public members (monoslam.cpp:118-177; kalman.h:51-52
   // through the Kalman struct below).  With enable_mapping = false, predict -> auto_select_n_features ->
   // make_measurements -> update -> finish_step is GoOneStep.

@@ -110,6 +110,13 @@ STEP_STATS_DTYPE = np.dtype([(n, np.int32) for n in ("stepped", "status_flags", 
                             [(n, np.float64) for n in ("nis", "log_det_S", "min_pivot", "max_pivot", "worst_feature_d2",
                                                        "position_var")] + [("reserved", np.int32, (2,))])
 
+# annotated frames (sl2_overlay_items, sl2_draw_items_batch ...): item kinds, layer bits and the 64-byte item
+SL2_ITEM_RING, SL2_ITEM_PATCH, SL2_ITEM_RECT = 1, 2, 3
+SL2_OVERLAY_SEARCH_REGIONS, SL2_OVERLAY_DESCRIPTORS, SL2_OVERLAY_INITIALISATION, SL2_OVERLAY_ALL = 1, 2, 4, 7
+OVERLAY_ITEM_DTYPE = np.dtype([("kind", np.int32), ("label", np.int32), ("a", np.int32, (4,)), ("patch", np.int32),
+                               ("rgb", np.uint8, (3,)), ("pad", np.uint8), ("q", np.float64, (4,))])
+assert OVERLAY_ITEM_DTYPE.itemsize == 64
+
 SL2_BLOB_MAGIC = 0x51324C53
 SL2_BLOB_SLOT_ARRAYS = 22
 SL2_BLOB_LAYOUT_OFFSETS = 7 + SL2_BLOB_SLOT_ARRAYS
@@ -141,6 +148,7 @@ EXPORTED_SYMBOLS = [
     "sl2_convert_frames", "sl2_convert_frame_host", "sl2_scale_camera",
     "sl2_converter_set_filters", "sl2_converter_get_filters", "sl2_convert_frame_host_filtered",
     "sl2_snapshot_bound", "sl2_snapshot_batch",
+    "sl2_overlay_item_bound", "sl2_overlay_items", "sl2_draw_items_batch", "sl2_draw_overlays", "sl2_draw_items_host",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -282,6 +290,14 @@ def _bind(L):
         L.sl2_snapshot_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.sl2_snapshot_bound.restype = C.c_size_t
         L.sl2_snapshot_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp, C.c_int]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_draw_overlays"):      # (an older build under test, scripts/ab_libs.sh)
+        L.sl2_overlay_item_bound.argtypes = [C.c_int, C.c_int]
+        L.sl2_overlay_item_bound.restype = C.c_size_t
+        L.sl2_overlay_items.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int]
+        L.sl2_draw_items_batch.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_int,
+                                           vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int]
+        L.sl2_draw_overlays.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int]
+        L.sl2_draw_items_host.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_size_t, C.c_int, vp]
     return L
 
 

@@ -220,6 +220,10 @@ struct sl2_engine : sl2::SeqArrays {
   size_t snapb_stage_bytes = 0;
   void* snapb_aux = nullptr;      // device: its offsets [B + 1] (uint64), then its cursors [B][2] (int32)
   void* snapb_aux_host = nullptr; // pinned host memory of the same layout: the cursors on their way in, the offsets on their way out
+  void* ovl_lists = nullptr;      // device: the draw lists of sl2_overlay_items' host form and of sl2_draw_overlays: items, counts, marked labels (first use; grown on demand)
+  size_t ovl_lists_bytes = 0;
+  void* ovl_images = nullptr;     // device: host frames on their way in and RGB images on their way out of sl2_draw_overlays (first use; grown on demand)
+  size_t ovl_images_bytes = 0;
   void* acc_dev = nullptr;        // device scratch of the get / set accessors (grown on demand)
   size_t acc_dev_bytes = 0;
   void* acc_host = nullptr;       // pinned host scratch of the same calls

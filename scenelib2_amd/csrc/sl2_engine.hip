@@ -580,6 +580,8 @@ void sl2_destroy(sl2_engine* e) {
   if (e->snapb_stage) hipFree(e->snapb_stage);
   if (e->snapb_aux) hipFree(e->snapb_aux);
   if (e->snapb_aux_host) hipHostFree(e->snapb_aux_host);
+  if (e->ovl_lists) hipFree(e->ovl_lists);
+  if (e->ovl_images) hipFree(e->ovl_images);
   if (e->acc_dev) hipFree(e->acc_dev);
   if (e->acc_host) hipHostFree(e->acc_host);
   for (auto& pe : e->pending) { hipEventDestroy(pe.start); hipEventDestroy(pe.stop); }

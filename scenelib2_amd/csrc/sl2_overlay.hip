@@ -1,0 +1,447 @@
+// Annotated frames (include/scenelib2_amd.h, "annotated frames"): the numerical half of
+// GraphicTool::DrawRawAR (graphic/graphictool.cpp:285-364) for a range of sequences - a draw list per sequence (k_overlay_list)
+// and a rasteriser (k_overlay_draw).  Two stream-ordered launches; no workgroup waits for another.  The pixel rules are
+// sl2_overlay_dev.hpp's, shared with sl2_draw_items_host.
+#include "sl2_common.hpp"
+#include "sl2_overlay_dev.hpp"
+
+namespace sl2 {
+
+static_assert(sizeof(sl2_overlay_item) == 64, "sl2_overlay_item is 64 bytes");
+static_assert(sizeof(OverlayPrep) == 72, "OverlayPrep");
+
+constexpr int kListThreads = 256;
+constexpr int kListSeqs = kListThreads / 64;      // sequences per workgroup of k_overlay_list, a wavefront each
+constexpr int kDrawThreads = 256;
+constexpr int kTileW = 64, kTileH = 16;           // a thread owns 4 consecutive pixels of a row
+constexpr int kDrawChunk = kDrawThreads;          // items culled and staged per round, one per thread: 18 KB of LDS
+constexpr int kMaxParticlesDrawn = 19;            // what the reference's counter lets through at most
+
+// ---- 1. the draw list of sequence seq0 + i: one wavefront, a lane per slot, 64 slots a round.  Every lane counts its slot's
+// items, a shuffle scan places them in slot order, then every lane writes its own.  Nothing is stored at or beyond item_stride.
+// patch_mode 0: an item's patch is i * N + the feature's index in feature_list_ order (the public list); 1: seq * N + slot, the
+// index into the engine's own template array (sl2_draw_overlays).
+__global__ void __launch_bounds__(kListThreads) k_overlay_list(const SeqArrays S, int seq0, int nseq, int N, int ld, int pcap, int kpart, int width,
+                                                               int height, int layers, int patch_mode, const int32_t* __restrict__ marked,
+                                                               sl2_overlay_item* __restrict__ items, int item_stride, int32_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * kListSeqs + (threadIdx.x >> 6);
+  if (i >= nseq) return;                               // (a whole wavefront)
+  const int seq = seq0 + i;
+  const size_t o = (size_t)seq * N;
+  const int ns = min(max(S.n_slots[seq], 0), N);
+  const CameraParams cam = load_cam(S.seq_cam, seq, width, height);
+  const double* xb = S.x + (size_t)seq * ld;
+  const int* psb = S.ps_i + (size_t)seq * kpart * kPsInts;
+  const int mark = marked ? marked[i] : -1;
+  sl2_overlay_item* list = items + (size_t)i * item_stride;
+  double xp[7];
+  for (int k = 0; k < 7; ++k) xp[k] = xb[k];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int total = 0, nlive = 0;                            // wave-uniform
+  for (int base = 0; base < ns; base += 64) {
+    const int f = base + lane;
+    const int fl = f < ns ? S.f_flags[o + f] : 0;
+    const bool part = (fl & FF_PARTIAL) != 0, full = !part && (fl & FF_ACTIVE) != 0;
+    const unsigned long long m_live = __ballot(part || full);
+    const int li = nlive + __popcll(m_live & below);
+    const int label = (part || full) ? S.f_label[o + f] : -1;
+    int c = 0;
+    bool has_ring = false, has_patch = false;      // (two named records, not an array: an index known only at run time would put them in scratch)
+    sl2_overlay_item it_ring = overlay_blank_item(SL2_ITEM_RING, label), it_patch = overlay_blank_item(SL2_ITEM_PATCH, label);
+    // the partial slot whose label sits in feature slot f, and its drawn particles
+    int ks = -1, np = 0, step = 1;
+    const double* pp = nullptr;
+    if (full) {
+      double zeroed[3], hi[2], Hx[14], Hy[6], Rn;
+      measurement_model(cam, xp, xb + 13 + 3 * f, zeroed, hi, Hx, Hy, &Rn);
+      if (zeroed[2] > 0.0) {
+        const bool sel = (fl & FF_SELECTED) != 0, ok = (fl & FF_SUCCESS) != 0;
+        uint8_t rgb[3];
+        overlay_colour(label == mark, sel, ok, rgb);
+        int cx, cy;
+        if ((layers & SL2_OVERLAY_SEARCH_REGIONS) && sel && overlay_round(S.f_h[(o + f) * 2], &cx) && overlay_round(S.f_h[(o + f) * 2 + 1], &cy)) {
+          const double* Sf = S.f_S + (o + f) * 4;
+          sl2_overlay_item& r = it_ring;
+          r.a[0] = cx; r.a[1] = cy;
+          r.rgb[0] = rgb[0]; r.rgb[1] = rgb[1]; r.rgb[2] = rgb[2];
+          r.q[0] = Sf[3]; r.q[1] = -(Sf[1] + Sf[2]); r.q[2] = Sf[0]; r.q[3] = 9.0 * (Sf[0] * Sf[3] - Sf[1] * Sf[2]);
+          has_ring = true;
+        }
+        const double px = (sel && ok) ? S.f_z[(o + f) * 2] : hi[0], py = (sel && ok) ? S.f_z[(o + f) * 2 + 1] : hi[1];
+        if ((layers & SL2_OVERLAY_DESCRIPTORS) && overlay_round(px, &cx) && overlay_round(py, &cy)) {
+          sl2_overlay_item& r = it_patch;
+          r.a[0] = cx; r.a[1] = cy;
+          r.rgb[0] = rgb[0]; r.rgb[1] = rgb[1]; r.rgb[2] = rgb[2];
+          r.patch = patch_mode ? seq * N + f : i * N + li;
+          has_patch = true;
+        }
+        c = (has_ring ? 1 : 0) + (has_patch ? 1 : 0);
+      }
+    } else if (part && (layers & SL2_OVERLAY_SEARCH_REGIONS)) {
+      for (int k = 0; k < kpart; ++k)
+        if (psb[k * kPsInts + kPsActive] && psb[k * kPsInts + kPsLabel] == f) ks = k;
+      if (ks >= 0) {
+        np = min(max(psb[ks * kPsInts + kPsNp], 0), pcap);
+        step = overlay_particle_step(np);
+        pp = S.particles + ((size_t)seq * kpart + ks) * pcap * kParticleDoubles;
+        int cx, cy;
+        for (int k = 0; k < np; ++k)
+          if ((k + 1) % step == 0 && overlay_round(pp[(size_t)k * kParticleDoubles + 3], &cx) && overlay_round(pp[(size_t)k * kParticleDoubles + 4], &cy)) ++c;
+        if (c > kMaxParticlesDrawn) c = kMaxParticlesDrawn;      // (cannot happen: n < 20 passes n, n >= 20 passes n / (n / 10) <= 19)
+      }
+    }
+    int incl = c;
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+    int at = total + incl - c;
+    if (full) {
+      if (has_ring && at < item_stride) list[at] = it_ring;
+      if (has_ring) ++at;
+      if (has_patch && at < item_stride) list[at] = it_patch;
+    } else if (c > 0) {
+      uint8_t rgb[3];
+      overlay_colour(label == mark, false, false, rgb);
+      int cx, cy, written = 0;
+      for (int k = 0; k < np && written < c; ++k)
+        if ((k + 1) % step == 0 && overlay_round(pp[(size_t)k * kParticleDoubles + 3], &cx) && overlay_round(pp[(size_t)k * kParticleDoubles + 4], &cy)) {
+          const double* p = pp + (size_t)k * kParticleDoubles;
+          sl2_overlay_item r = overlay_blank_item(SL2_ITEM_RING, label);
+          r.a[0] = cx; r.a[1] = cy;
+          r.rgb[0] = rgb[0]; r.rgb[1] = rgb[1]; r.rgb[2] = rgb[2];
+          r.q[0] = p[7]; r.q[1] = 2.0 * p[8]; r.q[2] = p[9]; r.q[3] = 9.0;
+          if (at + written < item_stride) list[at + written] = r;
+          ++written;
+        }
+    }
+    total += __shfl(incl, 63);
+    nlive += __popcll(m_live);
+  }
+  if (lane != 0) return;
+  if (layers & SL2_OVERLAY_INITIALISATION) {
+    const int* pi = S.part_i + (size_t)seq * kPartInts;
+    if (pi[kPartCreated]) {
+      sl2_overlay_item r = overlay_blank_item(SL2_ITEM_RECT, -1);
+      r.a[0] = pi[kPartUU] - 6; r.a[1] = pi[kPartVV] - 6; r.a[2] = pi[kPartUU] + 6; r.a[3] = pi[kPartVV] + 6;
+      r.rgb[1] = 255;
+      if (total < item_stride) list[total] = r;
+      ++total;
+    }
+    if (pi[kPartRegionValid]) {
+      sl2_overlay_item r = overlay_blank_item(SL2_ITEM_RECT, -1);
+      for (int k = 0; k < 4; ++k) r.a[k] = pi[kPartRegion + k];
+      r.rgb[1] = 255;
+      if (total < item_stride) list[total] = r;
+      ++total;
+    }
+  }
+  counts[i] = total < item_stride ? total : item_stride;
+}
+
+// ---- 2. the rasteriser: a workgroup per (image, tile of 64 x 16 pixels), a thread per 4 consecutive pixels of a row.  The list
+// is walked in rounds of kDrawChunk items: every thread prepares one, the items whose conservative box meets the TILE are staged
+// in list order into LDS (so what a round skips is the same for the whole workgroup), then every thread walks the staged items
+// for its pixels and keeps the last hit.  Later rounds overwrite earlier ones: painter's order.
+struct DrawArgs {
+  const uint8_t* frames; size_t seq_stride;
+  int width, height, tiles_x, tiles;
+  const sl2_overlay_item* items; int item_stride; const int32_t* counts;
+  const uint8_t* patches; size_t patch_stride; int npatches;
+  uint8_t* out; size_t out_stride;
+  int dword_out;      // every row of every image starts on a 4-byte boundary: a thread's 12 bytes go out as three dwords
+};
+
+__global__ void __launch_bounds__(kDrawThreads) k_overlay_draw(const DrawArgs A) {
+  __shared__ OverlayPrep s_prep[kDrawChunk];
+  __shared__ int s_wave[kDrawThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int img = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
+  const int x0 = (tile % A.tiles_x) * kTileW, y0 = (tile / A.tiles_x) * kTileH;
+  const int x1 = min(x0 + kTileW - 1, A.width - 1), y1 = min(y0 + kTileH - 1, A.height - 1);
+  const int px = x0 + (tid & 15) * 4, py = y0 + (tid >> 4);
+  const bool row_ok = py < A.height && px < A.width;
+  const uint8_t* frame = A.frames + (size_t)img * A.seq_stride;
+  uint32_t c[4];
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t g = (row_ok && px + j < A.width) ? frame[(size_t)py * A.width + px + j] : 0u;
+    c[j] = g | (g << 8) | (g << 16);
+  }
+  const int count = min(max(A.counts[img], 0), A.item_stride);
+  const sl2_overlay_item* list = A.items + (size_t)img * A.item_stride;
+  for (int base = 0; base < count; base += kDrawChunk) {
+    const int k = base + tid;
+    OverlayPrep p;
+    bool keep = false;
+    if (k < count) keep = overlay_prepare(list[k], A.npatches, &p) && overlay_box_meets(p, x0, y0, x1, y1);
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) s_wave[wv] = __popcll(m);
+    __syncthreads();
+    int off = __popcll(m & ((1ull << lane) - 1ull)), n = 0;
+    for (int w = 0; w < kDrawThreads / 64; ++w) { if (w < wv) off += s_wave[w]; n += s_wave[w]; }
+    if (keep) s_prep[off] = p;
+    __syncthreads();
+    if (row_ok)
+      for (int q = 0; q < n; ++q) {
+        const OverlayPrep& P = s_prep[q];
+        if (py < P.by0 || py > P.by1 || px > P.bx1 || px + 3 < P.bx0) continue;
+        for (int j = 0; j < 4; ++j) {
+          uint32_t h;
+          if (px + j < A.width && overlay_hit(P, A.patches, A.patch_stride, px + j, py, &h)) c[j] = h;
+        }
+      }
+    __syncthreads();      // (the next round overwrites s_prep and s_wave)
+  }
+  if (!row_ok) return;
+  uint8_t* o = A.out + (size_t)img * A.out_stride + ((size_t)py * A.width + px) * 3;
+  if (A.dword_out && px + 3 < A.width) {
+    uint32_t* o4 = reinterpret_cast<uint32_t*>(o);      // px is a multiple of 4, so 3 px is one of 4 too
+    o4[0] = c[0] | (c[1] << 24);
+    o4[1] = (c[1] >> 8) | (c[2] << 16);
+    o4[2] = (c[2] >> 16) | (c[3] << 8);
+  } else {
+    for (int j = 0; j < 4; ++j)
+      if (px + j < A.width) { o[3 * j] = (uint8_t)c[j]; o[3 * j + 1] = (uint8_t)(c[j] >> 8); o[3 * j + 2] = (uint8_t)(c[j] >> 16); }
+  }
+}
+
+static std::string at_text(const char* fn, const char* noun, int idx, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "%s: %s %d: %s", fn, noun, idx, what);
+  return buf;
+}
+// a fault that every sequence or image of the call shares (a stride, the geometry, a pointer): the range is named
+static std::string range_text(const char* fn, const char* noun, int first, int count, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "%s: %s %d .. %d: %s", fn, noun, first, first + (count > 0 ? count : 1) - 1, what);
+  return buf;
+}
+// why a range of sequences cannot be served (nullptr: it can)
+static const char* engine_range_fault(const sl2_engine* e, int seq0, int nseq, int layers) {
+  if (!e) return "null engine";
+  if (nseq < 1) return "nseq below 1";
+  if (seq0 < 0 || seq0 > e->B - nseq) return "outside the batch";
+  if (layers & ~SL2_OVERLAY_ALL) return "layers with bits outside SL2_OVERLAY_ALL";
+  return nullptr;
+}
+
+static int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, int nimages, int width, int height,
+                       const sl2_overlay_item* d_items, int item_stride, const int32_t* d_counts, const uint8_t* d_patches, size_t patch_stride,
+                       int npatches, uint8_t* d_out, size_t out_stride) {
+  DrawArgs A;
+  A.frames = d_frames; A.seq_stride = seq_stride; A.width = width; A.height = height;
+  A.tiles_x = (width + kTileW - 1) / kTileW;
+  A.tiles = A.tiles_x * ((height + kTileH - 1) / kTileH);
+  A.items = d_items; A.item_stride = item_stride; A.counts = d_counts;
+  A.patches = d_patches; A.patch_stride = patch_stride; A.npatches = d_patches ? npatches : 0;
+  A.out = d_out; A.out_stride = out_stride;
+  A.dword_out = ((3 * (size_t)width) % 4 == 0 && (uintptr_t)d_out % 4 == 0 && out_stride % 4 == 0) ? 1 : 0;
+  hipLaunchKernelGGL(k_overlay_draw, dim3((unsigned)(nimages * A.tiles)), dim3(kDrawThreads), 0, stream, A);
+  SL2_HIP(hipGetLastError());
+  return SL2_OK;
+}
+
+// what every drawing call checks of its image geometry (nullptr: fine)
+static const char* geometry_fault(int nimages, int width, int height, size_t seq_stride, size_t out_stride) {
+  if (nimages < 1) return "no images";
+  if (width < 1 || height < 1 || width > kOverlayMaxSide || height > kOverlayMaxSide) return "width or height outside 1 .. 32768";
+  if (seq_stride < (size_t)width * (size_t)height) return "seq_stride below width * height";
+  if (out_stride < 3 * (size_t)width * (size_t)height) return "out_stride below 3 * width * height";
+  const long long tiles = (long long)((width + kTileW - 1) / kTileW) * ((height + kTileH - 1) / kTileH);
+  if (tiles * nimages > 0x7fffffffll) return "more tiles than one launch takes";
+  return nullptr;
+}
+
+static int grow_device(void** p, size_t* have, size_t need) {
+  if (need <= *have) return SL2_OK;
+  if (*p) { SL2_HIP(hipFree(*p)); *p = nullptr; *have = 0; }
+  SL2_HIP(hipMalloc(p, need));
+  *have = need;
+  return SL2_OK;
+}
+
+static int launch_list(sl2_engine* e, int seq0, int nseq, int layers, int patch_mode, const int32_t* d_marked, sl2_overlay_item* d_items, int item_stride,
+                       int32_t* d_counts) {
+  // (the root's arrays on the engine's stream, like sl2_snapshot_batch: the groups' streams join it at the end of every stepping call)
+  LaunchScope ls(e, "k_overlay_list");
+  hipLaunchKernelGGL(k_overlay_list, dim3((nseq + kListSeqs - 1) / kListSeqs), dim3(kListThreads), 0, e->stream, seq_arrays(e), seq0, nseq, e->N, e->ld,
+                     e->pcap, e->kpart, e->cam.width, e->cam.height, layers, patch_mode, d_marked, d_items, item_stride, d_counts);
+  SL2_HIP(hipGetLastError());
+  return SL2_OK;
+}
+
+// engine-owned list staging: items [nseq][stride], then counts [nseq], then marked [nseq]
+struct ListStage { sl2_overlay_item* items; int32_t* counts; int32_t* marked; };
+static int list_stage(sl2_engine* e, int nseq, size_t stride, ListStage* st) {
+  const size_t item_bytes = sizeof(sl2_overlay_item) * stride * (size_t)nseq;
+  { int _rc = grow_device(&e->ovl_lists, &e->ovl_lists_bytes, item_bytes + 2 * sizeof(int32_t) * (size_t)nseq); if (_rc != SL2_OK) return _rc; }
+  st->items = (sl2_overlay_item*)e->ovl_lists;
+  st->counts = (int32_t*)((char*)e->ovl_lists + item_bytes);
+  st->marked = st->counts + nseq;
+  return SL2_OK;
+}
+
+}  // namespace sl2
+
+using namespace sl2;
+
+extern "C" size_t sl2_overlay_item_bound(int max_features, int partial_slots) {
+  if (max_features < 0 || partial_slots < 0) return 0;
+  return 2 * (size_t)max_features + (size_t)kMaxParticlesDrawn * (size_t)partial_slots + 2;
+}
+
+extern "C" int sl2_draw_items_host(const uint8_t* frame, int width, int height, const sl2_overlay_item* items, int count, const uint8_t* patches,
+                                   size_t patch_stride, int npatches, uint8_t* out) {
+  if (!frame || !out || count < 0 || (count > 0 && !items) || npatches < 0 || (npatches > 0 && (!patches || patch_stride < SL2_PATCH_BYTES))) {
+    set_error("sl2_draw_items_host: null pointer, negative count or patch_stride below 121");
+    return SL2_ERR_INVALID;
+  }
+  if (width < 1 || height < 1 || width > kOverlayMaxSide || height > kOverlayMaxSide) {
+    set_error("sl2_draw_items_host: width or height outside 1 .. 32768");
+    return SL2_ERR_INVALID;
+  }
+  std::vector<OverlayPrep> prep((size_t)count + 1);
+  overlay_draw_host_body(frame, width, height, items, count, patches, patch_stride, npatches, prep.data(), out);
+  return SL2_OK;
+}
+
+extern "C" int sl2_overlay_items(sl2_engine* e, int seq0, int nseq, int layers, const int32_t* marked, sl2_overlay_item* items, int item_stride,
+                                 int32_t* counts, int on_device) {
+  const char* why = engine_range_fault(e, seq0, nseq, layers);
+  if (!why && (!items || !counts)) why = "null items or counts";
+  if (!why && on_device && (uintptr_t)items % 8) why = "device items not 8-byte aligned";
+  if (!why && (item_stride < 0 || (size_t)item_stride < sl2_overlay_item_bound(e->N, e->kpart))) why = "item_stride below sl2_overlay_item_bound";
+  if (why) { set_error(range_text("sl2_overlay_items", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
+  SL2_HIP(hipSetDevice(e->device));
+  if (on_device) return launch_list(e, seq0, nseq, layers, 0, marked, items, item_stride, counts);
+  ListStage st;
+  { int _rc = list_stage(e, nseq, (size_t)item_stride, &st); if (_rc != SL2_OK) return _rc; }
+  if (marked) SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
+  { int _rc = launch_list(e, seq0, nseq, layers, 0, marked ? st.marked : nullptr, st.items, item_stride, st.counts); if (_rc != SL2_OK) return _rc; }
+  // whole strides come back in one copy: the items behind a list's count are not part of it (whatever the staging held)
+  SL2_HIP(hipMemcpyAsync(counts, st.counts, sizeof(int32_t) * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
+  SL2_HIP(hipMemcpyAsync(items, st.items, sizeof(sl2_overlay_item) * (size_t)item_stride * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
+  SL2_HIP(hipStreamSynchronize(e->stream));
+  return SL2_OK;
+}
+
+extern "C" int sl2_draw_overlays(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device, int layers,
+                                 const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device) {
+  const char* why = engine_range_fault(e, seq0, nseq, layers);
+  if (!why && (!frames || !out)) why = "null frames or out";
+  if (!why) why = geometry_fault(nseq, e->cam.width, e->cam.height, seq_stride, out_stride);
+  if (why) { set_error(range_text("sl2_draw_overlays", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
+  const int W = e->cam.width, H = e->cam.height;
+  SL2_HIP(hipSetDevice(e->device));
+  const size_t stride = sl2_overlay_item_bound(e->N, e->kpart), px = (size_t)W * H;
+  ListStage st;
+  { int _rc = list_stage(e, nseq, stride, &st); if (_rc != SL2_OK) return _rc; }
+  // image staging: host frames on their way in (packed), then host-bound images on their way out (packed)
+  const size_t in_bytes = frames_on_device ? 0 : ((px * (size_t)nseq + 255) & ~(size_t)255), out_bytes = out_on_device ? 0 : 3 * px * (size_t)nseq;
+  { int _rc = grow_device(&e->ovl_images, &e->ovl_images_bytes, in_bytes + out_bytes); if (_rc != SL2_OK) return _rc; }
+  const uint8_t* d_frames = frames;
+  size_t d_seq_stride = seq_stride;
+  if (!frames_on_device) {
+    SL2_HIP(hipMemcpy2DAsync(e->ovl_images, px, frames, seq_stride, px, (size_t)nseq, hipMemcpyHostToDevice, e->stream));
+    d_frames = (const uint8_t*)e->ovl_images; d_seq_stride = px;
+    // The caller's frames may be pageable memory and may be reused the moment the call returns.  The host form waits at its end
+    // anyway; with the output left on the device this is the one place the call waits: until the frames have been copied.
+    if (out_on_device) SL2_HIP(hipStreamSynchronize(e->stream));
+  }
+  const int32_t* d_marked = marked;
+  if (marked && !out_on_device) {
+    SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
+    d_marked = st.marked;
+  }
+  { int _rc = launch_list(e, seq0, nseq, layers, 1, d_marked, st.items, (int)stride, st.counts); if (_rc != SL2_OK) return _rc; }
+  uint8_t* d_out = out_on_device ? out : (uint8_t*)e->ovl_images + in_bytes;
+  const size_t d_out_stride = out_on_device ? out_stride : 3 * px;
+  {
+    LaunchScope ls(e, "k_overlay_draw");
+    int _rc = launch_draw(e->stream, d_frames, d_seq_stride, nseq, W, H, st.items, (int)stride, st.counts, e->patch, (size_t)kPatchStride,
+                          e->B * e->N, d_out, d_out_stride);
+    if (_rc != SL2_OK) return _rc;
+  }
+  if (out_on_device) return SL2_OK;
+  SL2_HIP(hipMemcpy2DAsync(out, out_stride, d_out, 3 * px, 3 * px, (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
+  SL2_HIP(hipStreamSynchronize(e->stream));
+  return SL2_OK;
+}
+
+extern "C" int sl2_draw_items_batch(int device, void* stream, const uint8_t* frames, int frames_on_device, int nimages, int width, int height,
+                                    size_t seq_stride, const sl2_overlay_item* items, int item_stride, const int32_t* counts, int items_on_device,
+                                    const uint8_t* patches, size_t patch_stride, int npatches, uint8_t* out, size_t out_stride, int out_on_device) {
+  if (!frames || !items || !counts || !out || item_stride < 0 || npatches < 0 || (npatches > 0 && (!patches || patch_stride < SL2_PATCH_BYTES)) ||
+      (items_on_device && (uintptr_t)items % 8)) {
+    set_error(range_text("sl2_draw_items_batch", "images", 0, nimages,
+                         "null pointer, negative item_stride or npatches, patch_stride below 121, or device items not 8-byte aligned"));
+    return SL2_ERR_INVALID;
+  }
+  if (const char* why = geometry_fault(nimages, width, height, seq_stride, out_stride)) {
+    set_error(range_text("sl2_draw_items_batch", "images", 0, nimages, why));
+    return SL2_ERR_INVALID;
+  }
+  if (!items_on_device)
+    for (int i = 0; i < nimages; ++i) {
+      if (counts[i] < 0 || counts[i] > item_stride) { set_error(at_text("sl2_draw_items_batch", "image", i, "count negative or over item_stride")); return SL2_ERR_INVALID; }
+      for (int k = 0; k < counts[i]; ++k)
+        if (const char* why = overlay_item_fault(items[(size_t)i * item_stride + k], npatches)) {
+          set_error(at_text("sl2_draw_items_batch", "image", i, why));
+          return SL2_ERR_INVALID;
+        }
+    }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device (the engine has no CPU fallback)"); return SL2_ERR_NO_DEVICE; }
+  SL2_HIP(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  // device temporaries of whatever arrived in host memory, released on every exit path (after the stream has drained)
+  struct Temps {
+    std::vector<void*> p;
+    hipStream_t st;
+    ~Temps() { if (!p.empty()) (void)hipStreamSynchronize(st); for (void* q : p) if (q) (void)hipFree(q); }
+    int alloc(void** o, size_t bytes) {
+      *o = nullptr;
+      const hipError_t e = hipMalloc(o, bytes ? bytes : 1);
+      if (e == hipSuccess) p.push_back(*o);
+      return e == hipSuccess ? SL2_OK : SL2_ERR_HIP;
+    }
+  } tmp;
+  tmp.st = st;
+  const size_t px = (size_t)width * height;
+  const uint8_t* d_frames = frames;
+  size_t d_seq_stride = seq_stride;
+  if (!frames_on_device) {
+    void* d = nullptr;
+    if (tmp.alloc(&d, px * (size_t)nimages)) { set_error("sl2_draw_items_batch: device allocation failed"); return SL2_ERR_HIP; }
+    SL2_HIP(hipMemcpy2DAsync(d, px, frames, seq_stride, px, (size_t)nimages, hipMemcpyHostToDevice, st));
+    d_frames = (const uint8_t*)d; d_seq_stride = px;
+  }
+  const sl2_overlay_item* d_items = items;
+  const int32_t* d_counts = counts;
+  const uint8_t* d_patches = patches;
+  if (!items_on_device) {
+    void *di = nullptr, *dc = nullptr, *dp = nullptr;
+    const size_t ib = sizeof(sl2_overlay_item) * (size_t)item_stride * (size_t)nimages, pb = (size_t)npatches * patch_stride;
+    if (tmp.alloc(&di, ib) || tmp.alloc(&dc, sizeof(int32_t) * (size_t)nimages) || tmp.alloc(&dp, pb)) {
+      set_error("sl2_draw_items_batch: device allocation failed");
+      return SL2_ERR_HIP;
+    }
+    if (ib) SL2_HIP(hipMemcpyAsync(di, items, ib, hipMemcpyHostToDevice, st));
+    SL2_HIP(hipMemcpyAsync(dc, counts, sizeof(int32_t) * (size_t)nimages, hipMemcpyHostToDevice, st));
+    // (the last entry of a host array need not be padded to the stride: 121 bytes of it are read)
+    if (pb) SL2_HIP(hipMemcpyAsync(dp, patches, pb - patch_stride + SL2_PATCH_BYTES, hipMemcpyHostToDevice, st));
+    d_items = (const sl2_overlay_item*)di; d_counts = (const int32_t*)dc; d_patches = npatches ? (const uint8_t*)dp : nullptr;
+  }
+  uint8_t* d_out = out;
+  size_t d_out_stride = out_stride;
+  if (!out_on_device) {
+    void* d = nullptr;
+    if (tmp.alloc(&d, 3 * px * (size_t)nimages)) { set_error("sl2_draw_items_batch: device allocation failed"); return SL2_ERR_HIP; }
+    d_out = (uint8_t*)d; d_out_stride = 3 * px;
+  }
+  { int _rc = launch_draw(st, d_frames, d_seq_stride, nimages, width, height, d_items, item_stride, d_counts, d_patches, patch_stride, npatches, d_out, d_out_stride);
+    if (_rc != SL2_OK) return _rc; }
+  if (!out_on_device) {
+    SL2_HIP(hipMemcpy2DAsync(out, out_stride, d_out, 3 * px, 3 * px, (size_t)nimages, hipMemcpyDeviceToHost, st));
+    SL2_HIP(hipStreamSynchronize(st));
+  }
+  return SL2_OK;
+}

@@ -306,6 +306,60 @@ class Engine:
                                            _lib.vp(int(out_ptr)), int(out_bytes), _lib.vp(int(offsets_ptr)), 1))
         return out_ptr, offsets_ptr
 
+    # ---- annotated frames (include/scenelib2_amd.h, "annotated frames") ----
+    def overlay_item_bound(self):
+        """sl2_overlay_item_bound for this engine's shape: no sequence's draw list is longer."""
+        kpart = max(1, min(4, self._prm.max_features_to_init_at_once))
+        return int(self.L.sl2_overlay_item_bound(self.max_features, kpart))
+
+    def _marked_arg(self, marked, nseq):
+        if marked is None:
+            return None, None
+        m = np.ascontiguousarray(marked, dtype=np.int32).reshape(nseq)
+        return m.ctypes.data_as(_lib.vp), m
+
+    def overlay_items(self, seq0=0, nseq=None, layers=_lib.SL2_OVERLAY_ALL, marked=None):
+        """sl2_overlay_items, host form: the draw lists of sequences seq0 .. seq0 + nseq - 1 as a list of arrays of
+        _lib.OVERLAY_ITEM_DTYPE.  layers: SL2_OVERLAY_* bits; marked: None or [nseq] labels (-1: none)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        stride = self.overlay_item_bound()
+        items = np.zeros((max(nseq, 1), stride), _lib.OVERLAY_ITEM_DTYPE)
+        counts = np.zeros(max(nseq, 1), np.int32)
+        mp, keep = self._marked_arg(marked, nseq)
+        self._ck(self.L.sl2_overlay_items(self.h, int(seq0), nseq, int(layers), mp, items.ctypes.data_as(_lib.vp), stride,
+                                          counts.ctypes.data_as(_lib.vp), 0))
+        return [items[i, :counts[i]].copy() for i in range(nseq)]
+
+    def draw_overlays(self, frames, seq0=0, nseq=None, layers=_lib.SL2_OVERLAY_ALL, marked=None, on_device=False, seq_stride=0,
+                      out_stride=0):
+        """sl2_draw_overlays with the images returned to the host: uint8 [nseq][height][width][3] (with out_stride above
+        3 width height: [nseq][out_stride] bytes, the images at the start of each).  frames: uint8 [nseq][height][width] in host
+        memory, or with on_device=True a device pointer (seq_stride bytes apart)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(self.cam["width"]), int(self.cam["height"])
+        if on_device:
+            fp, stride, keep = _lib.vp(int(frames)), int(seq_stride if seq_stride else self.frame_bytes), None
+        else:
+            keep = np.ascontiguousarray(frames, dtype=np.uint8).reshape(nseq, -1)
+            fp, stride = keep.ctypes.data_as(_lib.vp), keep.shape[1]
+        ostride = int(out_stride) if out_stride else 3 * w * h
+        out = np.zeros((max(nseq, 1), ostride), np.uint8)
+        mp, keep_m = self._marked_arg(marked, nseq)
+        self._ck(self.L.sl2_draw_overlays(self.h, int(seq0), nseq, fp, stride, int(bool(on_device)), int(layers), mp,
+                                          out.ctypes.data_as(_lib.vp), ostride, 0))
+        return out[:nseq].reshape(nseq, h, w, 3) if ostride == 3 * w * h else out[:nseq]
+
+    def draw_overlays_device(self, frames_ptr, out_ptr, seq0=0, nseq=None, layers=_lib.SL2_OVERLAY_ALL, marked_ptr=None, seq_stride=0,
+                             out_stride=0):
+        """sl2_draw_overlays, device form: frames_ptr, out_ptr and marked_ptr (int32 [nseq] or None) are device pointers as
+        integers.  Two launches on the engine's stream and no wait."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(self.cam["width"]), int(self.cam["height"])
+        self._ck(self.L.sl2_draw_overlays(self.h, int(seq0), nseq, _lib.vp(int(frames_ptr)), int(seq_stride if seq_stride else self.frame_bytes), 1,
+                                          int(layers), _lib.vp(int(marked_ptr)) if marked_ptr else None, _lib.vp(int(out_ptr)),
+                                          int(out_stride if out_stride else 3 * w * h), 1))
+        return out_ptr
+
     def features(self, seq, include_deleted=False):
         arr = (_lib.sl2_feature_info * self.max_features)()
         cnt = C.c_int(0)
@@ -664,6 +718,21 @@ class MonoSLAM:
         if keep is not None:
             self._engine.synchronize()  # the host buffer must outlive the copy queued in front of the step
         return self._after_step(enable_mapping)
+
+    # GraphicTool::DrawRawAR(frame, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation)
+    # — graphictool.cpp:285-364, without OpenGL
+    def DrawRawAR(self, frame, out_rgb=None, chk_display_2d_descriptors=True, chk_display_2d_search_regions=True,
+                  chk_display_initialisation=True):
+        """The frame annotated with the search ellipses, the templates, a partially initialised feature's particle ellipses and
+        the initialisation boxes (sl2_draw_overlays): uint8 [height][width][3], R, G, B; also written into out_rgb if given.
+        marked_feature_label_ is drawn green."""
+        layers = (_lib.SL2_OVERLAY_SEARCH_REGIONS if chk_display_2d_search_regions else 0) | \
+                 (_lib.SL2_OVERLAY_DESCRIPTORS if chk_display_2d_descriptors else 0) | \
+                 (_lib.SL2_OVERLAY_INITIALISATION if chk_display_initialisation else 0)
+        img = self._engine.draw_overlays(self._frame(frame), 0, 1, layers, [self.marked_feature_label_])[0]
+        if out_rgb is not None:
+            out_rgb[...] = img
+        return img
 
     def _frame(self, frame):
         f = np.ascontiguousarray(frame, dtype=np.uint8)
