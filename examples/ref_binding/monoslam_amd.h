@@ -110,6 +110,21 @@ class MonoSLAM {             // monoslam.h:69-219
     impl_.marked_feature_label_ = marked_feature_label_;
     impl_.DrawRawAR(view(frame), out_rgb.data, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation);
   }
+  // GraphicTool::DrawRectifiedAR (graphictool.cpp:222-283) with the reference's three check boxes: out_rgb becomes the undistorted
+  // frame with the 3-D scene over it, CV_8UC3 in R, G, B order, drawn on the device
+  void DrawRectifiedAR(cv::Mat frame, cv::Mat& out_rgb, const bool& chk_display_trajectory, const bool& chk_display_3d_features,
+                       const bool& chk_display_3d_uncertainties) {
+    out_rgb.create(frame.rows, frame.cols, CV_8UC3);
+    impl_.marked_feature_label_ = marked_feature_label_;
+    impl_.DrawRectifiedAR(view(frame), out_rgb.data, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties);
+  }
+  // GraphicTool::DrawAR (graphictool.cpp:177-220)
+  void DrawAR(cv::Mat frame, cv::Mat& out_rgb, const bool& chk_rectify_image_display, const bool& chk_display_trajectory,
+              const bool& chk_display_3d_features, const bool& chk_display_3d_uncertainties, const bool& chk_display_2d_descriptors,
+              const bool& chk_display_2d_search_regions, const bool& chk_display_initialisation) {
+    if (chk_rectify_image_display) DrawRectifiedAR(frame, out_rgb, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties);
+    else DrawRawAR(frame, out_rgb, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation);
+  }
   void InitialiseFeature(cv::Mat frame) {                                  // monoslam.cpp:1211-1235: at the clicked (uu_, vv_)
     impl_.uu_ = uu_; impl_.vv_ = vv_;
     impl_.InitialiseFeature(view(frame));

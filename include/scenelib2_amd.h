@@ -48,7 +48,9 @@ extern "C" {
  * for cameras much larger than the engine's image); sl2_snapshot_batch, sl2_snapshot_bound, SL2_SNAP_*,
  * sl2_snapshot_header.omitted_sections (taken from reserved[]: the public state of a range of sequences in one call); sl2_overlay_items,
  * sl2_draw_overlays, sl2_draw_items_batch, sl2_draw_items_host, sl2_overlay_item_bound, sl2_overlay_item, SL2_ITEM_*,
- * SL2_OVERLAY_* (annotated frames: the raw-image display of GraphicTool::DrawRawAR as a draw list and a rasteriser). */
+ * SL2_OVERLAY_* (annotated frames: the raw-image display of GraphicTool::DrawRawAR as a draw list and a rasteriser);
+ * SL2_ITEM_SEGMENT, sl2_rectify_frames, sl2_rectify_frame_host, sl2_scene_items, sl2_scene_item_bound, sl2_draw_rectified,
+ * SL2_SCENE_* (the rectified view of GraphicTool::DrawRectifiedAR: a line primitive, the undistorted frame, the 3-D scene). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -656,7 +658,7 @@ int sl2_snapshot_batch(sl2_engine* e, int seq0, int nseq, int sections, const in
  * both run on the device for a whole batch (k_overlay_list, k_overlay_draw: sl2_overlay.hip).
  *
  * THE ITEM, 64 bytes:
- *   kind    SL2_ITEM_RING, SL2_ITEM_PATCH or SL2_ITEM_RECT
+ *   kind    SL2_ITEM_RING, SL2_ITEM_PATCH or SL2_ITEM_RECT (and SL2_ITEM_SEGMENT: "the rectified view", below)
  *   label   the feature's label; -1 for a box
  *   a[4]    RING, PATCH: the centre (a[0], a[1]), the rest 0.  RECT: the inclusive corners x0, y0, x1, y1.
  *   patch   PATCH: index into the call's `patches` array, entry k at patches + k * patch_stride, 121 bytes of it used
@@ -728,7 +730,7 @@ int sl2_snapshot_batch(sl2_engine* e, int seq0, int nseq, int sections, const in
  * is outside the array.  A device-resident list cannot be looked at: the kernel clamps its count to 0 .. item_stride and skips
  * such items (they draw nothing, as the pixel rules say, and so they do in sl2_draw_items_host, which is the kernel's arithmetic
  * on the host); every loop is bounded by the clamped count and the image. */
-enum { SL2_ITEM_RING = 1, SL2_ITEM_PATCH = 2, SL2_ITEM_RECT = 3 };
+enum { SL2_ITEM_RING = 1, SL2_ITEM_PATCH = 2, SL2_ITEM_RECT = 3, SL2_ITEM_SEGMENT = 5 /* below; 4 is not a kind */ };
 enum { SL2_OVERLAY_SEARCH_REGIONS = 1, SL2_OVERLAY_DESCRIPTORS = 2, SL2_OVERLAY_INITIALISATION = 4, SL2_OVERLAY_ALL = 7 };
 typedef struct sl2_overlay_item {
   int32_t kind;
@@ -751,6 +753,115 @@ int sl2_draw_overlays(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, 
                       int layers, const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device);
 int sl2_draw_items_host(const uint8_t* frame, int width, int height, const sl2_overlay_item* items, int count,
                         const uint8_t* patches, size_t patch_stride, int npatches, uint8_t* out);
+
+/* ---- the rectified view (additions within SL2_API_VERSION 5): a line in the rasteriser, the undistorted frame, the 3-D scene ----
+ *
+ * GraphicTool::DrawRectifiedAR (graphic/graphictool.cpp:222-283) shows the MAP: the camera frame with the lens distortion
+ * removed and, over it, the 3-D features, their uncertainty ellipsoids, the rays of partially initialised features and the
+ * trajectory.  Its numerical half is the line primitive that scene needs, the frame (k_rectify), the scene as a DRAW LIST per
+ * sequence for the rasteriser above (k_scene_list), and the three chained (sl2_draw_rectified); all run on the device for a
+ * whole batch (sl2_rectify.hip).
+ *
+ * SL2_ITEM_SEGMENT = 5, a fourth kind of the item above, in every drawing call above (kind 4 stays unassigned and draws
+ * nothing):  a[4] = x0, y0, x1, y1, the two ends;  patch = -1;  q = 0.  THE PIXEL RULE, in integers (64-bit where products
+ * need it), no floating point:
+ *   each of the four coordinates beyond +-2^20 counts as +-2^20 (as for RECT);
+ *   dx = x1 - x0, dy = y1 - y0; the segment is x-major iff |dx| >= |dy|, else y-major;
+ *   the two ends are exchanged if that is needed for the major coordinate not to decrease from the first to the second;
+ *   x-major, with D = x1 - x0 >= 0 and dy = y1 - y0 after the exchange: the item covers (x, y) iff x0 <= x <= x1 and
+ *     y == y0 + floor((2 (x - x0) dy + D) / (2 D)) - the division FLOORED (towards minus infinity), not truncated; with
+ *     D == 0 (then dy == 0 too) it covers the one pixel (x0, y0);
+ *   y-major: the same with x and y exchanged.
+ *   One pixel per step of the major coordinate, the nearest one; where the line passes exactly midway between two pixels
+ *   (2 (x - x0) dy + D an exact multiple of 2 D) the one with the larger minor coordinate.  After the exchange a segment and
+ *   its reverse are the same item: they cover the same pixels, the ties included.  The set is clipped to the image; the
+ *   implementation's box is the ends' box.  The painter's rule is unchanged: the last item wins.
+ *
+ * sl2_rectify_frames   the frame with the lens distortion removed, for sequences seq0 .. seq0 + nseq - 1 in ONE launch
+ *   (k_rectify, sl2_rectify.hip).  frames: one grey image per sequence at frames + i * seq_stride, engine geometry, host or
+ *   device memory; out: grey images of the same size at out + i * out_stride.  Sequence seq0 + i is warped with ITS OWN u0, v0
+ *   and kd1 as the setters queued so far leave them (sl2_set_cameras), read on the device from the sequence's record: the call
+ *   is ordered behind them on the engine's stream.  THE PIXEL RULE, for output pixel (x, y), in FP64, in exactly this order,
+ *   without contraction into fused multiply-adds:
+ *     cx = x - u0;  cy = y - v0;  r2 = cx*cx + cy*cy;  f = 1.0 + (2.0*kd1)*r2;
+ *     !(f > 0): BORDER.  s = sqrt(f);  xs = cx / s + u0;  ys = cy / s + v0      (Camera::Project's distortion, camera.cpp:108-113:
+ *       where the ideal pinhole point (x, y) lands in the camera's own image);
+ *     xs or ys not finite, or beyond +-2^20: BORDER;
+ *     X = floor(xs*32.0 + 0.5), Y = floor(ys*32.0 + 0.5) as integers: the source position in 1/32 pixel;
+ *     ix = X >> 5 (floored), fx = X & 31 (0 .. 31), iy and fy likewise; p00 = frame(ix, iy), p10 = frame(ix + 1, iy),
+ *     p01 = frame(ix, iy + 1), p11 = frame(ix + 1, iy + 1), a tap off the image reading BORDER;
+ *     out = ((32-fx)*(32-fy)*p00 + fx*(32-fy)*p10 + (32-fx)*fy*p01 + fx*fy*p11 + 512) >> 10.
+ *   BORDER = 0.  With kd1 == 0 the output is the input.  The output has the INPUT's geometry and principal point and is exact
+ *   per pixel; the reference draws a 10 x 10 mesh of textured quads whose outline is the undistorted image border, i.e. it
+ *   scales the view so that the whole frame shows.  This call crops instead: what a pinhole camera of the same fku, fkv, u0,
+ *   v0 sees within width x height, so a 3-D point X in the camera frame lies at (u0 - fku X0/X2, v0 - fkv X1/X2) of the output.
+ *   Residency and waiting are sl2_draw_overlays': host frames are copied into engine-owned staging; in front of a device output
+ *   the call waits once, until they have been copied.  A host output is written into staging, then one wait and one copy of
+ *   exactly width height bytes per image.  With device frames and a device output: one launch on the engine's stream, no wait.
+ *   out must not overlap frames.  The call drops no captured step, changes nothing in the engine, does not consult the active
+ *   mask and works with sequence groups.
+ * sl2_rectify_frame_host   the plain C++ form of one image from the same source as the kernel (no device needed): byte for
+ *   byte its output.  width and height within 1 .. 32768; u0, v0, kd1 finite.
+ *
+ * THE SCENE'S DRAW LIST OF A SEQUENCE, from its CURRENT state, in DrawRectifiedAR's order.  `layers` holds the example's three
+ * checkboxes as bits: SL2_SCENE_TRAJECTORY = 1, SL2_SCENE_FEATURES = 2, SL2_SCENE_UNCERTAINTIES = 4.  The camera of the
+ * rectified image is the sequence's own (sl2_set_cameras) with kd1 = 0: a point X of the camera frame (zeroedyi: RRW (y - r)
+ * of the current xv_) with X[2] >= 0.01 (kNear_) projects to (u0 - fku X[0]/X[2], v0 - fkv X[1]/X[2]), evaluated as written.
+ * Colour and `marked` are SetFeatureColour's, as for the annotated frames above; rounding is int(v + 0.5), C truncation, and a
+ * coordinate that is not finite or rounds outside +-32767 omits its item.
+ *   A 3-D SEGMENT a .. b of the camera frame becomes an SL2_ITEM_SEGMENT in this order of operations:
+ *     (1) both ends with X[2] < 0.01: omitted.  One end behind: with t = (0.01 - a[2]) / (b[2] - a[2]) the point
+ *         (a[0] + t (b[0] - a[0]), a[1] + t (b[1] - a[1]), 0.01) replaces it;
+ *     (2) both ends are projected (p, r); not finite: omitted;
+ *     (3) the 2-D segment is clipped to the guard square [-32767, 32767]^2 by Liang-Barsky - edges in the order left, right,
+ *         top, bottom, each a constraint pk t <= qk with pk = -dx, dx, -dy, dy and qk = p[0] + 32767, 32767 - p[0],
+ *         p[1] + 32767, 32767 - p[1]; t0 = 0, t1 = 1 tightened by t = qk / pk; entirely outside: omitted; the ends become
+ *         p + t0 (dx, dy) and p + t1 (dx, dy);
+ *     (4) the four coordinates are rounded.
+ *   SL2_SCENE_TRAJECTORY, first: for consecutive entries of trajectory_store_ as sl2_get_trajectory returns them (the up to
+ *     1000 most recent, oldest first), the segment between the two, both taken into the camera frame; yellow, label -1.
+ *   Then the features in feature_list_ order:
+ *   fully initialised live feature, m = zeroedyi:
+ *     SL2_SCENE_FEATURES and m[2] >= 0.01: a filled 3 x 3 marker at the rounded projection (x, y), as RECT (x-1, y-1, x+1, y+1)
+ *       then RECT (x, y, x, y).
+ *     SL2_SCENE_UNCERTAINTIES: Sigma = Pzeroedyigraphics (feature_model.cpp:128-145) from the current P, with Jx =
+ *       dzeroedyi_by_dxp (3 x 7; dxp_by_dxv is the identity on the first seven columns), Jy = dzeroedyi_by_dyi = RRW, Pxx the
+ *       leading 7 x 7 of P, Pxy its first 7 rows in the feature's columns, Pyy the feature's block.  Summation order (so that
+ *       the list is reproducible to the bit): every inner sum starts at 0.0 and runs over its index upwards;
+ *       A = Jx Pxx, Bm = Jx Pxy, Cm = Jy Pyy;  T1[i][j] = sum_c A[i][c] Jx[j][c], T3[i][j] = sum_c Bm[i][c] Jy[j][c],
+ *       T4[i][j] = sum_c Cm[i][c] Jy[j][c];  Sigma[i][j] = ((T1[i][j] + T3[j][i]) + T3[i][j]) + T4[i][j].
+ *       The outline of the 3-sigma ellipsoid under the pinhole is a conic: D[i][j] = m[i]*m[j] - 9.0*Sigma[i][j] (entries 00,
+ *       01, 02, 11, 12, 22 from Sigma's 00, 01, 02, 11, 12, 22), d = D22.  Only if d > 0 and m[2] > 0 (the ellipsoid lies wholly
+ *       in front of the camera plane; d > 0 alone holds for one wholly behind it too): cn = (D02/d, D12/d); En00 = cn0*cn0 - D00/d, En01 = cn0*cn1 - D01/d, En11 = cn1*cn1 - D11/d;
+ *       E00 = (fku*En00)*fku, E01 = (fku*En01)*fkv, E11 = (fkv*En11)*fkv; a RING at the rounded (u0 - fku*cn0, v0 - fkv*cn1)
+ *       with A = E11, B = -2.0*E01, C = E00, rhs = E00*E11 - E01*E01.  A form that is not positive definite is listed and
+ *       draws nothing (the RING's own rule).
+ *   partially initialised feature, SL2_SCENE_FEATURES: the ray y0 .. y0 + 10.0 hhat (kSemiInfiniteLineLength_) of the partial
+ *     model's zeroed state (y0 = RRW (r_i - r), hhat = RRW hhat_i), as a 3-D segment above, with the feature's label and
+ *     colour.  (The reference draws no uncertainty on lines.)
+ *   Left out: DrawAxes - its extents are accumulators of the GL drawing state, not of the map.
+ *   No list is longer than sl2_scene_item_bound(max_features, partial_slots) = 3 max_features + partial_slots + 999.
+ *
+ * sl2_scene_items    the lists themselves; arguments, residency and waiting as sl2_overlay_items (items of a device list
+ *   8-byte aligned, item_stride at least sl2_scene_item_bound).  sl2_draw_items_batch accepts the lists as they are (no patches).
+ * sl2_draw_rectified rectify, list and draw with no host round trip: three stream-ordered launches (k_rectify into
+ *   engine-owned staging, k_scene_list, k_overlay_draw over the rectified grey).  Arguments, residency and waiting as
+ *   sl2_draw_overlays; out is RGB24.  Both drop no captured step, change nothing in the engine, do not consult the active
+ *   mask and work with sequence groups.
+ * Refused (SL2_ERR_INVALID, nothing queued, sl2_last_error() names the sequences): null pointers, a range outside the batch,
+ * nseq < 1, layers with bits outside SL2_SCENE_ALL, seq_stride below width height, out_stride below width height
+ * (sl2_rectify_frames) or 3 width height (sl2_draw_rectified), item_stride below the bound, a misaligned device `items`; in the
+ * host form a null pointer, a size outside 1 .. 32768 or a camera number that is not finite. */
+enum { SL2_SCENE_TRAJECTORY = 1, SL2_SCENE_FEATURES = 2, SL2_SCENE_UNCERTAINTIES = 4, SL2_SCENE_ALL = 7 };
+int sl2_rectify_frames(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device,
+                       uint8_t* out, size_t out_stride, int out_on_device);
+int sl2_rectify_frame_host(const uint8_t* frame, int width, int height, double u0, double v0, double kd1, uint8_t* out);
+/* Host only, no device: the longest scene list of a sequence of an engine of this shape; 0 for a negative argument. */
+size_t sl2_scene_item_bound(int max_features, int partial_slots);
+int sl2_scene_items(sl2_engine* e, int seq0, int nseq, int layers, const int32_t* marked /* [nseq] labels, NULL = none */,
+                    sl2_overlay_item* items, int item_stride, int32_t* counts, int on_device);
+int sl2_draw_rectified(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device,
+                       int layers, const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device);
 
 /* selected_feature_list_ (labels, selection order) and per-step counters:
  * counters[0] = number_of_visible_features_, [1] = #selected,

@@ -273,6 +273,29 @@ class MonoSLAM {
     check(sl2_draw_overlays(eng_, 0, 1, frame.data, px, frame.on_device ? 1 : 0, layers, &marked, out_rgb, 3 * px, 0), "sl2_draw_overlays");
   }
 
+  // GraphicTool::DrawRectifiedAR (graphic/graphictool.cpp:222-283) without OpenGL: the frame with the lens distortion removed and,
+  // over it, the trajectory, the 3-D features, their 3-sigma ellipsoids and the rays of partially initialised features, drawn
+  // on the device (sl2_draw_rectified) into out_rgb, RGB24 [height][width][3] in host memory.  The three arguments are the
+  // example's check boxes; marked_feature_label_ is drawn green.  From the state as the last call left it.
+  void DrawRectifiedAR(const Frame& frame, uint8_t* out_rgb, bool chk_display_trajectory, bool chk_display_3d_features,
+                       bool chk_display_3d_uncertainties) {
+    if (!eng_ || !frame.data || !out_rgb || frame.cols != camera_->width_ || frame.rows != camera_->height_)
+      throw std::runtime_error("MonoSLAM::DrawRectifiedAR: frame does not match the camera");
+    const int layers = (chk_display_trajectory ? SL2_SCENE_TRAJECTORY : 0) | (chk_display_3d_features ? SL2_SCENE_FEATURES : 0) |
+                       (chk_display_3d_uncertainties ? SL2_SCENE_UNCERTAINTIES : 0);
+    const int32_t marked = marked_feature_label_;
+    const size_t px = (size_t)frame.cols * frame.rows;
+    check(sl2_draw_rectified(eng_, 0, 1, frame.data, px, frame.on_device ? 1 : 0, layers, &marked, out_rgb, 3 * px, 0), "sl2_draw_rectified");
+  }
+
+  // GraphicTool::DrawAR (graphic/graphictool.cpp:177-220): the rectified view or the raw one, by the example's check box
+  void DrawAR(const Frame& frame, uint8_t* out_rgb, bool chk_rectify_image_display, bool chk_display_trajectory, bool chk_display_3d_features,
+              bool chk_display_3d_uncertainties, bool chk_display_2d_descriptors, bool chk_display_2d_search_regions,
+              bool chk_display_initialisation) {
+    if (chk_rectify_image_display) DrawRectifiedAR(frame, out_rgb, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties);
+    else DrawRawAR(frame, out_rgb, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation);
+  }
+
   // The seams of GoOneStep, callable one by one like the reference's public members (monoslam.cpp:118-177; kalman.h:51-52
   // through the Kalman struct below).  With enable_mapping = false, predict -> auto_select_n_features ->
   // make_measurements -> update -> finish_step is GoOneStep.

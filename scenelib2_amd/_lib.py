@@ -112,6 +112,8 @@ STEP_STATS_DTYPE = np.dtype([(n, np.int32) for n in ("stepped", "status_flags", 
 
 # annotated frames (sl2_overlay_items, sl2_draw_items_batch ...): item kinds, layer bits and the 64-byte item
 SL2_ITEM_RING, SL2_ITEM_PATCH, SL2_ITEM_RECT = 1, 2, 3
+SL2_ITEM_SEGMENT = 5      # (4 is not a kind)
+SL2_SCENE_TRAJECTORY, SL2_SCENE_FEATURES, SL2_SCENE_UNCERTAINTIES, SL2_SCENE_ALL = 1, 2, 4, 7
 SL2_OVERLAY_SEARCH_REGIONS, SL2_OVERLAY_DESCRIPTORS, SL2_OVERLAY_INITIALISATION, SL2_OVERLAY_ALL = 1, 2, 4, 7
 OVERLAY_ITEM_DTYPE = np.dtype([("kind", np.int32), ("label", np.int32), ("a", np.int32, (4,)), ("patch", np.int32),
                                ("rgb", np.uint8, (3,)), ("pad", np.uint8), ("q", np.float64, (4,))])
@@ -149,6 +151,7 @@ EXPORTED_SYMBOLS = [
     "sl2_converter_set_filters", "sl2_converter_get_filters", "sl2_convert_frame_host_filtered",
     "sl2_snapshot_bound", "sl2_snapshot_batch",
     "sl2_overlay_item_bound", "sl2_overlay_items", "sl2_draw_items_batch", "sl2_draw_overlays", "sl2_draw_items_host",
+    "sl2_rectify_frames", "sl2_rectify_frame_host", "sl2_scene_item_bound", "sl2_scene_items", "sl2_draw_rectified",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -298,6 +301,13 @@ def _bind(L):
                                            vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int]
         L.sl2_draw_overlays.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int]
         L.sl2_draw_items_host.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_size_t, C.c_int, vp]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_rectify_frames"):
+        L.sl2_rectify_frames.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int]
+        L.sl2_rectify_frame_host.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
+        L.sl2_scene_item_bound.argtypes = [C.c_int, C.c_int]
+        L.sl2_scene_item_bound.restype = C.c_size_t
+        L.sl2_scene_items.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int]
+        L.sl2_draw_rectified.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int]
     return L
 
 

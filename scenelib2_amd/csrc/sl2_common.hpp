@@ -298,6 +298,15 @@ int launch_small_back(sl2_engine* e, int save_trajectory, int panel_w);   // (Gr
 int launch_update(sl2_engine* e);
 int launch_syrk_on(sl2_engine* e, const double* Vt, double* P);
 int launch_finalize(sl2_engine* e, int save_trajectory);
+// sl2_overlay.hip, shared with the rectified view (sl2_rectify.hip): the rasteriser's launch, the checks of an image geometry
+// (nullptr: fine), the text of a refusal that a range shares, and the engine-owned staging of lists and images
+int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, int nimages, int width, int height, const sl2_overlay_item* d_items,
+                int item_stride, const int32_t* d_counts, const uint8_t* d_patches, size_t patch_stride, int npatches, uint8_t* d_out, size_t out_stride);
+const char* geometry_fault(int nimages, int width, int height, size_t seq_stride, size_t out_stride);
+std::string range_text(const char* fn, const char* noun, int first, int count, const char* what);
+int grow_device(void** p, size_t* have, size_t need);
+struct ListStage { sl2_overlay_item* items; int32_t* counts; int32_t* marked; };
+int list_stage(sl2_engine* e, int nseq, size_t stride, ListStage* st);
 int launch_mapping(sl2_engine* e, const TailPlan& tp);
 int launch_manual_init(sl2_engine* e, const int* d_uv);
 int launch_auto_init(sl2_engine* e);

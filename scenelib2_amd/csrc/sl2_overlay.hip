@@ -150,7 +150,9 @@ struct DrawArgs {
   int dword_out;      // every row of every image starts on a 4-byte boundary: a thread's 12 bytes go out as three dwords
 };
 
-__global__ void __launch_bounds__(kDrawThreads) k_overlay_draw(const DrawArgs A) {
+// (Eight waves a SIMD are asked for: with the SEGMENT kind the allocator took 66 registers without the bound, seven waves, and the
+// kernel - bound by latency, not by bytes - ran 12-14 % slower at 1024 sequences; at 64 registers it parks 20 scalars in vector lanes.)
+__global__ void __launch_bounds__(kDrawThreads, 8) k_overlay_draw(const DrawArgs A) {
   __shared__ OverlayPrep s_prep[kDrawChunk];
   __shared__ int s_wave[kDrawThreads / 64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -209,7 +211,7 @@ static std::string at_text(const char* fn, const char* noun, int idx, const char
   return buf;
 }
 // a fault that every sequence or image of the call shares (a stride, the geometry, a pointer): the range is named
-static std::string range_text(const char* fn, const char* noun, int first, int count, const char* what) {
+std::string range_text(const char* fn, const char* noun, int first, int count, const char* what) {
   char buf[256];
   snprintf(buf, sizeof(buf), "%s: %s %d .. %d: %s", fn, noun, first, first + (count > 0 ? count : 1) - 1, what);
   return buf;
@@ -223,7 +225,7 @@ static const char* engine_range_fault(const sl2_engine* e, int seq0, int nseq, i
   return nullptr;
 }
 
-static int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, int nimages, int width, int height,
+int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, int nimages, int width, int height,
                        const sl2_overlay_item* d_items, int item_stride, const int32_t* d_counts, const uint8_t* d_patches, size_t patch_stride,
                        int npatches, uint8_t* d_out, size_t out_stride) {
   DrawArgs A;
@@ -240,7 +242,7 @@ static int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_s
 }
 
 // what every drawing call checks of its image geometry (nullptr: fine)
-static const char* geometry_fault(int nimages, int width, int height, size_t seq_stride, size_t out_stride) {
+const char* geometry_fault(int nimages, int width, int height, size_t seq_stride, size_t out_stride) {
   if (nimages < 1) return "no images";
   if (width < 1 || height < 1 || width > kOverlayMaxSide || height > kOverlayMaxSide) return "width or height outside 1 .. 32768";
   if (seq_stride < (size_t)width * (size_t)height) return "seq_stride below width * height";
@@ -250,7 +252,7 @@ static const char* geometry_fault(int nimages, int width, int height, size_t seq
   return nullptr;
 }
 
-static int grow_device(void** p, size_t* have, size_t need) {
+int grow_device(void** p, size_t* have, size_t need) {
   if (need <= *have) return SL2_OK;
   if (*p) { SL2_HIP(hipFree(*p)); *p = nullptr; *have = 0; }
   SL2_HIP(hipMalloc(p, need));
@@ -269,8 +271,7 @@ static int launch_list(sl2_engine* e, int seq0, int nseq, int layers, int patch_
 }
 
 // engine-owned list staging: items [nseq][stride], then counts [nseq], then marked [nseq]
-struct ListStage { sl2_overlay_item* items; int32_t* counts; int32_t* marked; };
-static int list_stage(sl2_engine* e, int nseq, size_t stride, ListStage* st) {
+int list_stage(sl2_engine* e, int nseq, size_t stride, ListStage* st) {
   const size_t item_bytes = sizeof(sl2_overlay_item) * stride * (size_t)nseq;
   { int _rc = grow_device(&e->ovl_lists, &e->ovl_lists_bytes, item_bytes + 2 * sizeof(int32_t) * (size_t)nseq); if (_rc != SL2_OK) return _rc; }
   st->items = (sl2_overlay_item*)e->ovl_lists;

@@ -17,12 +17,15 @@ constexpr int kOverlayBoxHalfMax = 1 << 20;  // a ring's box is cut here: beyond
 struct OverlayPrep {      // 72 bytes
   int kind;               // SL2_ITEM_*
   int cx, cy;             // RING, PATCH: the centre
-  int bx0, by0, bx1, by1; // conservative inclusive box (RECT: the rectangle itself)
+  int bx0, by0, bx1, by1; // conservative inclusive box (RECT: the rectangle itself; SEGMENT: the endpoints' box)
   int patch;
   uint32_t rgb;           // r | g << 8 | b << 16
-  int pad;
+  int pad;                // SEGMENT: kSegYMajor | kSegMinorFalls (the box holds the rest: its sides are |dx| and |dy|); else 0
   double A, B, C, rhs;
 };
+
+constexpr int kSegYMajor = 1;      // |dy| > |dx|: y is the major coordinate
+constexpr int kSegMinorFalls = 2;  // walking the major coordinate upwards, the minor one decreases
 
 SL2_HD bool overlay_finite(double v) { return v - v == 0.0; }
 
@@ -53,6 +56,15 @@ SL2_HD void overlay_ring_half(double A, double B, double C, double rhs, int* hx,
 
 SL2_HD int overlay_clampc(int v) { return v < -kOverlayBoxHalfMax ? -kOverlayBoxHalfMax : v > kOverlayBoxHalfMax ? kOverlayBoxHalfMax : v; }
 
+// SEGMENT, the header's rule with the division multiplied out: with t = major - major0 in [0, D], d = the signed minor extent and
+// k = minor - minor0, k == floor((2 t d + D) / (2 D)) iff 2 D k <= 2 t d + D < 2 D k + 2 D.  All in 64-bit integers: the
+// coordinates are clamped to +-2^20, so D, |d| <= 2^21, |k| <= 2^21 and no product passes 2^44.  D == 0: the single pixel.
+SL2_HD bool overlay_segment_covers(int D, int d, int t, int k) {
+  if (D == 0) return t == 0 && k == 0;
+  const long long n = 2ll * t * d + D, lo = 2ll * D * k;
+  return lo <= n && n < lo + 2ll * D;
+}
+
 // False: the item draws nothing (unknown kind, patch index outside the array, invalid ring, inverted rectangle).
 SL2_HD bool overlay_prepare(const sl2_overlay_item& it, int npatches, OverlayPrep* p) {
   p->kind = it.kind;
@@ -64,6 +76,15 @@ SL2_HD bool overlay_prepare(const sl2_overlay_item& it, int npatches, OverlayPre
   const int a0 = overlay_clampc(it.a[0]), a1 = overlay_clampc(it.a[1]), a2 = overlay_clampc(it.a[2]), a3 = overlay_clampc(it.a[3]);
   p->cx = a0; p->cy = a1;
   p->bx0 = p->by0 = 0; p->bx1 = p->by1 = -1;
+  if (it.kind == SL2_ITEM_SEGMENT) {      // (its ends are pulled in like a rectangle's corners)
+    const int dx = a2 - a0, dy = a3 - a1, adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
+    const bool ymajor = adx < ady;
+    // the ends swapped so that the major coordinate does not decrease: the minor one falls iff the two differences differ in sign
+    const bool falls = ymajor ? (dy < 0 ? dx > 0 : dx < 0) : (dx < 0 ? dy > 0 : dy < 0);
+    p->pad = (ymajor ? kSegYMajor : 0) | (falls ? kSegMinorFalls : 0);
+    p->bx0 = a0 < a2 ? a0 : a2; p->bx1 = a0 < a2 ? a2 : a0; p->by0 = a1 < a3 ? a1 : a3; p->by1 = a1 < a3 ? a3 : a1;
+    return true;
+  }
   if (it.kind != SL2_ITEM_RECT && (a0 != it.a[0] || a1 != it.a[1])) return false;
   if (it.kind == SL2_ITEM_RING) {
     if (!overlay_ring_valid(it.q)) return false;
@@ -111,6 +132,15 @@ SL2_HD bool overlay_hit(const OverlayPrep& p, const uint8_t* patches, size_t pat
     }
     return true;
   }
+  if (p.kind == SL2_ITEM_SEGMENT) {
+    const int W = p.bx1 - p.bx0, H = p.by1 - p.by0;      // |dx|, |dy|
+    const bool falls = (p.pad & kSegMinorFalls) != 0;
+    const bool on = (p.pad & kSegYMajor) ? overlay_segment_covers(H, falls ? -W : W, y - p.by0, x - (falls ? p.bx1 : p.bx0))
+                                         : overlay_segment_covers(W, falls ? -H : H, x - p.bx0, y - (falls ? p.by1 : p.by0));
+    if (!on) return false;
+    *rgb = p.rgb;
+    return true;
+  }
   // RECT: the outline of the box
   if (x != p.bx0 && x != p.bx1 && y != p.by0 && y != p.by1) return false;
   *rgb = p.rgb;
@@ -119,7 +149,7 @@ SL2_HD bool overlay_hit(const OverlayPrep& p, const uint8_t* patches, size_t pat
 
 // Why a list cannot be drawn (nullptr: it can): the checks the host makes of a host-resident list.
 inline const char* overlay_item_fault(const sl2_overlay_item& it, int npatches) {
-  if (it.kind != SL2_ITEM_RING && it.kind != SL2_ITEM_PATCH && it.kind != SL2_ITEM_RECT) return "unknown item kind";
+  if (it.kind != SL2_ITEM_RING && it.kind != SL2_ITEM_PATCH && it.kind != SL2_ITEM_RECT && it.kind != SL2_ITEM_SEGMENT) return "unknown item kind";
   if (it.kind == SL2_ITEM_PATCH && (it.patch < 0 || it.patch >= npatches)) return "patch index outside the patches array";
   return nullptr;
 }

@@ -360,6 +360,81 @@ class Engine:
                                           int(out_stride if out_stride else 3 * w * h), 1))
         return out_ptr
 
+    # ---- the rectified view (include/scenelib2_amd.h, "the rectified view") ----
+    def rectify_frames(self, frames, seq0=0, nseq=None, on_device=False, seq_stride=0, out_stride=0):
+        """sl2_rectify_frames with the images returned to the host: uint8 [nseq][height][width] (with out_stride above
+        width height: [nseq][out_stride] bytes, the images at the start of each), sequence seq0 + i undistorted with its own
+        camera (set_cameras).  frames: uint8 [nseq][height][width] in host memory, or with on_device=True a device pointer
+        (seq_stride bytes apart)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(self.cam["width"]), int(self.cam["height"])
+        if on_device:
+            fp, stride, keep = _lib.vp(int(frames)), int(seq_stride if seq_stride else self.frame_bytes), None
+        else:
+            keep = np.ascontiguousarray(frames, dtype=np.uint8).reshape(nseq, -1)
+            fp, stride = keep.ctypes.data_as(_lib.vp), keep.shape[1]
+        ostride = int(out_stride) if out_stride else w * h
+        out = np.zeros((max(nseq, 1), ostride), np.uint8)
+        self._ck(self.L.sl2_rectify_frames(self.h, int(seq0), nseq, fp, stride, int(bool(on_device)), out.ctypes.data_as(_lib.vp), ostride, 0))
+        return out[:nseq].reshape(nseq, h, w) if ostride == w * h else out[:nseq]
+
+    def rectify_frames_device(self, frames_ptr, out_ptr, seq0=0, nseq=None, seq_stride=0, out_stride=0):
+        """sl2_rectify_frames, device form: frames_ptr and out_ptr are device pointers as integers (out must not overlap frames).
+        One launch on the engine's stream and no wait."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(self.cam["width"]), int(self.cam["height"])
+        self._ck(self.L.sl2_rectify_frames(self.h, int(seq0), nseq, _lib.vp(int(frames_ptr)), int(seq_stride if seq_stride else self.frame_bytes), 1,
+                                           _lib.vp(int(out_ptr)), int(out_stride if out_stride else w * h), 1))
+        return out_ptr
+
+    def scene_item_bound(self):
+        """sl2_scene_item_bound for this engine's shape: no sequence's scene list is longer."""
+        kpart = max(1, min(4, self._prm.max_features_to_init_at_once))
+        return int(self.L.sl2_scene_item_bound(self.max_features, kpart))
+
+    def scene_items(self, seq0=0, nseq=None, layers=_lib.SL2_SCENE_ALL, marked=None):
+        """sl2_scene_items, host form: the 3-D scene of sequences seq0 .. seq0 + nseq - 1 in their rectified images (trajectory,
+        feature markers, 3-sigma ellipsoid outlines, rays of partial features) as a list of arrays of _lib.OVERLAY_ITEM_DTYPE.
+        layers: SL2_SCENE_* bits; marked: None or [nseq] labels (-1: none)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        stride = self.scene_item_bound()
+        items = np.zeros((max(nseq, 1), stride), _lib.OVERLAY_ITEM_DTYPE)
+        counts = np.zeros(max(nseq, 1), np.int32)
+        mp, keep = self._marked_arg(marked, nseq)
+        self._ck(self.L.sl2_scene_items(self.h, int(seq0), nseq, int(layers), mp, items.ctypes.data_as(_lib.vp), stride,
+                                        counts.ctypes.data_as(_lib.vp), 0))
+        return [items[i, :counts[i]].copy() for i in range(nseq)]
+
+    def draw_rectified(self, frames, seq0=0, nseq=None, layers=_lib.SL2_SCENE_ALL, marked=None, on_device=False, seq_stride=0,
+                       out_stride=0):
+        """sl2_draw_rectified with the images returned to the host: the undistorted frames with the scene drawn over them,
+        uint8 [nseq][height][width][3] (with out_stride above 3 width height: [nseq][out_stride] bytes).  frames as for
+        draw_overlays."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(self.cam["width"]), int(self.cam["height"])
+        if on_device:
+            fp, stride, keep = _lib.vp(int(frames)), int(seq_stride if seq_stride else self.frame_bytes), None
+        else:
+            keep = np.ascontiguousarray(frames, dtype=np.uint8).reshape(nseq, -1)
+            fp, stride = keep.ctypes.data_as(_lib.vp), keep.shape[1]
+        ostride = int(out_stride) if out_stride else 3 * w * h
+        out = np.zeros((max(nseq, 1), ostride), np.uint8)
+        mp, keep_m = self._marked_arg(marked, nseq)
+        self._ck(self.L.sl2_draw_rectified(self.h, int(seq0), nseq, fp, stride, int(bool(on_device)), int(layers), mp,
+                                           out.ctypes.data_as(_lib.vp), ostride, 0))
+        return out[:nseq].reshape(nseq, h, w, 3) if ostride == 3 * w * h else out[:nseq]
+
+    def draw_rectified_device(self, frames_ptr, out_ptr, seq0=0, nseq=None, layers=_lib.SL2_SCENE_ALL, marked_ptr=None, seq_stride=0,
+                              out_stride=0):
+        """sl2_draw_rectified, device form: frames_ptr, out_ptr and marked_ptr (int32 [nseq] or None) are device pointers as
+        integers.  Three launches on the engine's stream and no wait."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(self.cam["width"]), int(self.cam["height"])
+        self._ck(self.L.sl2_draw_rectified(self.h, int(seq0), nseq, _lib.vp(int(frames_ptr)), int(seq_stride if seq_stride else self.frame_bytes), 1,
+                                           int(layers), _lib.vp(int(marked_ptr)) if marked_ptr else None, _lib.vp(int(out_ptr)),
+                                           int(out_stride if out_stride else 3 * w * h), 1))
+        return out_ptr
+
     def features(self, seq, include_deleted=False):
         arr = (_lib.sl2_feature_info * self.max_features)()
         cnt = C.c_int(0)
@@ -733,6 +808,29 @@ class MonoSLAM:
         if out_rgb is not None:
             out_rgb[...] = img
         return img
+
+    # GraphicTool::DrawRectifiedAR(frame, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties)
+    # — graphictool.cpp:222-283, without OpenGL
+    def DrawRectifiedAR(self, frame, out_rgb=None, chk_display_trajectory=True, chk_display_3d_features=True,
+                        chk_display_3d_uncertainties=True):
+        """The frame with the lens distortion removed and, over it, the trajectory, the 3-D features, their 3-sigma ellipsoids
+        and the rays of partially initialised features (sl2_draw_rectified): uint8 [height][width][3], R, G, B; also written
+        into out_rgb if given.  marked_feature_label_ is drawn green."""
+        layers = (_lib.SL2_SCENE_TRAJECTORY if chk_display_trajectory else 0) | \
+                 (_lib.SL2_SCENE_FEATURES if chk_display_3d_features else 0) | \
+                 (_lib.SL2_SCENE_UNCERTAINTIES if chk_display_3d_uncertainties else 0)
+        img = self._engine.draw_rectified(self._frame(frame), 0, 1, layers, [self.marked_feature_label_])[0]
+        if out_rgb is not None:
+            out_rgb[...] = img
+        return img
+
+    # GraphicTool::DrawAR — graphictool.cpp:177-220: the rectified view or the raw one, by the example's check box
+    def DrawAR(self, frame, out_rgb=None, chk_rectify_image_display=False, chk_display_trajectory=True, chk_display_3d_features=True,
+               chk_display_3d_uncertainties=True, chk_display_2d_descriptors=True, chk_display_2d_search_regions=True,
+               chk_display_initialisation=True):
+        if chk_rectify_image_display:
+            return self.DrawRectifiedAR(frame, out_rgb, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties)
+        return self.DrawRawAR(frame, out_rgb, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation)
 
     def _frame(self, frame):
         f = np.ascontiguousarray(frame, dtype=np.uint8)
