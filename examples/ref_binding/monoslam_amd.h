@@ -125,6 +125,16 @@ class MonoSLAM {             // monoslam.h:69-219
     if (chk_rectify_image_display) DrawRectifiedAR(frame, out_rgb, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties);
     else DrawRawAR(frame, out_rgb, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation);
   }
+  // GraphicTool::Draw3dScene (graphictool.cpp:113-175) with the reference's three check boxes, seen through `view` (sl2_view_look_at;
+  // the pane's GL model-view matrix in the reference): out_rgb becomes the world view, CV_8UC3 in R, G, B order, width x height
+  void Draw3dScene(const sl2_view& view, cv::Mat& out_rgb, int width, int height, const bool& chk_display_trajectory,
+                   const bool& chk_display_3d_features, const bool& chk_display_3d_uncertainties) {
+    out_rgb.create(height, width, CV_8UC3);
+    impl_.marked_feature_label_ = marked_feature_label_;
+    impl_.Draw3dScene(view, out_rgb.data, width, height, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties);
+  }
+  // GraphicTool::Picker (graphictool.cpp:1475-1571): label + 1 of the feature under the click, 0 for none; y runs downwards
+  int Picker(int x, int y, const bool& threed) { return impl_.Picker(x, y, threed); }
   void InitialiseFeature(cv::Mat frame) {                                  // monoslam.cpp:1211-1235: at the clicked (uu_, vv_)
     impl_.uu_ = uu_; impl_.vv_ = vv_;
     impl_.InitialiseFeature(view(frame));

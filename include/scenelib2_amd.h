@@ -50,7 +50,9 @@ extern "C" {
  * sl2_draw_overlays, sl2_draw_items_batch, sl2_draw_items_host, sl2_overlay_item_bound, sl2_overlay_item, SL2_ITEM_*,
  * SL2_OVERLAY_* (annotated frames: the raw-image display of GraphicTool::DrawRawAR as a draw list and a rasteriser);
  * SL2_ITEM_SEGMENT, sl2_rectify_frames, sl2_rectify_frame_host, sl2_scene_items, sl2_scene_item_bound, sl2_draw_rectified,
- * SL2_SCENE_* (the rectified view of GraphicTool::DrawRectifiedAR: a line primitive, the undistorted frame, the 3-D scene). */
+ * SL2_SCENE_* (the rectified view of GraphicTool::DrawRectifiedAR: a line primitive, the undistorted frame, the 3-D scene);
+ * sl2_view, sl2_view_look_at, sl2_world_items, sl2_world_item_bound, sl2_draw_world, SL2_WORLD_*, sl2_pick_items_batch,
+ * sl2_pick_items_host (the world view of GraphicTool::Draw3dScene from a free camera, and GraphicTool::Picker). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -862,6 +864,112 @@ int sl2_scene_items(sl2_engine* e, int seq0, int nseq, int layers, const int32_t
                     sl2_overlay_item* items, int item_stride, int32_t* counts, int on_device);
 int sl2_draw_rectified(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device,
                        int layers, const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device);
+
+/* ---- the world view and picking (additions within SL2_API_VERSION 5): the 3-D scene from a free camera ----
+ *
+ * GraphicTool::Draw3dScene (graphic/graphictool.cpp:113-175) shows the map, the trajectory and the camera FROM OUTSIDE, through a
+ * movable virtual camera; GraphicTool::Picker (1475-1571) answers which feature lies under a click.  Their numerical half is a
+ * DRAW LIST per sequence for the rasteriser above (k_world_list) and a query over any draw list (k_pick_items), both for a
+ * whole batch (sl2_world_view.hip).  No new item kind: RECT, RING and SEGMENT only.
+ *
+ * THE VIEW, sl2_view, 88 bytes: a pinhole camera posed in the world with the reference's conventions, r its position, q = qWR
+ * (w, x, y, z) used AS GIVEN (not normalised: Eigen's inverse() and toRotationMatrix(), as for xv_).  A world point Y has
+ * view-frame coordinates X = zeroedyi((r, q), Y) = RRW (Y - r), the expressions of the sequence's own camera frame, and a
+ * point with X[2] >= 0.01 lies at (u0 - fku X[0]/X[2], v0 - fkv X[1]/X[2]), evaluated as written.
+ * sl2_view_look_at   host only: the view at `eye` whose frame has z towards `target`, x = up x z normalised (image LEFT) and
+ *   y = z x x (image UP), as a unit quaternion with q[0] >= 0.  A point displaced along `up` lands at a smaller v, one to the
+ *   viewer's right at a larger u, the target at (u0, v0).  Refused: a null pointer, a number that is not finite, eye == target,
+ *   `up` zero or parallel to the viewing direction (|up x z| <= 1e-12 |up|).  The reference example's view is
+ *   eye (0, 0.18, -1.4), target (0, 0.13, 0), up (0, 1, 0) (ModelViewLookAt, pangolin_util.cpp) with the camera's intrinsics.
+ *
+ * THE WORLD'S DRAW LIST OF A SEQUENCE, from its CURRENT state, in Draw3dScene's order.  `layers`: SL2_WORLD_TRAJECTORY = 1,
+ * SL2_WORLD_FEATURES = 2, SL2_WORLD_UNCERTAINTIES = 4 (the example's three check boxes), SL2_WORLD_CAMERA = 8, SL2_WORLD_AXES = 16
+ * (the reference always draws the camera, and the axes with the features box).  Colour, `marked`, rounding (int(v + 0.5), C
+ * truncation; not finite or outside +-32767 omits the item) and the rule of a 3-D SEGMENT (steps (1) to (4): near plane 0.01,
+ * projection, Liang-Barsky to the guard square, rounding) are those of the rectified view above, word for word, with the VIEW
+ * in the place of the sequence's camera: "into the view frame" below is X = RRW (Y - r) of the view.
+ *   SL2_WORLD_CAMERA, first (DrawCamera, drawn as wire): 16 segments, colour (150, 150, 150), label -1.  The glyph's frame is
+ *     the world turned by qWO = qWR * (0, 0, 1, 0) = (-qy, -qz, qw, qx) of the current xv_'s (qw, qx, qy, qz), at r of xv_: a
+ *     glyph point g is the world point W[i] = r[i] + ((0.0 + R[i][0] g[0]) + R[i][1] g[1]) + R[i][2] g[2], R =
+ *     toRotationMatrix(qWO) without normalisation, and W is then taken into the view frame.  Edges 0 .. 11 are the body box
+ *     x in {-0.032, 0.026}, y in {-0.034, 0.020}, z in {-0.012, 0.012} (lensposx, lensposy, width, height, depth), a corner
+ *     written (bx, by, bz) with bit 0 = the lower and 1 = the upper value: edge e = 0 .. 3 runs along x from (0, e & 1, e >> 1)
+ *     to (1, e & 1, e >> 1); edge 4 + e along y from (e & 1, 0, e >> 1) to (e & 1, 1, e >> 1); edge 8 + e along z from
+ *     (e & 1, e >> 1, 0) to (e & 1, e >> 1, 1).  Edges 12 .. 15 are the lens's front face at z = -0.017, corners c0 .. c3 =
+ *     (-0.012, -0.012), (0.012, -0.012), (0.012, 0.012), (-0.012, 0.012): edge 12 + k from ck to c((k + 1) % 4).
+ *   SL2_WORLD_TRAJECTORY: consecutive entries of trajectory_store_ as sl2_get_trajectory returns them, both into the view
+ *     frame, the 3-D segment between them; yellow, label -1.
+ *   Then the features in feature_list_ order (one loop, as in Draw3dScene):
+ *   fully initialised live feature, m = y into the view frame:
+ *     SL2_WORLD_FEATURES and m[2] >= 0.01: the filled 3 x 3 marker at the rounded projection, RECT (x-1, y-1, x+1, y+1) then
+ *       RECT (x, y, x, y).
+ *     SL2_WORLD_UNCERTAINTIES: the world-frame ellipsoid (func_yigraphics_and_Pyiyigraphics: y_ and Pyy_ alone, no camera
+ *       uncertainty) in the view frame: Sigma = (Jy Pyy) Jy^T, Jy = RRW of the view, Pyy the feature's block of the current P;
+ *       every inner sum starts at 0.0 and runs over its index upwards: Cm[i][c] = sum_k Jy[i][k] Pyy[k][c],
+ *       Sigma[i][j] = sum_c Cm[i][c] Jy[j][c].  Then the conic of the rectified view above from (m, Sigma) and the view's fku,
+ *       fkv, u0, v0, under the same conditions (d > 0 and m[2] > 0): a RING.
+ *   partially initialised feature, SL2_WORLD_FEATURES: the ray r_i .. r_i + 10.0 hhat_i of its state IN THE WORLD
+ *     (b[k] = r_i[k] + 10.0 * hhat_i[k]), both ends into the view frame, a 3-D segment with the feature's label and colour.
+ *   SL2_WORLD_AXES, last (DrawAxes without letters, tick numbers and lighting): the EXTENTS xmin, xmax, ymin, ymax, zmin, zmax
+ *     start at 0.0 and take in (v < min: min = v; v > max: max = v, per coordinate) r of xv_ and, with SL2_WORLD_FEATURES set,
+ *     y of every fully initialised live feature (UpdateDrawingDimension, graphictool.cpp:126, 138, 155).  Three white segments
+ *     (255, 255, 255), label -1, both ends into the view frame: (xmin,0,0)..(xmax,0,0), (0,ymin,0)..(0,ymax,0),
+ *     (0,0,zmin)..(0,0,zmax).
+ *   No list is longer than sl2_world_item_bound(max_features, partial_slots) = 3 max_features + partial_slots + 999 + 19.
+ *
+ * sl2_world_items   the lists; items, item_stride, counts, marked as sl2_scene_items.  views: nviews == 1 (one view for all
+ *   sequences) or nviews == nseq (view i for sequence seq0 + i).  extents: [nseq][6] doubles or NULL - the EXTENTS above,
+ *   computed whether or not SL2_WORLD_AXES is among the layers: a client fits its next view with them.  on_device == 0: views,
+ *   marked, items, counts, extents are host memory; engine-owned staging, one wait.  on_device != 0: all are device pointers
+ *   (items and views 8-byte aligned); one launch on the engine's stream, no wait.
+ * sl2_draw_world    fill, list and draw with no host round trip: engine-owned staging of nseq grey images of width x height
+ *   (ANY size within 1 .. 32768, not the engine's) is filled with the grey level `background` (0 .. 255), then k_world_list,
+ *   then k_overlay_draw; all stream-ordered.  out: RGB24 image i at out + i * out_stride.  out_on_device == 0: views, marked
+ *   and out are host memory, one wait and one copy of exactly 3 width height bytes per image.  out_on_device != 0: all three
+ *   are device pointers and the call never waits.
+ * Both drop no captured step, change nothing in the engine, do not consult the active mask and work with sequence groups.
+ * Refused (SL2_ERR_INVALID, nothing queued, sl2_last_error() names the call and the sequences): null pointers, a range outside
+ * the batch, nseq < 1, nviews other than 1 or nseq, layers with bits outside SL2_WORLD_ALL, item_stride below the bound, device
+ * items or views not 8-byte aligned, width or height outside 1 .. 32768, background outside 0 .. 255, out_stride below
+ * 3 width height, a HOST-resident view with a number that is not finite (the sequence is named).  A device-resident view cannot
+ * be looked at: one with a number that is not finite lists nothing it touches and cannot fault - every rule above omits an
+ * item whose coordinates are not finite, and every store is bounded by item_stride.
+ *
+ * PICKING (GraphicTool::Picker: gluPickMatrix(x, y, 7, 7) over the names of the drawn features).  The window is the 7 x 7 pixels
+ * centred on the click (x, y), clipped to the image.  The answer is the LAST item in list order with label >= 0 that covers,
+ * by THE PIXEL RULES above, at least one pixel of the window: picked = (its label, its index in the list); (-1, -1) if there
+ * is none.  Items with label -1 neither count nor hide anything (coverage, not visibility: a labelled item under an unlabelled
+ * one is still picked).  A PATCH covers its 13 x 13 square whatever its template holds.  An item that draws nothing (unknown
+ * kind, a ring that fails its own rule, a patch index outside 0 .. npatches - 1, an inverted rectangle) is never picked.  A
+ * click outside the image answers (-1, -1); it is not refused.  The adapters return label + 1, the reference's GL name.
+ * sl2_pick_items_batch   list i at items + i * item_stride with counts[i] items, click i = clicks[2 i], clicks[2 i + 1],
+ *   answer i in picked[2 i], picked[2 i + 1].  on_device != 0: items (8-byte aligned), counts, clicks and picked are device
+ *   pointers; one launch on `stream` (k_pick_items), no wait; a count is clamped to 0 .. item_stride.  on_device == 0: all four
+ *   are host memory; the lists are checked as sl2_draw_items_batch checks them (a count outside 0 .. item_stride, an unknown
+ *   kind or a patch index outside the array is refused, the image named), copied to temporaries, and the call waits.
+ * sl2_pick_items_host    the plain C++ form of one image from the same source as the kernel (no device needed); nothing is
+ *   refused of the items.
+ * Refused: null pointers, nimages < 1, width or height outside 1 .. 32768, item_stride, count or npatches negative, misaligned
+ * device items. */
+enum { SL2_WORLD_TRAJECTORY = 1, SL2_WORLD_FEATURES = 2, SL2_WORLD_UNCERTAINTIES = 4, SL2_WORLD_CAMERA = 8, SL2_WORLD_AXES = 16,
+       SL2_WORLD_ALL = 31 };
+typedef struct sl2_view {
+  double r[3];              /* position in the world */
+  double q[4];              /* qWR (w, x, y, z), used as given */
+  double fku, fkv, u0, v0;
+} sl2_view;                                    /* 88 bytes */
+int sl2_view_look_at(const double eye[3], const double target[3], const double up[3], double fku, double fkv, double u0, double v0,
+                     sl2_view* out);
+/* Host only, no device: the longest world list of a sequence of an engine of this shape; 0 for a negative argument. */
+size_t sl2_world_item_bound(int max_features, int partial_slots);
+int sl2_world_items(sl2_engine* e, int seq0, int nseq, const sl2_view* views, int nviews, int layers, const int32_t* marked,
+                    sl2_overlay_item* items, int item_stride, int32_t* counts, double* extents /* [nseq][6] or NULL */, int on_device);
+int sl2_draw_world(sl2_engine* e, int seq0, int nseq, const sl2_view* views, int nviews, int width, int height, int background,
+                   int layers, const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device);
+int sl2_pick_items_batch(int device, void* stream, int nimages, int width, int height, const sl2_overlay_item* items, int item_stride,
+                         const int32_t* counts, int npatches, const int32_t* clicks /* [nimages][2] x, y */,
+                         int32_t* picked /* [nimages][2] label, item index */, int on_device);
+int sl2_pick_items_host(int width, int height, const sl2_overlay_item* items, int count, int npatches, int x, int y, int32_t picked[2]);
 
 /* selected_feature_list_ (labels, selection order) and per-step counters:
  * counters[0] = number_of_visible_features_, [1] = #selected,

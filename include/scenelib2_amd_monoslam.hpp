@@ -270,6 +270,7 @@ class MonoSLAM {
                        (chk_display_initialisation ? SL2_OVERLAY_INITIALISATION : 0);
     const int32_t marked = marked_feature_label_;
     const size_t px = (size_t)frame.cols * frame.rows;
+    last_ar_kind_ = 1; last_ar_layers_ = layers;      // (Picker: the check boxes of the last call)
     check(sl2_draw_overlays(eng_, 0, 1, frame.data, px, frame.on_device ? 1 : 0, layers, &marked, out_rgb, 3 * px, 0), "sl2_draw_overlays");
   }
 
@@ -285,6 +286,7 @@ class MonoSLAM {
                        (chk_display_3d_uncertainties ? SL2_SCENE_UNCERTAINTIES : 0);
     const int32_t marked = marked_feature_label_;
     const size_t px = (size_t)frame.cols * frame.rows;
+    last_ar_kind_ = 2; last_ar_layers_ = layers;
     check(sl2_draw_rectified(eng_, 0, 1, frame.data, px, frame.on_device ? 1 : 0, layers, &marked, out_rgb, 3 * px, 0), "sl2_draw_rectified");
   }
 
@@ -294,6 +296,45 @@ class MonoSLAM {
               bool chk_display_initialisation) {
     if (chk_rectify_image_display) DrawRectifiedAR(frame, out_rgb, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties);
     else DrawRawAR(frame, out_rgb, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation);
+  }
+
+  // GraphicTool::Draw3dScene (graphic/graphictool.cpp:113-175) without OpenGL: the map, the trajectory and the camera seen through
+  // `view` (sl2_view_look_at; the GL model-view matrix of the reference's pane) over a black background, drawn on the device
+  // (sl2_draw_world) into out_rgb, RGB24 [height][width][3] in host memory, of any size.  The three arguments are the example's
+  // check boxes: the camera is always drawn and the axes with the features, as in the reference; marked_feature_label_ is drawn
+  // green.  The view, the size and the boxes are remembered for Picker.
+  void Draw3dScene(const sl2_view& view, uint8_t* out_rgb, int width, int height, bool chk_display_trajectory, bool chk_display_3d_features,
+                   bool chk_display_3d_uncertainties) {
+    if (!eng_ || !out_rgb) throw std::runtime_error("MonoSLAM::Draw3dScene: not initialised or no output");
+    const int layers = (chk_display_trajectory ? SL2_WORLD_TRAJECTORY : 0) | (chk_display_3d_features ? SL2_WORLD_FEATURES | SL2_WORLD_AXES : 0) |
+                       (chk_display_3d_uncertainties ? SL2_WORLD_UNCERTAINTIES : 0) | SL2_WORLD_CAMERA;
+    const int32_t marked = marked_feature_label_;
+    check(sl2_draw_world(eng_, 0, 1, &view, 1, width, height, 0, layers, &marked, out_rgb, 3 * (size_t)width * (size_t)height, 0), "sl2_draw_world");
+    last_3d_view_ = view; last_3d_width_ = width; last_3d_height_ = height; last_3d_layers_ = layers; last_3d_valid_ = true;
+  }
+
+  // GraphicTool::Picker (graphic/graphictool.cpp:1475-1571): the GL name of the feature under pixel (x, y) - image coordinates, y
+  // downwards - of the last Draw3dScene (threed) or DrawAR image: label + 1, or 0 for none, so that
+  // mark_feature_by_lab(Picker(x, y, true) - 1) reads as in pangolin_util.cpp.  The list of that call is rebuilt from the current
+  // state with the remembered check boxes and view; sl2_pick_items_host answers by the rasteriser's own coverage.
+  int Picker(int x, int y, bool threed) {
+    if (!eng_ || (threed ? !last_3d_valid_ : last_ar_kind_ == 0)) return 0;
+    const int kpart = kMaxFeaturesToInitAtOnce_ < 1 ? 1 : (kMaxFeaturesToInitAtOnce_ > 4 ? 4 : kMaxFeaturesToInitAtOnce_);
+    const size_t bound = threed ? sl2_world_item_bound(max_features_, kpart)
+                                : (last_ar_kind_ == 1 ? sl2_overlay_item_bound(max_features_, kpart) : sl2_scene_item_bound(max_features_, kpart));
+    std::vector<sl2_overlay_item> items(bound);
+    int32_t count = 0, picked[2] = {-1, -1};
+    int w = camera_->width_, h = camera_->height_;
+    if (threed) {
+      w = last_3d_width_; h = last_3d_height_;
+      check(sl2_world_items(eng_, 0, 1, &last_3d_view_, 1, last_3d_layers_, nullptr, items.data(), (int)bound, &count, nullptr, 0), "sl2_world_items");
+    } else if (last_ar_kind_ == 1) {
+      check(sl2_overlay_items(eng_, 0, 1, last_ar_layers_, nullptr, items.data(), (int)bound, &count, 0), "sl2_overlay_items");
+    } else {
+      check(sl2_scene_items(eng_, 0, 1, last_ar_layers_, nullptr, items.data(), (int)bound, &count, 0), "sl2_scene_items");
+    }
+    check(sl2_pick_items_host(w, h, items.data(), count, max_features_, x, y, picked), "sl2_pick_items_host");
+    return picked[0] + 1;
   }
 
   // The seams of GoOneStep, callable one by one like the reference's public members (monoslam.cpp:118-177; kalman.h:51-52
@@ -618,6 +659,10 @@ class MonoSLAM {
   int traj_seen_ = 0, patch_seen_ = 0, status_flags_ = 0;
   std::map<int, std::array<uint8_t, SL2_PATCH_BYTES>> patch_cache_;
   int max_features_, device_;
+  sl2_view last_3d_view_{};                                   // Picker: the view, size and layers of the last Draw3dScene ...
+  int last_3d_width_ = 0, last_3d_height_ = 0, last_3d_layers_ = 0;
+  bool last_3d_valid_ = false;
+  int last_ar_kind_ = 0, last_ar_layers_ = 0;                 // ... and of the last DrawAR: 0 none, 1 raw, 2 rectified
   bool map_full_ = false;
   sl2_engine* eng_ = nullptr;
   sl2_converter* converter_ = nullptr;   // SetFrameSource: raw camera frames in front of GoOneStep

@@ -10,6 +10,8 @@ from .config import load_config, parse_vars_file, read_pgm  # noqa: F401
 from .monoslam import Engine, Feature, MonoSLAM, decode_snapshot  # noqa: F401
 from . import improc  # noqa: F401
 from .convert import FrameConverter, convert_frame_host, scale_camera  # noqa: F401
+from . import world_view  # noqa: F401
+from .world_view import look_at  # noqa: F401
 
 __all__ = ["Engine", "MonoSLAM", "Feature", "load_config", "parse_vars_file", "read_pgm", "FrameConverter",
-           "convert_frame_host", "scale_camera", "decode_snapshot"]
+           "convert_frame_host", "scale_camera", "decode_snapshot", "world_view", "look_at"]

@@ -118,6 +118,18 @@ SL2_OVERLAY_SEARCH_REGIONS, SL2_OVERLAY_DESCRIPTORS, SL2_OVERLAY_INITIALISATION,
 OVERLAY_ITEM_DTYPE = np.dtype([("kind", np.int32), ("label", np.int32), ("a", np.int32, (4,)), ("patch", np.int32),
                                ("rgb", np.uint8, (3,)), ("pad", np.uint8), ("q", np.float64, (4,))])
 assert OVERLAY_ITEM_DTYPE.itemsize == 64
+# the world view (sl2_world_items, sl2_draw_world, sl2_pick_items_*): layer bits and the 88-byte view
+SL2_WORLD_TRAJECTORY, SL2_WORLD_FEATURES, SL2_WORLD_UNCERTAINTIES, SL2_WORLD_CAMERA, SL2_WORLD_AXES, SL2_WORLD_ALL = 1, 2, 4, 8, 16, 31
+
+
+class sl2_view(C.Structure):
+    _fields_ = [("r", C.c_double * 3), ("q", C.c_double * 4), ("fku", C.c_double), ("fkv", C.c_double), ("u0", C.c_double),
+                ("v0", C.c_double)]
+
+
+VIEW_DTYPE = np.dtype([("r", np.float64, (3,)), ("q", np.float64, (4,)), ("fku", np.float64), ("fkv", np.float64),
+                       ("u0", np.float64), ("v0", np.float64)])
+assert C.sizeof(sl2_view) == 88 and VIEW_DTYPE.itemsize == 88
 
 SL2_BLOB_MAGIC = 0x51324C53
 SL2_BLOB_SLOT_ARRAYS = 22
@@ -152,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "sl2_snapshot_bound", "sl2_snapshot_batch",
     "sl2_overlay_item_bound", "sl2_overlay_items", "sl2_draw_items_batch", "sl2_draw_overlays", "sl2_draw_items_host",
     "sl2_rectify_frames", "sl2_rectify_frame_host", "sl2_scene_item_bound", "sl2_scene_items", "sl2_draw_rectified",
+    "sl2_view_look_at", "sl2_world_item_bound", "sl2_world_items", "sl2_draw_world", "sl2_pick_items_batch", "sl2_pick_items_host",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures"]
@@ -308,6 +321,14 @@ def _bind(L):
         L.sl2_scene_item_bound.restype = C.c_size_t
         L.sl2_scene_items.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int]
         L.sl2_draw_rectified.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_world_items"):
+        L.sl2_view_look_at.argtypes = [c_dp, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+        L.sl2_world_item_bound.argtypes = [C.c_int, C.c_int]
+        L.sl2_world_item_bound.restype = C.c_size_t
+        L.sl2_world_items.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int]
+        L.sl2_draw_world.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int]
+        L.sl2_pick_items_batch.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int]
+        L.sl2_pick_items_host.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     return L
 
 

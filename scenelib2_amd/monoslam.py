@@ -435,6 +435,61 @@ class Engine:
                                            int(out_stride if out_stride else 3 * w * h), 1))
         return out_ptr
 
+    # ---- the world view (include/scenelib2_amd.h, "the world view and picking") ----
+    def world_item_bound(self):
+        """sl2_world_item_bound for this engine's shape: no sequence's world list is longer."""
+        kpart = max(1, min(4, self._prm.max_features_to_init_at_once))
+        return int(self.L.sl2_world_item_bound(self.max_features, kpart))
+
+    @staticmethod
+    def _views_arg(views, nseq):
+        """One view (world_view.look_at / world_view.view) or a sequence of nseq of them, as a contiguous VIEW_DTYPE array."""
+        v = np.atleast_1d(np.ascontiguousarray(views, dtype=_lib.VIEW_DTYPE)).reshape(-1)
+        if v.size not in (1, nseq):
+            raise ValueError("one view, or one per sequence")
+        return v
+
+    def world_items(self, views, seq0=0, nseq=None, layers=_lib.SL2_WORLD_ALL, marked=None):
+        """sl2_world_items, host form: the 3-D scene of sequences seq0 .. seq0 + nseq - 1 seen through `views` (one, or one per
+        sequence) - camera glyph, trajectory, feature markers, 3-sigma ellipsoid outlines, rays, axes - as (lists, extents):
+        a list of arrays of _lib.OVERLAY_ITEM_DTYPE and float64 [nseq][6] = xmin, xmax, ymin, ymax, zmin, zmax of each map.
+        layers: SL2_WORLD_* bits; marked: None or [nseq] labels (-1: none)."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        stride = self.world_item_bound()
+        v = self._views_arg(views, nseq)
+        items = np.zeros((max(nseq, 1), stride), _lib.OVERLAY_ITEM_DTYPE)
+        counts = np.zeros(max(nseq, 1), np.int32)
+        extents = np.zeros((max(nseq, 1), 6), np.float64)
+        mp, keep = self._marked_arg(marked, nseq)
+        self._ck(self.L.sl2_world_items(self.h, int(seq0), nseq, v.ctypes.data_as(_lib.vp), v.size, int(layers), mp,
+                                        items.ctypes.data_as(_lib.vp), stride, counts.ctypes.data_as(_lib.vp),
+                                        extents.ctypes.data_as(_lib.vp), 0))
+        return [items[i, :counts[i]].copy() for i in range(nseq)], extents[:nseq]
+
+    def draw_world(self, views, width, height, seq0=0, nseq=None, background=0, layers=_lib.SL2_WORLD_ALL, marked=None, out_stride=0):
+        """sl2_draw_world with the images returned to the host: the world view of every sequence of the range over a constant
+        grey background, uint8 [nseq][height][width][3] (with out_stride above 3 width height: [nseq][out_stride] bytes).  The
+        size is the caller's, not the engine's."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        w, h = int(width), int(height)
+        v = self._views_arg(views, nseq)
+        ostride = int(out_stride) if out_stride else 3 * w * h
+        out = np.zeros((max(nseq, 1), max(ostride, 1)), np.uint8)
+        mp, keep_m = self._marked_arg(marked, nseq)
+        self._ck(self.L.sl2_draw_world(self.h, int(seq0), nseq, v.ctypes.data_as(_lib.vp), v.size, w, h, int(background), int(layers), mp,
+                                       out.ctypes.data_as(_lib.vp), ostride, 0))
+        return out[:nseq].reshape(nseq, h, w, 3) if ostride == 3 * w * h else out[:nseq]
+
+    def draw_world_device(self, views_ptr, nviews, width, height, out_ptr, seq0=0, nseq=None, background=0, layers=_lib.SL2_WORLD_ALL,
+                          marked_ptr=None, out_stride=0):
+        """sl2_draw_world, device form: views_ptr (nviews sl2_view records), out_ptr and marked_ptr (int32 [nseq] or None) are
+        device pointers as integers.  A fill and two launches on the engine's stream and no wait."""
+        nseq = self.batch - seq0 if nseq is None else int(nseq)
+        self._ck(self.L.sl2_draw_world(self.h, int(seq0), nseq, _lib.vp(int(views_ptr)), int(nviews), int(width), int(height), int(background),
+                                       int(layers), _lib.vp(int(marked_ptr)) if marked_ptr else None, _lib.vp(int(out_ptr)),
+                                       int(out_stride if out_stride else 3 * int(width) * int(height)), 1))
+        return out_ptr
+
     def features(self, seq, include_deleted=False):
         arr = (_lib.sl2_feature_info * self.max_features)()
         cnt = C.c_int(0)
@@ -696,6 +751,8 @@ class MonoSLAM:
         self.uu_, self.vv_ = 0, 0                   # image selection (set by the GUI's mouse handler in the reference)
         self.location_selected_flag_ = False
         self.marked_feature_label_ = -1             # monoslam.h:171
+        self._last_3d = None                        # Picker: the view, size and layers of the last Draw3dScene ...
+        self._last_ar = None                        # ... and the kind and layers of the last DrawAR
         self._converter = None                      # SetFrameSource: raw camera frames in front of GoOneStep
         self._frame_dev = None
         self._frame_filter = "linear"               # SetFrameFilter
@@ -804,6 +861,7 @@ class MonoSLAM:
         layers = (_lib.SL2_OVERLAY_SEARCH_REGIONS if chk_display_2d_search_regions else 0) | \
                  (_lib.SL2_OVERLAY_DESCRIPTORS if chk_display_2d_descriptors else 0) | \
                  (_lib.SL2_OVERLAY_INITIALISATION if chk_display_initialisation else 0)
+        self._last_ar = ("raw", layers)             # (Picker: the check boxes of the last call)
         img = self._engine.draw_overlays(self._frame(frame), 0, 1, layers, [self.marked_feature_label_])[0]
         if out_rgb is not None:
             out_rgb[...] = img
@@ -819,6 +877,7 @@ class MonoSLAM:
         layers = (_lib.SL2_SCENE_TRAJECTORY if chk_display_trajectory else 0) | \
                  (_lib.SL2_SCENE_FEATURES if chk_display_3d_features else 0) | \
                  (_lib.SL2_SCENE_UNCERTAINTIES if chk_display_3d_uncertainties else 0)
+        self._last_ar = ("rectified", layers)
         img = self._engine.draw_rectified(self._frame(frame), 0, 1, layers, [self.marked_feature_label_])[0]
         if out_rgb is not None:
             out_rgb[...] = img
@@ -831,6 +890,44 @@ class MonoSLAM:
         if chk_rectify_image_display:
             return self.DrawRectifiedAR(frame, out_rgb, chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties)
         return self.DrawRawAR(frame, out_rgb, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation)
+
+    # GraphicTool::Draw3dScene(chk_display_trajectory, chk_display_3d_features, chk_display_3d_uncertainties)
+    # — graphictool.cpp:113-175, without OpenGL: the view is the caller's (world_view.look_at), not a GL model-view matrix
+    def Draw3dScene(self, view, out_rgb=None, width=None, height=None, chk_display_trajectory=True, chk_display_3d_features=True,
+                    chk_display_3d_uncertainties=True):
+        """The map, the trajectory and the camera seen through `view` over a black background (sl2_draw_world): uint8
+        [height][width][3], R, G, B (the camera's size by default); also written into out_rgb if given.  The camera is always
+        drawn and the axes with the features, as in the reference; marked_feature_label_ is drawn green."""
+        w = int(self.camera_["width"] if width is None else width)
+        h = int(self.camera_["height"] if height is None else height)
+        layers = (_lib.SL2_WORLD_TRAJECTORY if chk_display_trajectory else 0) | \
+                 (_lib.SL2_WORLD_FEATURES | _lib.SL2_WORLD_AXES if chk_display_3d_features else 0) | \
+                 (_lib.SL2_WORLD_UNCERTAINTIES if chk_display_3d_uncertainties else 0) | _lib.SL2_WORLD_CAMERA
+        self._last_3d = (np.array(view, dtype=_lib.VIEW_DTYPE), w, h, layers)
+        img = self._engine.draw_world(view, w, h, 0, 1, 0, layers, [self.marked_feature_label_])[0]
+        if out_rgb is not None:
+            out_rgb[...] = img
+        return img
+
+    # GraphicTool::Picker(x, y, ..., threed) — graphictool.cpp:1475-1571: the GL name (label + 1) under the click, 0 for none
+    def Picker(self, x, y, threed=True):
+        """The feature under pixel (x, y) of the last Draw3dScene (threed) or DrawAR image, image coordinates with y downwards:
+        the list of that call is rebuilt from the current state with the remembered check boxes and view, and
+        sl2_pick_items_host answers.  Returns label + 1, the reference's name convention, or 0:
+        mark_feature_by_lab(Picker(x, y) - 1) reads as in pangolin_util.cpp."""
+        from . import world_view
+        if threed:
+            if self._last_3d is None:
+                return 0
+            view, w, h, layers = self._last_3d
+            items = self._engine.world_items(view, 0, 1, layers)[0][0]
+        else:
+            if self._last_ar is None:
+                return 0
+            kind, layers = self._last_ar
+            w, h = int(self.camera_["width"]), int(self.camera_["height"])
+            items = (self._engine.overlay_items(0, 1, layers) if kind == "raw" else self._engine.scene_items(0, 1, layers))[0]
+        return world_view.pick_items_host(w, h, items, x, y, npatches=self._engine.max_features)[0] + 1
 
     def _frame(self, frame):
         f = np.ascontiguousarray(frame, dtype=np.uint8)
