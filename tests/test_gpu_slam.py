@@ -569,7 +569,8 @@ def test_build_variants_of_the_test_library(build_variant, n_features, monkeypat
 def test_both_substitution_kernels_on_small_batches(n_features, monkeypatch):
     """Up to eight sequences the forward substitution runs in k_fwdsub_ksplit (a block row's products dealt to four waves), larger
     batches in k_fwdsub_lds; SL2_NO_KSPLIT (a development switch of the TEST build, read when the engine is created) forces the
-    latter.  Both must stay on the oracle at every block count from one to seven, and agree with each other to rounding."""
+    latter.  Both must stay on the oracle at 1, 2, 4 and 7 blocks (5, 24, 60 and 100 features; tests/test_gpu_ekf_update_edges.py
+    runs every block count from 1 to 13), and agree with each other to rounding."""
     from scenelib2_amd import _lib
     states = []
     for no_ksplit in (False, True):

@@ -2,8 +2,9 @@
 
 Truth is independent of the kernel under test.  An engine is stepped by the seams - predict, select, make_measurements -;
 features(seq) and total_covariance(seq) then hold the measurement Jacobians, the innovations and the PRIOR covariance.  H and
-S = H P H^T + R are built here in np.longdouble, S is factored by a hand-written Cholesky and L w = nu is solved in
-np.longdouble as well; only then does the engine's kalman_filter_update run, and step_stats is read.
+S = H P H^T + R are built in np.longdouble, S is factored by a hand-written Cholesky and L w = nu is solved in
+np.longdouble as well (tests/ekf_update_truth.py, shared with the posterior's truth); only then does the engine's
+kalman_filter_update run, and step_stats is read.
 
 Tolerances: nis, min_pivot, max_pivot: relative error <= 8 m 2^-53 cond(S), the forward-error shape of a Cholesky
 solve; log_det_S: absolute error <= 8 m 2^-53 (cond(S) + sum |log L_rr|); cond(S) by np.linalg.cond in the test.  worst_feature_d2
@@ -12,6 +13,7 @@ determinism statement: exact equality.  Each test asserts the `dof` it means to 
 import numpy as np
 import pytest
 
+from ekf_update_truth import chol_solve_longdouble, innovation_system, measured_features
 from mapping_helpers import make_mapping_sequence
 from scenelib2_amd import Engine, _lib, synth
 from slam_helpers import Pair
@@ -24,42 +26,15 @@ INT_FIELDS = ("stepped", "status_flags", "sequence_steps", "n_features", "n_part
 DBL_FIELDS = ("nis", "log_det_S", "min_pivot", "max_pivot", "worst_feature_d2", "position_var")
 
 
-def chol_solve_longdouble(S, nu):
-    """L (S = L L^T, column by column) and w = L^-1 nu in np.longdouble."""
-    m = S.shape[0]
-    L = np.zeros((m, m), dtype=np.longdouble)
-    for j in range(m):
-        d = S[j, j] - L[j, :j] @ L[j, :j]
-        assert d > 0
-        L[j, j] = np.sqrt(d)
-        if j + 1 < m:
-            L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
-    w = np.zeros(m, dtype=np.longdouble)
-    for j in range(m):
-        w[j] = (nu[j] - L[j, :j] @ w[:j]) / L[j, j]
-    return L, w
-
-
 def truth_before_update(e, b):
     """Call between make_measurements and kalman_filter_update: what the record of sequence b must say after the update."""
-    feats = e.features(b)
-    ok = [f for f in feats if f["selected"] and f["success"]]      # feature_list_ order = slot order = the rows' order
+    ok = measured_features(e, b)                                   # feature_list_ order = slot order = the rows' order
     m = 2 * len(ok)
     t = dict(dof=m, n_matched=len(ok), worst_label=-1, worst_feature_d2=0.0, nis=0.0, log_det_S=0.0, min_pivot=0.0, max_pivot=0.0,
              cond=1.0, sum_abs_log=0.0, cond_worst=1.0)
     if not m:
         return t
-    P = e.total_covariance(b).astype(np.longdouble)
-    n = P.shape[0]
-    Hx = np.concatenate([f["dh_by_dxp"] for f in ok]).astype(np.longdouble)            # [m][7]
-    Hy = np.concatenate([f["dh_by_dy"] for f in ok]).astype(np.longdouble)             # [m][3]
-    pos = np.repeat([f["pos"] for f in ok], 2)
-    assert (pos >= 13).all() and (pos + 3 <= n).all()
-    cols = pos[:, None] + np.arange(3)[None, :]                                        # [m][3]
-    A = Hx @ P[:7, :] + np.einsum("rk,rkn->rn", Hy, P[cols])                            # H P, row by row (10 non-zeros a row)
-    S = A[:, :7] @ Hx.T + np.einsum("rck,ck->rc", A[:, cols], Hy)                      # (H P) H^T
-    S = S + np.diag(np.repeat([f["R"] for f in ok], 2).astype(np.longdouble))
-    nu = np.concatenate([f["nu"] for f in ok]).astype(np.longdouble)
+    _, S, nu = innovation_system(e.total_covariance(b), ok)        # tests/ekf_update_truth.py: H P, S and nu in np.longdouble
     L, w = chol_solve_longdouble(S, nu)
     d = np.diag(L)
     t.update(nis=float(w @ w), log_det_S=float(2 * np.log(d).sum()), min_pivot=float(d.min()), max_pivot=float(d.max()),
