@@ -220,9 +220,11 @@ struct sl2_engine : sl2::SeqArrays {
   size_t snapb_stage_bytes = 0;
   void* snapb_aux = nullptr;      // device: its offsets [B + 1] (uint64), then its cursors [B][2] (int32)
   void* snapb_aux_host = nullptr; // pinned host memory of the same layout: the cursors on their way in, the offsets on their way out
-  void* ovl_lists = nullptr;      // device: the draw lists of sl2_overlay_items' host form and of sl2_draw_overlays: items, counts, marked labels (first use; grown on demand)
+  void* ovl_lists = nullptr;      // device: the draw lists of the host forms of sl2_overlay_items, sl2_scene_items and sl2_world_items and of sl2_draw_overlays,
+                                  // sl2_draw_rectified and sl2_draw_world: items, counts, marked labels, views, extents (sl2_display.hpp: ListStage; first use, grown on demand)
   size_t ovl_lists_bytes = 0;
-  void* ovl_images = nullptr;     // device: host frames on their way in and RGB images on their way out of sl2_draw_overlays (first use; grown on demand)
+  void* ovl_images = nullptr;     // device: host frames on their way in, grey frames and images on their way out of sl2_draw_overlays, sl2_rectify_frames,
+                                  // sl2_draw_rectified and sl2_draw_world (sl2_display.hpp: draw_call; first use, grown on demand)
   size_t ovl_images_bytes = 0;
   void* acc_dev = nullptr;        // device scratch of the get / set accessors (grown on demand)
   size_t acc_dev_bytes = 0;
@@ -298,15 +300,6 @@ int launch_small_back(sl2_engine* e, int save_trajectory, int panel_w);   // (Gr
 int launch_update(sl2_engine* e);
 int launch_syrk_on(sl2_engine* e, const double* Vt, double* P);
 int launch_finalize(sl2_engine* e, int save_trajectory);
-// sl2_overlay.hip, shared with the rectified view (sl2_rectify.hip): the rasteriser's launch, the checks of an image geometry
-// (nullptr: fine), the text of a refusal that a range shares, and the engine-owned staging of lists and images
-int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, int nimages, int width, int height, const sl2_overlay_item* d_items,
-                int item_stride, const int32_t* d_counts, const uint8_t* d_patches, size_t patch_stride, int npatches, uint8_t* d_out, size_t out_stride);
-const char* geometry_fault(int nimages, int width, int height, size_t seq_stride, size_t out_stride);
-std::string range_text(const char* fn, const char* noun, int first, int count, const char* what);
-int grow_device(void** p, size_t* have, size_t need);
-struct ListStage { sl2_overlay_item* items; int32_t* counts; int32_t* marked; };
-int list_stage(sl2_engine* e, int nseq, size_t stride, ListStage* st);
 int launch_mapping(sl2_engine* e, const TailPlan& tp);
 int launch_manual_init(sl2_engine* e, const int* d_uv);
 int launch_auto_init(sl2_engine* e);

@@ -1,56 +1,50 @@
 // Annotated frames (include/scenelib2_amd.h, "annotated frames"): the numerical half of
 // GraphicTool::DrawRawAR (graphic/graphictool.cpp:285-364) for a range of sequences - a draw list per sequence (k_overlay_list)
 // and a rasteriser (k_overlay_draw).  Two stream-ordered launches; no workgroup waits for another.  The pixel rules are
-// sl2_overlay_dev.hpp's, shared with sl2_draw_items_host.
-#include "sl2_common.hpp"
-#include "sl2_overlay_dev.hpp"
+// sl2_overlay_dev.hpp's, shared with sl2_draw_items_host.  The plain functions of sl2_display.hpp, which the three views share,
+// are defined here.
+#include "sl2_display.hpp"
+#include "sl2_drawlist_dev.hpp"
 
 namespace sl2 {
 
 static_assert(sizeof(sl2_overlay_item) == 64, "sl2_overlay_item is 64 bytes");
 static_assert(sizeof(OverlayPrep) == 72, "OverlayPrep");
 
-constexpr int kListThreads = 256;
-constexpr int kListSeqs = kListThreads / 64;      // sequences per workgroup of k_overlay_list, a wavefront each
 constexpr int kDrawThreads = 256;
 constexpr int kTileW = 64, kTileH = 16;           // a thread owns 4 consecutive pixels of a row
 constexpr int kDrawChunk = kDrawThreads;          // items culled and staged per round, one per thread: 18 KB of LDS
 constexpr int kMaxParticlesDrawn = 19;            // what the reference's counter lets through at most
 
-// ---- 1. the draw list of sequence seq0 + i: one wavefront, a lane per slot, 64 slots a round.  Every lane counts its slot's
-// items, a shuffle scan places them in slot order, then every lane writes its own.  Nothing is stored at or beyond item_stride.
+// ---- 1. the draw list of sequence seq0 + i: one wavefront (sl2_drawlist_dev.hpp), a lane per slot, 64 slots a round.  Every lane
+// counts its slot's items, the writer places them in slot order, then every lane writes its own.
 // patch_mode 0: an item's patch is i * N + the feature's index in feature_list_ order (the public list); 1: seq * N + slot, the
 // index into the engine's own template array (sl2_draw_overlays).
 __global__ void __launch_bounds__(kListThreads) k_overlay_list(const SeqArrays S, int seq0, int nseq, int N, int ld, int pcap, int kpart, int width,
                                                                int height, int layers, int patch_mode, const int32_t* __restrict__ marked,
                                                                sl2_overlay_item* __restrict__ items, int item_stride, int32_t* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * kListSeqs + (threadIdx.x >> 6);
-  if (i >= nseq) return;                               // (a whole wavefront)
-  const int seq = seq0 + i;
-  const size_t o = (size_t)seq * N;
-  const int ns = min(max(S.n_slots[seq], 0), N);
+  SeqWave q;
+  if (!seq_wave(S, seq0, nseq, N, ld, kpart, marked, &q)) return;
+  const int lane = q.lane, seq = q.seq, mark = q.mark;
+  const size_t o = q.o;
+  const double* xb = q.xb;
   const CameraParams cam = load_cam(S.seq_cam, seq, width, height);
-  const double* xb = S.x + (size_t)seq * ld;
-  const int* psb = S.ps_i + (size_t)seq * kpart * kPsInts;
-  const int mark = marked ? marked[i] : -1;
-  sl2_overlay_item* list = items + (size_t)i * item_stride;
+  ListWriter w(items, q.i, item_stride, lane);
   double xp[7];
   for (int k = 0; k < 7; ++k) xp[k] = xb[k];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int total = 0, nlive = 0;                            // wave-uniform
-  for (int base = 0; base < ns; base += 64) {
+  int nlive = 0;                                       // wave-uniform: the live features of the rounds before
+  for (int base = 0; base < q.ns; base += 64) {
     const int f = base + lane;
-    const int fl = f < ns ? S.f_flags[o + f] : 0;
-    const bool part = (fl & FF_PARTIAL) != 0, full = !part && (fl & FF_ACTIVE) != 0;
+    const SlotClass s = classify_slot(S, o, f, q.ns);
+    const int fl = s.fl, label = s.label;
+    const bool part = s.part, full = s.full;
     const unsigned long long m_live = __ballot(part || full);
-    const int li = nlive + __popcll(m_live & below);
-    const int label = (part || full) ? S.f_label[o + f] : -1;
+    const int li = nlive + __popcll(m_live & w.below);
     int c = 0;
     bool has_ring = false, has_patch = false;      // (two named records, not an array: an index known only at run time would put them in scratch)
     sl2_overlay_item it_ring = overlay_blank_item(SL2_ITEM_RING, label), it_patch = overlay_blank_item(SL2_ITEM_PATCH, label);
     // the partial slot whose label sits in feature slot f, and its drawn particles
-    int ks = -1, np = 0, step = 1;
+    int np = 0, step = 1;
     const double* pp = nullptr;
     if (full) {
       double zeroed[3], hi[2], Hx[14], Hy[6], Rn;
@@ -62,27 +56,23 @@ __global__ void __launch_bounds__(kListThreads) k_overlay_list(const SeqArrays S
         int cx, cy;
         if ((layers & SL2_OVERLAY_SEARCH_REGIONS) && sel && overlay_round(S.f_h[(o + f) * 2], &cx) && overlay_round(S.f_h[(o + f) * 2 + 1], &cy)) {
           const double* Sf = S.f_S + (o + f) * 4;
+          it_ring = draw_item(SL2_ITEM_RING, label, cx, cy, 0, 0, rgb);
           sl2_overlay_item& r = it_ring;
-          r.a[0] = cx; r.a[1] = cy;
-          r.rgb[0] = rgb[0]; r.rgb[1] = rgb[1]; r.rgb[2] = rgb[2];
           r.q[0] = Sf[3]; r.q[1] = -(Sf[1] + Sf[2]); r.q[2] = Sf[0]; r.q[3] = 9.0 * (Sf[0] * Sf[3] - Sf[1] * Sf[2]);
           has_ring = true;
         }
         const double px = (sel && ok) ? S.f_z[(o + f) * 2] : hi[0], py = (sel && ok) ? S.f_z[(o + f) * 2 + 1] : hi[1];
         if ((layers & SL2_OVERLAY_DESCRIPTORS) && overlay_round(px, &cx) && overlay_round(py, &cy)) {
-          sl2_overlay_item& r = it_patch;
-          r.a[0] = cx; r.a[1] = cy;
-          r.rgb[0] = rgb[0]; r.rgb[1] = rgb[1]; r.rgb[2] = rgb[2];
-          r.patch = patch_mode ? seq * N + f : i * N + li;
+          it_patch = draw_item(SL2_ITEM_PATCH, label, cx, cy, 0, 0, rgb);
+          it_patch.patch = patch_mode ? seq * N + f : q.i * N + li;
           has_patch = true;
         }
         c = (has_ring ? 1 : 0) + (has_patch ? 1 : 0);
       }
     } else if (part && (layers & SL2_OVERLAY_SEARCH_REGIONS)) {
-      for (int k = 0; k < kpart; ++k)
-        if (psb[k * kPsInts + kPsActive] && psb[k * kPsInts + kPsLabel] == f) ks = k;
+      const int ks = partial_slot_of(q.psb, kpart, f);
       if (ks >= 0) {
-        np = min(max(psb[ks * kPsInts + kPsNp], 0), pcap);
+        np = min(max(q.psb[ks * kPsInts + kPsNp], 0), pcap);
         step = overlay_particle_step(np);
         pp = S.particles + ((size_t)seq * kpart + ks) * pcap * kParticleDoubles;
         int cx, cy;
@@ -91,13 +81,10 @@ __global__ void __launch_bounds__(kListThreads) k_overlay_list(const SeqArrays S
         if (c > kMaxParticlesDrawn) c = kMaxParticlesDrawn;      // (cannot happen: n < 20 passes n, n >= 20 passes n / (n / 10) <= 19)
       }
     }
-    int incl = c;
-    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-    int at = total + incl - c;
+    int at = w.reserve(c);
     if (full) {
-      if (has_ring && at < item_stride) list[at] = it_ring;
-      if (has_ring) ++at;
-      if (has_patch && at < item_stride) list[at] = it_patch;
+      if (has_ring) w.put(at++, it_ring);
+      if (has_patch) w.put(at, it_patch);
     } else if (c > 0) {
       uint8_t rgb[3];
       overlay_colour(label == mark, false, false, rgb);
@@ -105,36 +92,22 @@ __global__ void __launch_bounds__(kListThreads) k_overlay_list(const SeqArrays S
       for (int k = 0; k < np && written < c; ++k)
         if ((k + 1) % step == 0 && overlay_round(pp[(size_t)k * kParticleDoubles + 3], &cx) && overlay_round(pp[(size_t)k * kParticleDoubles + 4], &cy)) {
           const double* p = pp + (size_t)k * kParticleDoubles;
-          sl2_overlay_item r = overlay_blank_item(SL2_ITEM_RING, label);
-          r.a[0] = cx; r.a[1] = cy;
-          r.rgb[0] = rgb[0]; r.rgb[1] = rgb[1]; r.rgb[2] = rgb[2];
+          sl2_overlay_item r = draw_item(SL2_ITEM_RING, label, cx, cy, 0, 0, rgb);
           r.q[0] = p[7]; r.q[1] = 2.0 * p[8]; r.q[2] = p[9]; r.q[3] = 9.0;
-          if (at + written < item_stride) list[at + written] = r;
+          w.put(at + written, r);
           ++written;
         }
     }
-    total += __shfl(incl, 63);
     nlive += __popcll(m_live);
   }
-  if (lane != 0) return;
-  if (layers & SL2_OVERLAY_INITIALISATION) {
+  if (lane == 0 && (layers & SL2_OVERLAY_INITIALISATION)) {      // the two boxes of the feature being initialised, behind the features
     const int* pi = S.part_i + (size_t)seq * kPartInts;
-    if (pi[kPartCreated]) {
-      sl2_overlay_item r = overlay_blank_item(SL2_ITEM_RECT, -1);
-      r.a[0] = pi[kPartUU] - 6; r.a[1] = pi[kPartVV] - 6; r.a[2] = pi[kPartUU] + 6; r.a[3] = pi[kPartVV] + 6;
-      r.rgb[1] = 255;
-      if (total < item_stride) list[total] = r;
-      ++total;
-    }
-    if (pi[kPartRegionValid]) {
-      sl2_overlay_item r = overlay_blank_item(SL2_ITEM_RECT, -1);
-      for (int k = 0; k < 4; ++k) r.a[k] = pi[kPartRegion + k];
-      r.rgb[1] = 255;
-      if (total < item_stride) list[total] = r;
-      ++total;
-    }
+    const uint8_t green[3] = {0, 255, 0};
+    if (pi[kPartCreated]) w.put(w.total++, draw_item(SL2_ITEM_RECT, -1, pi[kPartUU] - 6, pi[kPartVV] - 6, pi[kPartUU] + 6, pi[kPartVV] + 6, green));
+    if (pi[kPartRegionValid])
+      w.put(w.total++, draw_item(SL2_ITEM_RECT, -1, pi[kPartRegion], pi[kPartRegion + 1], pi[kPartRegion + 2], pi[kPartRegion + 3], green));
   }
-  counts[i] = total < item_stride ? total : item_stride;
+  w.finish(counts, q.i);
 }
 
 // ---- 2. the rasteriser: a workgroup per (image, tile of 64 x 16 pixels), a thread per 4 consecutive pixels of a row.  The list
@@ -210,19 +183,32 @@ static std::string at_text(const char* fn, const char* noun, int idx, const char
   snprintf(buf, sizeof(buf), "%s: %s %d: %s", fn, noun, idx, what);
   return buf;
 }
-// a fault that every sequence or image of the call shares (a stride, the geometry, a pointer): the range is named
 std::string range_text(const char* fn, const char* noun, int first, int count, const char* what) {
   char buf[256];
   snprintf(buf, sizeof(buf), "%s: %s %d .. %d: %s", fn, noun, first, first + (count > 0 ? count : 1) - 1, what);
   return buf;
 }
-// why a range of sequences cannot be served (nullptr: it can)
-static const char* engine_range_fault(const sl2_engine* e, int seq0, int nseq, int layers) {
+const char* range_fault(const sl2_engine* e, int seq0, int nseq, int layers, int all_layers, const char* layers_fault, const char* views_fault) {
   if (!e) return "null engine";
   if (nseq < 1) return "nseq below 1";
   if (seq0 < 0 || seq0 > e->B - nseq) return "outside the batch";
-  if (layers & ~SL2_OVERLAY_ALL) return "layers with bits outside SL2_OVERLAY_ALL";
+  if (views_fault) return views_fault;
+  if (layers & ~all_layers) return layers_fault;
   return nullptr;
+}
+std::string view_fault_text(const char* fn, int seq0, int nseq, const sl2_view* views, int nviews) {
+  for (int i = 0; i < nviews; ++i) {
+    const sl2_view& v = views[i];
+    const double all[11] = {v.r[0], v.r[1], v.r[2], v.q[0], v.q[1], v.q[2], v.q[3], v.fku, v.fkv, v.u0, v.v0};
+    for (double d : all) {
+      if (overlay_finite(d)) continue;
+      char buf[256];
+      if (nviews == 1) snprintf(buf, sizeof(buf), "%s: sequences %d .. %d: the view holds a number that is not finite", fn, seq0, seq0 + nseq - 1);
+      else snprintf(buf, sizeof(buf), "%s: sequence %d: its view holds a number that is not finite", fn, seq0 + i);
+      return buf;
+    }
+  }
+  return std::string();
 }
 
 int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, int nimages, int width, int height,
@@ -241,7 +227,6 @@ int launch_draw(hipStream_t stream, const uint8_t* d_frames, size_t seq_stride, 
   return SL2_OK;
 }
 
-// what every drawing call checks of its image geometry (nullptr: fine)
 const char* geometry_fault(int nimages, int width, int height, size_t seq_stride, size_t out_stride) {
   if (nimages < 1) return "no images";
   if (width < 1 || height < 1 || width > kOverlayMaxSide || height > kOverlayMaxSide) return "width or height outside 1 .. 32768";
@@ -260,23 +245,34 @@ int grow_device(void** p, size_t* have, size_t need) {
   return SL2_OK;
 }
 
-static int launch_list(sl2_engine* e, int seq0, int nseq, int layers, int patch_mode, const int32_t* d_marked, sl2_overlay_item* d_items, int item_stride,
-                       int32_t* d_counts) {
+static int launch_list(sl2_engine* e, int seq0, int nseq, int layers, int patch_mode, const ListStage& d) {
   // (the root's arrays on the engine's stream, like sl2_snapshot_batch: the groups' streams join it at the end of every stepping call)
   LaunchScope ls(e, "k_overlay_list");
   hipLaunchKernelGGL(k_overlay_list, dim3((nseq + kListSeqs - 1) / kListSeqs), dim3(kListThreads), 0, e->stream, seq_arrays(e), seq0, nseq, e->N, e->ld,
-                     e->pcap, e->kpart, e->cam.width, e->cam.height, layers, patch_mode, d_marked, d_items, item_stride, d_counts);
+                     e->pcap, e->kpart, e->cam.width, e->cam.height, layers, patch_mode, d.marked, d.items, d.stride, d.counts);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 
-// engine-owned list staging: items [nseq][stride], then counts [nseq], then marked [nseq]
-int list_stage(sl2_engine* e, int nseq, size_t stride, ListStage* st) {
-  const size_t item_bytes = sizeof(sl2_overlay_item) * stride * (size_t)nseq;
-  { int _rc = grow_device(&e->ovl_lists, &e->ovl_lists_bytes, item_bytes + 2 * sizeof(int32_t) * (size_t)nseq); if (_rc != SL2_OK) return _rc; }
-  st->items = (sl2_overlay_item*)e->ovl_lists;
-  st->counts = (int32_t*)((char*)e->ovl_lists + item_bytes);
+int list_stage(sl2_engine* e, int nseq, int nviews, size_t stride, ListStage* st) {
+  const size_t item_bytes = sizeof(sl2_overlay_item) * stride * (size_t)nseq, int_bytes = 2 * sizeof(int32_t) * (size_t)nseq;
+  const size_t view_bytes = sizeof(sl2_view) * (size_t)nviews, ext_bytes = 6 * sizeof(double) * (size_t)nseq;
+  { int _rc = grow_device(&e->ovl_lists, &e->ovl_lists_bytes, item_bytes + int_bytes + view_bytes + ext_bytes); if (_rc != SL2_OK) return _rc; }
+  char* p = (char*)e->ovl_lists;
+  st->items = (sl2_overlay_item*)p;
+  st->stride = (int)stride;
+  st->counts = (int32_t*)(p + item_bytes);
   st->marked = st->counts + nseq;
+  st->views = (const sl2_view*)(p + item_bytes + int_bytes);      // (8-byte aligned: 64 stride nseq + 8 nseq)
+  st->extents = (double*)(p + item_bytes + int_bytes + view_bytes);
+  return SL2_OK;
+}
+
+int stage_inputs(sl2_engine* e, int nseq, const sl2_view* views, int nviews, const int32_t* marked, ListStage* st) {
+  if (views) SL2_HIP(hipMemcpyAsync((void*)st->views, views, sizeof(sl2_view) * (size_t)nviews, hipMemcpyHostToDevice, e->stream));
+  else st->views = nullptr;
+  if (marked) SL2_HIP(hipMemcpyAsync((void*)st->marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
+  else st->marked = nullptr;
   return SL2_OK;
 }
 
@@ -306,65 +302,20 @@ extern "C" int sl2_draw_items_host(const uint8_t* frame, int width, int height, 
 
 extern "C" int sl2_overlay_items(sl2_engine* e, int seq0, int nseq, int layers, const int32_t* marked, sl2_overlay_item* items, int item_stride,
                                  int32_t* counts, int on_device) {
-  const char* why = engine_range_fault(e, seq0, nseq, layers);
-  if (!why && (!items || !counts)) why = "null items or counts";
-  if (!why && on_device && (uintptr_t)items % 8) why = "device items not 8-byte aligned";
-  if (!why && (item_stride < 0 || (size_t)item_stride < sl2_overlay_item_bound(e->N, e->kpart))) why = "item_stride below sl2_overlay_item_bound";
-  if (why) { set_error(range_text("sl2_overlay_items", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
-  SL2_HIP(hipSetDevice(e->device));
-  if (on_device) return launch_list(e, seq0, nseq, layers, 0, marked, items, item_stride, counts);
-  ListStage st;
-  { int _rc = list_stage(e, nseq, (size_t)item_stride, &st); if (_rc != SL2_OK) return _rc; }
-  if (marked) SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-  { int _rc = launch_list(e, seq0, nseq, layers, 0, marked ? st.marked : nullptr, st.items, item_stride, st.counts); if (_rc != SL2_OK) return _rc; }
-  // whole strides come back in one copy: the items behind a list's count are not part of it (whatever the staging held)
-  SL2_HIP(hipMemcpyAsync(counts, st.counts, sizeof(int32_t) * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipMemcpyAsync(items, st.items, sizeof(sl2_overlay_item) * (size_t)item_stride * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipStreamSynchronize(e->stream));
-  return SL2_OK;
+  const char* why = range_fault(e, seq0, nseq, layers, SL2_OVERLAY_ALL, "layers with bits outside SL2_OVERLAY_ALL");
+  return items_call("sl2_overlay_items", e, seq0, nseq, why, sl2_overlay_item_bound, "item_stride below sl2_overlay_item_bound", nullptr, 0, marked, items,
+                    item_stride, counts, nullptr, on_device, [&](const ListStage& d) { return launch_list(e, seq0, nseq, layers, 0, d); });
 }
 
 extern "C" int sl2_draw_overlays(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device, int layers,
                                  const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device) {
-  const char* why = engine_range_fault(e, seq0, nseq, layers);
+  const char* why = range_fault(e, seq0, nseq, layers, SL2_OVERLAY_ALL, "layers with bits outside SL2_OVERLAY_ALL");
   if (!why && (!frames || !out)) why = "null frames or out";
   if (!why) why = geometry_fault(nseq, e->cam.width, e->cam.height, seq_stride, out_stride);
   if (why) { set_error(range_text("sl2_draw_overlays", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
-  const int W = e->cam.width, H = e->cam.height;
-  SL2_HIP(hipSetDevice(e->device));
-  const size_t stride = sl2_overlay_item_bound(e->N, e->kpart), px = (size_t)W * H;
-  ListStage st;
-  { int _rc = list_stage(e, nseq, stride, &st); if (_rc != SL2_OK) return _rc; }
-  // image staging: host frames on their way in (packed), then host-bound images on their way out (packed)
-  const size_t in_bytes = frames_on_device ? 0 : ((px * (size_t)nseq + 255) & ~(size_t)255), out_bytes = out_on_device ? 0 : 3 * px * (size_t)nseq;
-  { int _rc = grow_device(&e->ovl_images, &e->ovl_images_bytes, in_bytes + out_bytes); if (_rc != SL2_OK) return _rc; }
-  const uint8_t* d_frames = frames;
-  size_t d_seq_stride = seq_stride;
-  if (!frames_on_device) {
-    SL2_HIP(hipMemcpy2DAsync(e->ovl_images, px, frames, seq_stride, px, (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-    d_frames = (const uint8_t*)e->ovl_images; d_seq_stride = px;
-    // The caller's frames may be pageable memory and may be reused the moment the call returns.  The host form waits at its end
-    // anyway; with the output left on the device this is the one place the call waits: until the frames have been copied.
-    if (out_on_device) SL2_HIP(hipStreamSynchronize(e->stream));
-  }
-  const int32_t* d_marked = marked;
-  if (marked && !out_on_device) {
-    SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-    d_marked = st.marked;
-  }
-  { int _rc = launch_list(e, seq0, nseq, layers, 1, d_marked, st.items, (int)stride, st.counts); if (_rc != SL2_OK) return _rc; }
-  uint8_t* d_out = out_on_device ? out : (uint8_t*)e->ovl_images + in_bytes;
-  const size_t d_out_stride = out_on_device ? out_stride : 3 * px;
-  {
-    LaunchScope ls(e, "k_overlay_draw");
-    int _rc = launch_draw(e->stream, d_frames, d_seq_stride, nseq, W, H, st.items, (int)stride, st.counts, e->patch, (size_t)kPatchStride,
-                          e->B * e->N, d_out, d_out_stride);
-    if (_rc != SL2_OK) return _rc;
-  }
-  if (out_on_device) return SL2_OK;
-  SL2_HIP(hipMemcpy2DAsync(out, out_stride, d_out, 3 * px, 3 * px, (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipStreamSynchronize(e->stream));
-  return SL2_OK;
+  // the rasteriser draws over the caller's frames as they are, and reads the engine's own templates
+  return draw_call(e, nseq, e->cam.width, e->cam.height, sl2_overlay_item_bound(e->N, e->kpart), frames, seq_stride, frames_on_device, nullptr, 0, marked,
+                   e->patch, out, out_stride, out_on_device, nullptr, [&](const ListStage& d) { return launch_list(e, seq0, nseq, layers, 1, d); });
 }
 
 extern "C" int sl2_draw_items_batch(int device, void* stream, const uint8_t* frames, int frames_on_device, int nimages, int width, int height,
@@ -393,19 +344,7 @@ extern "C" int sl2_draw_items_batch(int device, void* stream, const uint8_t* fra
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device (the engine has no CPU fallback)"); return SL2_ERR_NO_DEVICE; }
   SL2_HIP(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  // device temporaries of whatever arrived in host memory, released on every exit path (after the stream has drained)
-  struct Temps {
-    std::vector<void*> p;
-    hipStream_t st;
-    ~Temps() { if (!p.empty()) (void)hipStreamSynchronize(st); for (void* q : p) if (q) (void)hipFree(q); }
-    int alloc(void** o, size_t bytes) {
-      *o = nullptr;
-      const hipError_t e = hipMalloc(o, bytes ? bytes : 1);
-      if (e == hipSuccess) p.push_back(*o);
-      return e == hipSuccess ? SL2_OK : SL2_ERR_HIP;
-    }
-  } tmp;
-  tmp.st = st;
+  DeviceTemps tmp(st);
   const size_t px = (size_t)width * height;
   const uint8_t* d_frames = frames;
   size_t d_seq_stride = seq_stride;

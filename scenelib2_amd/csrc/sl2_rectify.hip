@@ -4,8 +4,8 @@
 // sl2_rectify_dev.hpp's, shared with sl2_rectify_frame_host.  The scene half (DrawRectifiedAR's features, ellipsoids, rays and
 // trajectory) is a draw list per sequence (k_scene_list) for the rasteriser of sl2_overlay.hip; sl2_draw_rectified chains the
 // three launches on the engine's stream.
-#include "sl2_common.hpp"
-#include "sl2_overlay_dev.hpp"
+#include "sl2_display.hpp"
+#include "sl2_drawlist_dev.hpp"
 #include "sl2_rectify_dev.hpp"
 
 namespace sl2 {
@@ -44,70 +44,34 @@ __global__ void __launch_bounds__(kRectThreads) k_rectify(const SeqArrays S, con
   }
 }
 
-// ---- the scene's draw list of sequence seq0 + i: one wavefront, after k_overlay_list's pattern.  First the trajectory, a lane
-// per pair of consecutive entries, 64 pairs a round (each yields one item or none: a ballot places them); then the features, a
-// lane per slot, 64 slots a round (up to three items each: a shuffle scan places them in slot order).  Nothing is stored at or
-// beyond item_stride.
-constexpr int kSceneThreads = 256;
-constexpr int kSceneSeqs = kSceneThreads / 64;
-
-__device__ __forceinline__ sl2_overlay_item scene_item(int kind, int label, int a0, int a1, int a2, int a3, const uint8_t rgb[3]) {
-  sl2_overlay_item it = overlay_blank_item(kind, label);
-  it.a[0] = a0; it.a[1] = a1; it.a[2] = a2; it.a[3] = a3;
-  it.rgb[0] = rgb[0]; it.rgb[1] = rgb[1]; it.rgb[2] = rgb[2];
-  return it;
-}
-
-__global__ void __launch_bounds__(kSceneThreads) k_scene_list(const SeqArrays S, int seq0, int nseq, int N, int ld, int ppos, int kpart, int width,
-                                                              int height, int layers, const int32_t* __restrict__ marked,
-                                                              sl2_overlay_item* __restrict__ items, int item_stride, int32_t* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * kSceneSeqs + (threadIdx.x >> 6);
-  if (i >= nseq) return;                               // (a whole wavefront)
-  const int seq = seq0 + i;
-  const size_t o = (size_t)seq * N;
-  const int ns = min(max(S.n_slots[seq], 0), N);
-  const CameraParams cam = load_cam(S.seq_cam, seq, width, height);
-  const double* xb = S.x + (size_t)seq * ld;
-  const double* Pb = S.P + (size_t)seq * ld * ld;
-  const int* psb = S.ps_i + (size_t)seq * kpart * kPsInts;
-  const int mark = marked ? marked[i] : -1;
-  sl2_overlay_item* list = items + (size_t)i * item_stride;
+// ---- the scene's draw list of sequence seq0 + i: one wavefront (sl2_drawlist_dev.hpp).  First the trajectory, then the features,
+// a lane per slot, 64 slots a round (up to three items each, placed in slot order).
+__global__ void __launch_bounds__(kListThreads) k_scene_list(const SeqArrays S, int seq0, int nseq, int N, int ld, int ppos, int kpart, int width,
+                                                             int height, int layers, const int32_t* __restrict__ marked,
+                                                             sl2_overlay_item* __restrict__ items, int item_stride, int32_t* __restrict__ counts) {
+  SeqWave w;
+  if (!seq_wave(S, seq0, nseq, N, ld, kpart, marked, &w)) return;
+  const CameraParams cam = load_cam(S.seq_cam, w.seq, width, height);
+  const double* xb = w.xb;
+  const double* Pb = S.P + (size_t)w.seq * ld * ld;
+  ListWriter list(items, w.i, item_stride, w.lane);
   double xp[7];
   for (int k = 0; k < 7; ++k) xp[k] = xb[k];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int total = 0;                                       // wave-uniform
-  if (layers & SL2_SCENE_TRAJECTORY) {
-    const int pushed = max(S.traj_count[seq], 0), have = min(pushed, kTrajCapacity), nseg = have - 1;
-    const double* tr = S.traj + (size_t)seq * kTrajCapacity * 3;
-    const uint8_t yellow[3] = {255, 255, 0};
-    for (int base = 0; base < nseg; base += 64) {
-      const int j = base + lane;
-      bool ok = false;
-      int c[4] = {0, 0, 0, 0};
-      if (j < nseg) {
-        const int first = pushed - have + j;          // the logical index of the older end: entry j of sl2_get_trajectory
-        double a[3], b[3];
-        zeroedyi_only(xp, tr + (size_t)(first % kTrajCapacity) * 3, a);
-        zeroedyi_only(xp, tr + (size_t)((first + 1) % kTrajCapacity) * 3, b);
-        ok = scene_segment(cam.fku, cam.fkv, cam.u0, cam.v0, a, b, c);
-      }
-      const unsigned long long m = __ballot(ok);
-      const int at = total + __popcll(m & below);
-      if (ok && at < item_stride) list[at] = scene_item(SL2_ITEM_SEGMENT, -1, c[0], c[1], c[2], c[3], yellow);
-      total += __popcll(m);
-    }
-  }
+  if (layers & SL2_SCENE_TRAJECTORY)
+    list_trajectory(list, S, w.seq, [&](const double* older, const double* newer, int* c) {
+      double a[3], b[3];
+      zeroedyi_only(xp, older, a);
+      zeroedyi_only(xp, newer, b);
+      return scene_segment(cam.fku, cam.fkv, cam.u0, cam.v0, a, b, c);
+    });
   if (layers & (SL2_SCENE_FEATURES | SL2_SCENE_UNCERTAINTIES))
-    for (int base = 0; base < ns; base += 64) {
-      const int f = base + lane;
-      const int fl = f < ns ? S.f_flags[o + f] : 0;
-      const bool part = (fl & FF_PARTIAL) != 0, full = !part && (fl & FF_ACTIVE) != 0;
-      const int label = (part || full) ? S.f_label[o + f] : -1;
+    for (int base = 0; base < w.ns; base += 64) {
+      const int f = base + w.lane;
+      const SlotClass s = classify_slot(S, w.o, f, w.ns);
       bool has_marker = false, has_ring = false, has_ray = false;
       int mx = 0, my = 0, rx = 0, ry = 0, ray[4] = {0, 0, 0, 0};
       double q[4] = {0.0, 0.0, 0.0, 0.0};
-      if (full) {
+      if (s.full) {
         const int pos = 13 + 3 * f;
         double m[3];
         if (layers & SL2_SCENE_UNCERTAINTIES) {
@@ -129,10 +93,8 @@ __global__ void __launch_bounds__(kSceneThreads) k_scene_list(const SeqArrays S,
           scene_project(cam.fku, cam.fkv, cam.u0, cam.v0, m, p);
           has_marker = overlay_round(p[0], &mx) && overlay_round(p[1], &my);
         }
-      } else if (part && (layers & SL2_SCENE_FEATURES)) {
-        int ks = -1;
-        for (int k = 0; k < kpart; ++k)
-          if (psb[k * kPsInts + kPsActive] && psb[k * kPsInts + kPsLabel] == f) ks = k;
+      } else if (s.part && (layers & SL2_SCENE_FEATURES)) {
+        const int ks = partial_slot_of(w.psb, kpart, f);
         if (ks >= 0) {
           // the partial model's zeroed state (part_feature_model.cpp:80-146): RRW (r_i - r) and RRW hhat_i
           const double* y6 = xb + ppos + 6 * ks;
@@ -144,28 +106,9 @@ __global__ void __launch_bounds__(kSceneThreads) k_scene_list(const SeqArrays S,
           has_ray = scene_segment(cam.fku, cam.fkv, cam.u0, cam.v0, a, b, ray);
         }
       }
-      const int c = (has_marker ? 2 : 0) + (has_ring ? 1 : 0) + (has_ray ? 1 : 0);
-      int incl = c;
-      for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-      int at = total + incl - c;
-      if (c > 0) {
-        uint8_t rgb[3];
-        overlay_colour(label == mark, full && (fl & FF_SELECTED) != 0, full && (fl & FF_SUCCESS) != 0, rgb);
-        if (has_marker) {
-          if (at < item_stride) list[at] = scene_item(SL2_ITEM_RECT, label, mx - 1, my - 1, mx + 1, my + 1, rgb);
-          if (at + 1 < item_stride) list[at + 1] = scene_item(SL2_ITEM_RECT, label, mx, my, mx, my, rgb);
-          at += 2;
-        }
-        if (has_ring && at < item_stride) {
-          sl2_overlay_item r = scene_item(SL2_ITEM_RING, label, rx, ry, 0, 0, rgb);
-          r.q[0] = q[0]; r.q[1] = q[1]; r.q[2] = q[2]; r.q[3] = q[3];
-          list[at] = r;
-        }
-        if (has_ray && at < item_stride) list[at] = scene_item(SL2_ITEM_SEGMENT, label, ray[0], ray[1], ray[2], ray[3], rgb);
-      }
-      total += __shfl(incl, 63);
+      list_feature(list, s, w.mark, has_marker, mx, my, has_ring, rx, ry, q, has_ray, ray);
     }
-  if (lane == 0) counts[i] = total < item_stride ? total : item_stride;
+  list.finish(counts, w.i);
 }
 
 // one launch of k_rectify: device frames in, device images out
@@ -185,28 +128,12 @@ static int launch_rectify(sl2_engine* e, int seq0, int nseq, const uint8_t* d_fr
   return SL2_OK;
 }
 
-static int launch_scene_list(sl2_engine* e, int seq0, int nseq, int layers, const int32_t* d_marked, sl2_overlay_item* d_items, int item_stride,
-                             int32_t* d_counts) {
+static int launch_scene_list(sl2_engine* e, int seq0, int nseq, int layers, const ListStage& d) {
   LaunchScope ls(e, "k_scene_list");
-  hipLaunchKernelGGL(k_scene_list, dim3((nseq + kSceneSeqs - 1) / kSceneSeqs), dim3(kSceneThreads), 0, e->stream, seq_arrays(e), seq0, nseq, e->N, e->ld,
-                     e->ppos, e->kpart, e->cam.width, e->cam.height, layers, d_marked, d_items, item_stride, d_counts);
+  hipLaunchKernelGGL(k_scene_list, dim3((nseq + kListSeqs - 1) / kListSeqs), dim3(kListThreads), 0, e->stream, seq_arrays(e), seq0, nseq, e->N, e->ld,
+                     e->ppos, e->kpart, e->cam.width, e->cam.height, layers, d.marked, d.items, d.stride, d.counts);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
-}
-
-// why a range of sequences cannot be served (nullptr: it can)
-static const char* scene_range_fault(const sl2_engine* e, int seq0, int nseq, int layers) {
-  if (!e) return "null engine";
-  if (nseq < 1) return "nseq below 1";
-  if (seq0 < 0 || seq0 > e->B - nseq) return "outside the batch";
-  if (layers & ~SL2_SCENE_ALL) return "layers with bits outside SL2_SCENE_ALL";
-  return nullptr;
-}
-
-static std::string rectify_range_text(int first, int count, const char* what) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), "sl2_rectify_frames: sequences %d .. %d: %s", first, first + (count > 0 ? count : 1) - 1, what);
-  return buf;
 }
 
 }  // namespace sl2
@@ -226,17 +153,14 @@ extern "C" int sl2_rectify_frame_host(const uint8_t* frame, int width, int heigh
 
 extern "C" int sl2_rectify_frames(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device, uint8_t* out,
                                   size_t out_stride, int out_on_device) {
-  const char* why = nullptr;
-  if (!e) why = "null engine";
-  else if (nseq < 1) why = "nseq below 1";
-  else if (seq0 < 0 || seq0 > e->B - nseq) why = "outside the batch";
-  else if (!frames || !out) why = "null frames or out";
-  else if (seq_stride < (size_t)e->cam.width * (size_t)e->cam.height) why = "seq_stride below width * height";
-  else if (out_stride < (size_t)e->cam.width * (size_t)e->cam.height) why = "out_stride below width * height";
+  const char* why = range_fault(e, seq0, nseq, 0, 0, nullptr);      // (no layers)
   const int W = e ? e->cam.width : 0, H = e ? e->cam.height : 0;
+  if (!why && (!frames || !out)) why = "null frames or out";
+  if (!why && seq_stride < (size_t)W * (size_t)H) why = "seq_stride below width * height";
+  if (!why && out_stride < (size_t)W * (size_t)H) why = "out_stride below width * height";      // (one byte a pixel: not geometry_fault's rule)
   const long long tiles_x = (W + kRectTileW - 1) / kRectTileW, tiles = tiles_x * ((H + kRectTileH - 1) / kRectTileH);
   if (!why && (W > kRectifyMaxSide || H > kRectifyMaxSide || tiles * nseq > 0x7fffffffll)) why = "more tiles than one launch takes";
-  if (why) { set_error(rectify_range_text(seq0, nseq, why)); return SL2_ERR_INVALID; }
+  if (why) { set_error(range_text("sl2_rectify_frames", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
   SL2_HIP(hipSetDevice(e->device));
   // image staging (shared with sl2_draw_overlays, which orders itself on the same stream): host frames on their way in
   // (packed), then host-bound images on their way out (packed)
@@ -267,65 +191,23 @@ extern "C" size_t sl2_scene_item_bound(int max_features, int partial_slots) {
 
 extern "C" int sl2_scene_items(sl2_engine* e, int seq0, int nseq, int layers, const int32_t* marked, sl2_overlay_item* items, int item_stride,
                                int32_t* counts, int on_device) {
-  const char* why = scene_range_fault(e, seq0, nseq, layers);
-  if (!why && (!items || !counts)) why = "null items or counts";
-  if (!why && on_device && (uintptr_t)items % 8) why = "device items not 8-byte aligned";
-  if (!why && (item_stride < 0 || (size_t)item_stride < sl2_scene_item_bound(e->N, e->kpart))) why = "item_stride below sl2_scene_item_bound";
-  if (why) { set_error(range_text("sl2_scene_items", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
-  SL2_HIP(hipSetDevice(e->device));
-  if (on_device) return launch_scene_list(e, seq0, nseq, layers, marked, items, item_stride, counts);
-  ListStage st;
-  { int _rc = list_stage(e, nseq, (size_t)item_stride, &st); if (_rc != SL2_OK) return _rc; }
-  if (marked) SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-  { int _rc = launch_scene_list(e, seq0, nseq, layers, marked ? st.marked : nullptr, st.items, item_stride, st.counts); if (_rc != SL2_OK) return _rc; }
-  // whole strides come back in one copy: the items behind a list's count are not part of it (whatever the staging held)
-  SL2_HIP(hipMemcpyAsync(counts, st.counts, sizeof(int32_t) * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipMemcpyAsync(items, st.items, sizeof(sl2_overlay_item) * (size_t)item_stride * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipStreamSynchronize(e->stream));
-  return SL2_OK;
+  const char* why = range_fault(e, seq0, nseq, layers, SL2_SCENE_ALL, "layers with bits outside SL2_SCENE_ALL");
+  return items_call("sl2_scene_items", e, seq0, nseq, why, sl2_scene_item_bound, "item_stride below sl2_scene_item_bound", nullptr, 0, marked, items,
+                    item_stride, counts, nullptr, on_device, [&](const ListStage& d) { return launch_scene_list(e, seq0, nseq, layers, d); });
 }
 
 extern "C" int sl2_draw_rectified(sl2_engine* e, int seq0, int nseq, const uint8_t* frames, size_t seq_stride, int frames_on_device, int layers,
                                   const int32_t* marked, uint8_t* out, size_t out_stride, int out_on_device) {
-  const char* why = scene_range_fault(e, seq0, nseq, layers);
+  const char* why = range_fault(e, seq0, nseq, layers, SL2_SCENE_ALL, "layers with bits outside SL2_SCENE_ALL");
   if (!why && (!frames || !out)) why = "null frames or out";
   if (!why) why = geometry_fault(nseq, e->cam.width, e->cam.height, seq_stride, out_stride);
   if (why) { set_error(range_text("sl2_draw_rectified", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
   const int W = e->cam.width, H = e->cam.height;
-  SL2_HIP(hipSetDevice(e->device));
-  const size_t stride = sl2_scene_item_bound(e->N, e->kpart), px = (size_t)W * H;
-  ListStage st;
-  { int _rc = list_stage(e, nseq, stride, &st); if (_rc != SL2_OK) return _rc; }
-  // image staging: host frames on their way in (packed), the rectified grey frames (packed: the rasteriser's frames), then
-  // host-bound images on their way out (packed)
-  const size_t in_bytes = frames_on_device ? 0 : ((px * (size_t)nseq + 255) & ~(size_t)255), grey_bytes = (px * (size_t)nseq + 255) & ~(size_t)255;
-  const size_t out_bytes = out_on_device ? 0 : 3 * px * (size_t)nseq;
-  { int _rc = grow_device(&e->ovl_images, &e->ovl_images_bytes, in_bytes + grey_bytes + out_bytes); if (_rc != SL2_OK) return _rc; }
-  const uint8_t* d_frames = frames;
-  size_t d_seq_stride = seq_stride;
-  if (!frames_on_device) {
-    SL2_HIP(hipMemcpy2DAsync(e->ovl_images, px, frames, seq_stride, px, (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-    d_frames = (const uint8_t*)e->ovl_images; d_seq_stride = px;
-    // (as in sl2_draw_overlays: the one wait of the device form with host frames, until they have been copied)
-    if (out_on_device) SL2_HIP(hipStreamSynchronize(e->stream));
-  }
-  const int32_t* d_marked = marked;
-  if (marked && !out_on_device) {
-    SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-    d_marked = st.marked;
-  }
-  uint8_t* d_grey = (uint8_t*)e->ovl_images + in_bytes;
-  { int _rc = launch_rectify(e, seq0, nseq, d_frames, d_seq_stride, d_grey, px); if (_rc != SL2_OK) return _rc; }
-  { int _rc = launch_scene_list(e, seq0, nseq, layers, d_marked, st.items, (int)stride, st.counts); if (_rc != SL2_OK) return _rc; }
-  uint8_t* d_out = out_on_device ? out : d_grey + grey_bytes;
-  const size_t d_out_stride = out_on_device ? out_stride : 3 * px;
-  {
-    LaunchScope ls(e, "k_overlay_draw");
-    int _rc = launch_draw(e->stream, d_grey, px, nseq, W, H, st.items, (int)stride, st.counts, nullptr, 0, 0, d_out, d_out_stride);
-    if (_rc != SL2_OK) return _rc;
-  }
-  if (out_on_device) return SL2_OK;
-  SL2_HIP(hipMemcpy2DAsync(out, out_stride, d_out, 3 * px, 3 * px, (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipStreamSynchronize(e->stream));
-  return SL2_OK;
+  // the rasteriser draws over the rectified frames
+  return draw_call(e, nseq, W, H, sl2_scene_item_bound(e->N, e->kpart), frames, seq_stride, frames_on_device, nullptr, 0, marked, nullptr, out, out_stride,
+                   out_on_device,
+                   [&](const uint8_t* d_frames, size_t d_seq_stride, uint8_t* d_grey) {
+                     return launch_rectify(e, seq0, nseq, d_frames, d_seq_stride, d_grey, (size_t)W * H);
+                   },
+                   [&](const ListStage& d) { return launch_scene_list(e, seq0, nseq, layers, d); });
 }

@@ -3,8 +3,8 @@
 // sequences.  k_world_list lists the map, the trajectory, the camera glyph and the axes as seen from a free camera, for the
 // rasteriser of sl2_overlay.hip; k_pick_items answers which labelled item of any draw list covers a click's window.  The
 // arithmetic is sl2_world_view_dev.hpp's, shared with sl2_pick_items_host.  No workgroup waits for another.
-#include "sl2_common.hpp"
-#include "sl2_overlay_dev.hpp"
+#include "sl2_display.hpp"
+#include "sl2_drawlist_dev.hpp"
 #include "sl2_rectify_dev.hpp"
 #include "sl2_world_view_dev.hpp"
 
@@ -12,17 +12,8 @@ namespace sl2 {
 
 static_assert(sizeof(sl2_view) == 88, "sl2_view is 88 bytes");
 
-constexpr int kWorldThreads = 256;
-constexpr int kWorldSeqs = kWorldThreads / 64;      // sequences per workgroup of k_world_list, a wavefront each
 constexpr int kPickThreads = 256;
 constexpr int kPickImages = kPickThreads / 64;      // images per workgroup of k_pick_items, a wavefront each
-
-__device__ __forceinline__ sl2_overlay_item world_item(int kind, int label, int a0, int a1, int a2, int a3, const uint8_t rgb[3]) {
-  sl2_overlay_item it = overlay_blank_item(kind, label);
-  it.a[0] = a0; it.a[1] = a1; it.a[2] = a2; it.a[3] = a3;
-  it.rgb[0] = rgb[0]; it.rgb[1] = rgb[1]; it.rgb[2] = rgb[2];
-  return it;
-}
 
 __device__ __forceinline__ double wave_min(double v) {
   for (int d = 32; d > 0; d >>= 1) { const double t = __shfl_xor(v, d); if (t < v) v = t; }
@@ -33,73 +24,45 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
-// ---- the world's draw list of sequence seq0 + i: one wavefront, after k_scene_list's pattern.  The glyph's 16 edges, the
-// trajectory's pairs (64 a round) and the three axes yield one item or none per lane: a ballot places them.  The features, a
-// lane per slot, 64 slots a round, yield up to three: a shuffle scan places them in slot order.  Every lane keeps the extents of
-// the slots it saw; a wave min / max after the last round makes them the map's, before the axes are listed.  Nothing is stored
-// at or beyond item_stride.
-__global__ void __launch_bounds__(kWorldThreads) k_world_list(const SeqArrays S, int seq0, int nseq, int N, int ld, int ppos, int kpart,
-                                                              const sl2_view* __restrict__ views, int nviews, int layers,
-                                                              const int32_t* __restrict__ marked, sl2_overlay_item* __restrict__ items,
-                                                              int item_stride, int32_t* __restrict__ counts, double* __restrict__ extents) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * kWorldSeqs + (threadIdx.x >> 6);
-  if (i >= nseq) return;                               // (a whole wavefront)
-  const int seq = seq0 + i;
-  const size_t o = (size_t)seq * N;
-  const int ns = min(max(S.n_slots[seq], 0), N);
-  const sl2_view view = views[nviews == 1 ? 0 : i];
-  const double* xb = S.x + (size_t)seq * ld;
-  const double* Pb = S.P + (size_t)seq * ld * ld;
-  const int* psb = S.ps_i + (size_t)seq * kpart * kPsInts;
-  const int mark = marked ? marked[i] : -1;
-  sl2_overlay_item* list = items + (size_t)i * item_stride;
+// ---- the world's draw list of sequence seq0 + i: one wavefront (sl2_drawlist_dev.hpp).  The glyph's 16 edges, the trajectory's
+// pairs and the three axes yield one item or none per lane; the features, a lane per slot, 64 slots a round, up to three, placed
+// in slot order.  Every lane keeps the extents of the slots it saw; a wave min / max after the last round makes them the map's,
+// before the axes are listed.
+__global__ void __launch_bounds__(kListThreads) k_world_list(const SeqArrays S, int seq0, int nseq, int N, int ld, int ppos, int kpart,
+                                                             const sl2_view* __restrict__ views, int nviews, int layers,
+                                                             const int32_t* __restrict__ marked, sl2_overlay_item* __restrict__ items,
+                                                             int item_stride, int32_t* __restrict__ counts, double* __restrict__ extents) {
+  SeqWave w;
+  if (!seq_wave(S, seq0, nseq, N, ld, kpart, marked, &w)) return;
+  const int lane = w.lane;
+  const sl2_view view = views[nviews == 1 ? 0 : w.i];
+  const double* xb = w.xb;
+  const double* Pb = S.P + (size_t)w.seq * ld * ld;
+  ListWriter list(items, w.i, item_stride, lane);
   double xp[7], xv[7];
   world_view_pose(view, xp);
   for (int k = 0; k < 7; ++k) xv[k] = xb[k];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int total = 0;                                       // wave-uniform
   if (layers & SL2_WORLD_CAMERA) {
     const uint8_t grey[3] = {150, 150, 150};
     int c[4] = {0, 0, 0, 0};
     const bool ok = lane < kWorldGlyphEdges && world_glyph_segment(view, xp, xv, lane, c);
-    const unsigned long long m = __ballot(ok);
-    const int at = total + __popcll(m & below);
-    if (ok && at < item_stride) list[at] = world_item(SL2_ITEM_SEGMENT, -1, c[0], c[1], c[2], c[3], grey);
-    total += __popcll(m);
+    const int at = list.one(ok);
+    if (ok) list.put(at, draw_item(SL2_ITEM_SEGMENT, -1, c[0], c[1], c[2], c[3], grey));
   }
-  if (layers & SL2_WORLD_TRAJECTORY) {
-    const int pushed = max(S.traj_count[seq], 0), have = min(pushed, kTrajCapacity), nseg = have - 1;
-    const double* tr = S.traj + (size_t)seq * kTrajCapacity * 3;
-    const uint8_t yellow[3] = {255, 255, 0};
-    for (int base = 0; base < nseg; base += 64) {
-      const int j = base + lane;
-      bool ok = false;
-      int c[4] = {0, 0, 0, 0};
-      if (j < nseg) {
-        const int first = pushed - have + j;          // the logical index of the older end: entry j of sl2_get_trajectory
-        ok = world_segment(view, xp, tr + (size_t)(first % kTrajCapacity) * 3, tr + (size_t)((first + 1) % kTrajCapacity) * 3, c);
-      }
-      const unsigned long long m = __ballot(ok);
-      const int at = total + __popcll(m & below);
-      if (ok && at < item_stride) list[at] = world_item(SL2_ITEM_SEGMENT, -1, c[0], c[1], c[2], c[3], yellow);
-      total += __popcll(m);
-    }
-  }
+  if (layers & SL2_WORLD_TRAJECTORY)
+    list_trajectory(list, S, w.seq, [&](const double* older, const double* newer, int* c) { return world_segment(view, xp, older, newer, c); });
   // the extents: r of xv_ (every lane, the same), then the lane's own slots
   // (six named scalars, not an array: the axes pick theirs by lane, and an index known only at run time would put it in scratch)
   double xmin = 0.0, xmax = 0.0, ymin = 0.0, ymax = 0.0, zmin = 0.0, zmax = 0.0;
   world_extend(&xmin, &xmax, xv[0]); world_extend(&ymin, &ymax, xv[1]); world_extend(&zmin, &zmax, xv[2]);
   const bool list_features = (layers & (SL2_WORLD_FEATURES | SL2_WORLD_UNCERTAINTIES)) != 0;
-  for (int base = 0; base < ns; base += 64) {
+  for (int base = 0; base < w.ns; base += 64) {
     const int f = base + lane;
-    const int fl = f < ns ? S.f_flags[o + f] : 0;
-    const bool part = (fl & FF_PARTIAL) != 0, full = !part && (fl & FF_ACTIVE) != 0;
-    const int label = (part || full) ? S.f_label[o + f] : -1;
+    const SlotClass s = classify_slot(S, w.o, f, w.ns);
     bool has_marker = false, has_ring = false, has_ray = false;
     int mk[2] = {0, 0}, rc[2] = {0, 0}, ray[4] = {0, 0, 0, 0};
     double q[4] = {0.0, 0.0, 0.0, 0.0};
-    if (full) {
+    if (s.full) {
       const int pos = 13 + 3 * f;
       if (layers & SL2_WORLD_FEATURES) { world_extend(&xmin, &xmax, xb[pos]); world_extend(&ymin, &ymax, xb[pos + 1]); world_extend(&zmin, &zmax, xb[pos + 2]); }
       if (list_features) {
@@ -110,33 +73,12 @@ __global__ void __launch_bounds__(kWorldThreads) k_world_list(const SeqArrays S,
             for (int c = 0; c < 3; ++c) Pyy[r * 3 + c] = Pb[(size_t)(pos + r) * ld + pos + c];
         world_feature(view, xp, xb + pos, Pyy, (layers & SL2_WORLD_FEATURES) != 0, want_ring, &has_marker, mk, &has_ring, rc, q);
       }
-    } else if (part && (layers & SL2_WORLD_FEATURES)) {
-      int ks = -1;
-      for (int k = 0; k < kpart; ++k)
-        if (psb[k * kPsInts + kPsActive] && psb[k * kPsInts + kPsLabel] == f) ks = k;
+    } else if (s.part && (layers & SL2_WORLD_FEATURES)) {
+      const int ks = partial_slot_of(w.psb, kpart, f);
       if (ks >= 0) has_ray = world_ray(view, xp, xb + ppos + 6 * ks, ray);
     }
     if (!list_features) continue;                      // (wave-uniform: the round only fed the extents)
-    const int c = (has_marker ? 2 : 0) + (has_ring ? 1 : 0) + (has_ray ? 1 : 0);
-    int incl = c;
-    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-    int at = total + incl - c;
-    if (c > 0) {
-      uint8_t rgb[3];
-      overlay_colour(label == mark, full && (fl & FF_SELECTED) != 0, full && (fl & FF_SUCCESS) != 0, rgb);
-      if (has_marker) {
-        if (at < item_stride) list[at] = world_item(SL2_ITEM_RECT, label, mk[0] - 1, mk[1] - 1, mk[0] + 1, mk[1] + 1, rgb);
-        if (at + 1 < item_stride) list[at + 1] = world_item(SL2_ITEM_RECT, label, mk[0], mk[1], mk[0], mk[1], rgb);
-        at += 2;
-      }
-      if (has_ring && at < item_stride) {
-        sl2_overlay_item r = world_item(SL2_ITEM_RING, label, rc[0], rc[1], 0, 0, rgb);
-        r.q[0] = q[0]; r.q[1] = q[1]; r.q[2] = q[2]; r.q[3] = q[3];
-        list[at] = r;
-      }
-      if (has_ray && at < item_stride) list[at] = world_item(SL2_ITEM_SEGMENT, label, ray[0], ray[1], ray[2], ray[3], rgb);
-    }
-    total += __shfl(incl, 63);
+    list_feature(list, s, w.mark, has_marker, mk[0], mk[1], has_ring, rc[0], rc[1], q, has_ray, ray);
   }
   xmin = wave_min(xmin); xmax = wave_max(xmax);
   ymin = wave_min(ymin); ymax = wave_max(ymax);
@@ -146,15 +88,12 @@ __global__ void __launch_bounds__(kWorldThreads) k_world_list(const SeqArrays S,
     int c[4] = {0, 0, 0, 0};
     const double lo = lane == 0 ? xmin : (lane == 1 ? ymin : zmin), hi = lane == 0 ? xmax : (lane == 1 ? ymax : zmax);
     const bool ok = lane < kWorldAxes && world_axis_segment(view, xp, lo, hi, lane, c);
-    const unsigned long long m = __ballot(ok);
-    const int at = total + __popcll(m & below);
-    if (ok && at < item_stride) list[at] = world_item(SL2_ITEM_SEGMENT, -1, c[0], c[1], c[2], c[3], white);
-    total += __popcll(m);
+    const int at = list.one(ok);
+    if (ok) list.put(at, draw_item(SL2_ITEM_SEGMENT, -1, c[0], c[1], c[2], c[3], white));
   }
-  if (lane != 0) return;
-  counts[i] = total < item_stride ? total : item_stride;
-  if (extents) {
-    double* ex = extents + (size_t)i * 6;
+  list.finish(counts, w.i);
+  if (lane == 0 && extents) {
+    double* ex = extents + (size_t)w.i * 6;
     ex[0] = xmin; ex[1] = xmax; ex[2] = ymin; ex[3] = ymax; ex[4] = zmin; ex[5] = zmax;
   }
 }
@@ -183,59 +122,19 @@ __global__ void __launch_bounds__(kPickThreads) k_pick_items(int nimages, int wi
   picked[2 * i + 1] = best;
 }
 
-static int launch_world_list(sl2_engine* e, int seq0, int nseq, const sl2_view* d_views, int nviews, int layers, const int32_t* d_marked,
-                             sl2_overlay_item* d_items, int item_stride, int32_t* d_counts, double* d_extents) {
+static int launch_world_list(sl2_engine* e, int seq0, int nseq, int nviews, int layers, const ListStage& d) {
   // (the root's arrays on the engine's stream, like sl2_scene_items: the groups' streams join it at the end of every stepping call)
   LaunchScope ls(e, "k_world_list");
-  hipLaunchKernelGGL(k_world_list, dim3((nseq + kWorldSeqs - 1) / kWorldSeqs), dim3(kWorldThreads), 0, e->stream, seq_arrays(e), seq0, nseq, e->N, e->ld,
-                     e->ppos, e->kpart, d_views, nviews, layers, d_marked, d_items, item_stride, d_counts, d_extents);
+  hipLaunchKernelGGL(k_world_list, dim3((nseq + kListSeqs - 1) / kListSeqs), dim3(kListThreads), 0, e->stream, seq_arrays(e), seq0, nseq, e->N, e->ld,
+                     e->ppos, e->kpart, d.views, nviews, layers, d.marked, d.items, d.stride, d.counts, d.extents);
   SL2_HIP(hipGetLastError());
   return SL2_OK;
 }
 
-// engine-owned staging of the host forms (the lists' own block, grown on demand): items [nseq][stride], counts [nseq], marked
-// [nseq], views [nviews], extents [nseq][6]
-struct WorldStage { sl2_overlay_item* items; int32_t* counts; int32_t* marked; sl2_view* views; double* extents; };
-static int world_stage(sl2_engine* e, int nseq, int nviews, size_t stride, WorldStage* st) {
-  const size_t item_bytes = sizeof(sl2_overlay_item) * stride * (size_t)nseq, int_bytes = 2 * sizeof(int32_t) * (size_t)nseq;
-  const size_t view_bytes = sizeof(sl2_view) * (size_t)nviews, ext_bytes = 6 * sizeof(double) * (size_t)nseq;
-  { int _rc = grow_device(&e->ovl_lists, &e->ovl_lists_bytes, item_bytes + int_bytes + view_bytes + ext_bytes); if (_rc != SL2_OK) return _rc; }
-  char* p = (char*)e->ovl_lists;
-  st->items = (sl2_overlay_item*)p;
-  st->counts = (int32_t*)(p + item_bytes);
-  st->marked = st->counts + nseq;
-  st->views = (sl2_view*)(p + item_bytes + int_bytes);      // (8-byte aligned: 64 stride nseq + 8 nseq)
-  st->extents = (double*)(p + item_bytes + int_bytes + view_bytes);
-  return SL2_OK;
-}
-
-// why a range of sequences cannot be served (nullptr: it can)
+// why a range of sequences cannot be seen through these views (nullptr: it can)
 static const char* world_range_fault(const sl2_engine* e, int seq0, int nseq, const sl2_view* views, int nviews, int layers) {
-  if (!e) return "null engine";
-  if (nseq < 1) return "nseq below 1";
-  if (seq0 < 0 || seq0 > e->B - nseq) return "outside the batch";
-  if (!views) return "null views";
-  if (nviews != 1 && nviews != nseq) return "nviews is neither 1 nor nseq";
-  if (layers & ~SL2_WORLD_ALL) return "layers with bits outside SL2_WORLD_ALL";
-  return nullptr;
-}
-
-// the first host-resident view with a number that is not finite (-1: none)
-static int bad_view(const sl2_view* views, int nviews) {
-  for (int i = 0; i < nviews; ++i) {
-    const sl2_view& v = views[i];
-    const double all[11] = {v.r[0], v.r[1], v.r[2], v.q[0], v.q[1], v.q[2], v.q[3], v.fku, v.fkv, v.u0, v.v0};
-    for (double d : all)
-      if (!overlay_finite(d)) return i;
-  }
-  return -1;
-}
-
-static std::string view_text(const char* fn, int seq0, int nseq, int nviews, int bad) {
-  char buf[256];
-  if (nviews == 1) snprintf(buf, sizeof(buf), "%s: sequences %d .. %d: the view holds a number that is not finite", fn, seq0, seq0 + nseq - 1);
-  else snprintf(buf, sizeof(buf), "%s: sequence %d: its view holds a number that is not finite", fn, seq0 + bad);
-  return buf;
+  const char* views_fault = !views ? "null views" : (nviews != 1 && nviews != nseq) ? "nviews is neither 1 nor nseq" : nullptr;
+  return range_fault(e, seq0, nseq, layers, SL2_WORLD_ALL, "layers with bits outside SL2_WORLD_ALL", views_fault);
 }
 
 }  // namespace sl2
@@ -294,28 +193,8 @@ extern "C" size_t sl2_world_item_bound(int max_features, int partial_slots) {
 extern "C" int sl2_world_items(sl2_engine* e, int seq0, int nseq, const sl2_view* views, int nviews, int layers, const int32_t* marked,
                                sl2_overlay_item* items, int item_stride, int32_t* counts, double* extents, int on_device) {
   const char* why = world_range_fault(e, seq0, nseq, views, nviews, layers);
-  if (!why && (!items || !counts)) why = "null items or counts";
-  if (!why && on_device && ((uintptr_t)items % 8 || (uintptr_t)views % 8 || (uintptr_t)extents % 8)) why = "device items, views or extents not 8-byte aligned";
-  if (!why && (item_stride < 0 || (size_t)item_stride < sl2_world_item_bound(e->N, e->kpart))) why = "item_stride below sl2_world_item_bound";
-  if (why) { set_error(range_text("sl2_world_items", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
-  if (!on_device) {
-    const int bad = bad_view(views, nviews);
-    if (bad >= 0) { set_error(view_text("sl2_world_items", seq0, nseq, nviews, bad)); return SL2_ERR_INVALID; }
-  }
-  SL2_HIP(hipSetDevice(e->device));
-  if (on_device) return launch_world_list(e, seq0, nseq, views, nviews, layers, marked, items, item_stride, counts, extents);
-  WorldStage st;
-  { int _rc = world_stage(e, nseq, nviews, (size_t)item_stride, &st); if (_rc != SL2_OK) return _rc; }
-  SL2_HIP(hipMemcpyAsync(st.views, views, sizeof(sl2_view) * (size_t)nviews, hipMemcpyHostToDevice, e->stream));
-  if (marked) SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-  { int _rc = launch_world_list(e, seq0, nseq, st.views, nviews, layers, marked ? st.marked : nullptr, st.items, item_stride, st.counts, st.extents);
-    if (_rc != SL2_OK) return _rc; }
-  // whole strides come back in one copy: the items behind a list's count are not part of it (whatever the staging held)
-  SL2_HIP(hipMemcpyAsync(counts, st.counts, sizeof(int32_t) * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipMemcpyAsync(items, st.items, sizeof(sl2_overlay_item) * (size_t)item_stride * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  if (extents) SL2_HIP(hipMemcpyAsync(extents, st.extents, 6 * sizeof(double) * (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipStreamSynchronize(e->stream));
-  return SL2_OK;
+  return items_call("sl2_world_items", e, seq0, nseq, why, sl2_world_item_bound, "item_stride below sl2_world_item_bound", views, nviews, marked, items,
+                    item_stride, counts, extents, on_device, [&](const ListStage& d) { return launch_world_list(e, seq0, nseq, nviews, layers, d); });
 }
 
 extern "C" int sl2_draw_world(sl2_engine* e, int seq0, int nseq, const sl2_view* views, int nviews, int width, int height, int background,
@@ -327,40 +206,16 @@ extern "C" int sl2_draw_world(sl2_engine* e, int seq0, int nseq, const sl2_view*
   if (!why) why = geometry_fault(nseq, width, height, (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0), out_stride);
   if (why) { set_error(range_text("sl2_draw_world", "sequences", seq0, nseq, why)); return SL2_ERR_INVALID; }
   if (!out_on_device) {
-    const int bad = bad_view(views, nviews);
-    if (bad >= 0) { set_error(view_text("sl2_draw_world", seq0, nseq, nviews, bad)); return SL2_ERR_INVALID; }
+    const std::string bad = view_fault_text("sl2_draw_world", seq0, nseq, views, nviews);
+    if (!bad.empty()) { set_error(bad); return SL2_ERR_INVALID; }
   }
-  SL2_HIP(hipSetDevice(e->device));
-  const size_t stride = sl2_world_item_bound(e->N, e->kpart), px = (size_t)width * height;
-  WorldStage st;
-  { int _rc = world_stage(e, nseq, nviews, stride, &st); if (_rc != SL2_OK) return _rc; }
-  // image staging: the constant grey frames (packed: the rasteriser's frames), then host-bound images on their way out (packed)
-  const size_t grey_bytes = (px * (size_t)nseq + 255) & ~(size_t)255, out_bytes = out_on_device ? 0 : 3 * px * (size_t)nseq;
-  { int _rc = grow_device(&e->ovl_images, &e->ovl_images_bytes, grey_bytes + out_bytes); if (_rc != SL2_OK) return _rc; }
-  uint8_t* d_grey = (uint8_t*)e->ovl_images;
-  SL2_HIP(hipMemsetAsync(d_grey, background, px * (size_t)nseq, e->stream));
-  const sl2_view* d_views = views;
-  const int32_t* d_marked = marked;
-  if (!out_on_device) {
-    SL2_HIP(hipMemcpyAsync(st.views, views, sizeof(sl2_view) * (size_t)nviews, hipMemcpyHostToDevice, e->stream));
-    d_views = st.views;
-    if (marked) {
-      SL2_HIP(hipMemcpyAsync(st.marked, marked, sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice, e->stream));
-      d_marked = st.marked;
-    }
-  }
-  { int _rc = launch_world_list(e, seq0, nseq, d_views, nviews, layers, d_marked, st.items, (int)stride, st.counts, nullptr); if (_rc != SL2_OK) return _rc; }
-  uint8_t* d_out = out_on_device ? out : d_grey + grey_bytes;
-  const size_t d_out_stride = out_on_device ? out_stride : 3 * px;
-  {
-    LaunchScope ls(e, "k_overlay_draw");
-    int _rc = launch_draw(e->stream, d_grey, px, nseq, width, height, st.items, (int)stride, st.counts, nullptr, 0, 0, d_out, d_out_stride);
-    if (_rc != SL2_OK) return _rc;
-  }
-  if (out_on_device) return SL2_OK;
-  SL2_HIP(hipMemcpy2DAsync(out, out_stride, d_out, 3 * px, 3 * px, (size_t)nseq, hipMemcpyDeviceToHost, e->stream));
-  SL2_HIP(hipStreamSynchronize(e->stream));
-  return SL2_OK;
+  // the rasteriser draws over constant grey frames
+  return draw_call(e, nseq, width, height, sl2_world_item_bound(e->N, e->kpart), nullptr, 0, 0, views, nviews, marked, nullptr, out, out_stride, out_on_device,
+                   [&](const uint8_t*, size_t, uint8_t* d_grey) {
+                     SL2_HIP(hipMemsetAsync(d_grey, background, (size_t)width * height * (size_t)nseq, e->stream));
+                     return SL2_OK;
+                   },
+                   [&](const ListStage& d) { return launch_world_list(e, seq0, nseq, nviews, layers, d); });
 }
 
 extern "C" int sl2_pick_items_host(int width, int height, const sl2_overlay_item* items, int count, int npatches, int x, int y, int32_t picked[2]) {
@@ -406,17 +261,12 @@ extern "C" int sl2_pick_items_batch(int device, void* stream, int nimages, int w
     SL2_HIP(hipGetLastError());
     return SL2_OK;
   }
-  // one device temporary of whatever arrived in host memory, released on every exit path (after the stream has drained)
-  struct Temp {
-    void* p = nullptr;
-    hipStream_t st;
-    ~Temp() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
-  } tmp;
-  tmp.st = st;
+  DeviceTemps tmp(st);
+  void* d = nullptr;
   const size_t ib = sizeof(sl2_overlay_item) * (size_t)item_stride * (size_t)nimages, nb = sizeof(int32_t) * (size_t)nimages;
-  if (hipMalloc(&tmp.p, ib + 5 * nb) != hipSuccess) { tmp.p = nullptr; set_error("sl2_pick_items_batch: device allocation failed"); return SL2_ERR_HIP; }
-  sl2_overlay_item* d_items = (sl2_overlay_item*)tmp.p;
-  int32_t* d_counts = (int32_t*)((char*)tmp.p + ib);
+  if (tmp.alloc(&d, ib + 5 * nb)) { set_error("sl2_pick_items_batch: device allocation failed"); return SL2_ERR_HIP; }
+  sl2_overlay_item* d_items = (sl2_overlay_item*)d;
+  int32_t* d_counts = (int32_t*)((char*)d + ib);
   int32_t *d_clicks = d_counts + nimages, *d_picked = d_clicks + 2 * (size_t)nimages;
   if (ib) SL2_HIP(hipMemcpyAsync(d_items, items, ib, hipMemcpyHostToDevice, st));
   SL2_HIP(hipMemcpyAsync(d_counts, counts, nb, hipMemcpyHostToDevice, st));

@@ -154,7 +154,10 @@ def test_bindings_and_adapters_know_the_feature():
     hpp = open(os.path.join(ROOT, "include", "scenelib2_amd_monoslam.hpp")).read()
     assert "void SetFrameSource(" in hpp and "bool GoOneStepRaw(" in hpp and "sl2_convert_frames" in hpp
     mk = open(os.path.join(ROOT, "scenelib2_amd", "csrc", "Makefile")).read()
-    assert mk.count("sl2_convert.hip") == 1 and "sl2_convert_dev.hpp" in mk and "sl2_convert.o" in mk
+    assert mk.count("sl2_convert.hip") == 1 and "sl2_convert_dev.hpp" in mk
+    # the trace library links every product object it does not rebuild, this one among them: its list derives from $(OBJS)
+    assert "\ntrace: $(filter-out $(TRACE_SRCS:.hip=.o),$(OBJS))\n" in mk and "$(TRACE_OBJS) $^ -lz" in mk
+    assert "sl2_convert.hip" in mk.split("\nSRCS = ")[1].split("\n")[0] and "sl2_convert.hip" not in mk.split("\nTRACE_SRCS = ")[1].split("\n")[0]
 
 
 def test_host_body_stays_inside_exactly_sized_blocks_under_asan(tmp_path):

@@ -12,15 +12,16 @@ put through the host form."""
 import numpy as np
 import pytest
 
+import display_helpers as dh
 import oracle_api as oa
 import overlay_cases as oc
+from display_helpers import SENTINEL, assert_images, assert_lists_equal
 from mapping_helpers import make_mapping_sequence
 from scenelib2_amd import Engine, _lib, overlay
 from slam_helpers import Pair
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 SR, DESC, INIT = overlay.SL2_OVERLAY_SEARCH_REGIONS, overlay.SL2_OVERLAY_DESCRIPTORS, overlay.SL2_OVERLAY_INITIALISATION
 
 
@@ -49,62 +50,9 @@ def batches():
     return groups
 
 
-def _pack_lists(lists, stride):
-    items = np.zeros((len(lists), stride), oc.ITEM)
-    counts = np.zeros(len(lists), np.int32)
-    for i, a in enumerate(lists):
-        items[i, :a.size] = a
-        counts[i] = a.size
-    return items, counts
-
-
-def _draw(g, w, h, frames_dev, items_dev, out_dev, seq_pad=0, item_pad=0, out_pad=0):
-    """One sl2_draw_items_batch call over a whole group; returns the images [n][h][w][3] after checking the guard bytes."""
-    L = _lib.load()
-    if not items_dev:          # a host-resident list with a bad item is refused (tests/test_overlay_host.py): those cases go by device lists
-        keep = [i for i, name in enumerate(g["names"]) if not name.startswith("bad_")]
-        g = dict(names=[g["names"][i] for i in keep], lists=[g["lists"][i] for i in keep], frames=g["frames"][keep], want=g["want"][keep],
-                 patches=g["patches"])
-    n = len(g["lists"])
-    seq_stride, out_stride = w * h + seq_pad, 3 * w * h + out_pad
-    stride = max(a.size for a in g["lists"]) + item_pad
-    items, counts = _pack_lists(g["lists"], stride)
-    if item_pad:          # what lies behind a list's count is not part of it
-        for i in range(n):
-            items[i, counts[i]:] = oc.circle(w // 2, h // 2, 4, oc.GREEN)
-    frames = np.full((n, seq_stride), 77, np.uint8)
-    frames[:, :w * h] = g["frames"].reshape(n, -1)
-    out = np.full((n, out_stride), SENTINEL, np.uint8)
-    P = g["patches"]
-    bufs = []
-    def dev(a):
-        b = _lib.DeviceBuffer(a.nbytes)
-        b.upload(a)
-        bufs.append(b)
-        return b
-    fp = dev(frames).ptr if frames_dev else frames.ctypes.data
-    if items_dev:
-        ip, cp, pp = dev(items).ptr, dev(counts).ptr, dev(P).ptr
-    else:
-        ip, cp, pp = items.ctypes.data, counts.ctypes.data, P.ctypes.data
-    dout = dev(out) if out_dev else None
-    op = dout.ptr if out_dev else out.ctypes.data
-    vp = _lib.vp
-    _lib.check(L.sl2_draw_items_batch(0, None, vp(fp), int(frames_dev), n, w, h, seq_stride, vp(ip), stride, vp(cp), int(items_dev), vp(pp),
-                                      P.shape[1], P.shape[0], vp(op), out_stride, int(out_dev)), L)
-    if out_dev:
-        out = dout.download(out.shape, np.uint8)          # (a blocking copy on the null stream: behind the launch)
-    for b in bufs:
-        b.free()
-    assert (out[:, 3 * w * h:] == SENTINEL).all(), "bytes between the images were written"
-    return g, out[:, :3 * w * h].reshape(n, h, w, 3)
-
-
-def _assert_images(g_got):
-    g, got = g_got
-    assert len(got) == len(g["names"]) > 20
-    for i, name in enumerate(g["names"]):
-        assert np.array_equal(got[i], g["want"][i]), (name, np.argwhere((got[i] != g["want"][i]).any(axis=2))[:5].tolist())
+def _draw(g, w, h, *residency, **pads):
+    """(A host-resident list with a bad item is refused, tests/test_overlay_host.py: the bad_ cases go by device lists.)"""
+    return dh.draw_items_batch(g, w, h, *residency, filler=oc.circle(w // 2, h // 2, 4, oc.GREEN), refused_prefix="bad_", **pads)
 
 
 @pytest.mark.parametrize("size", oc.SIZES)
@@ -113,7 +61,7 @@ def test_raster_cases_equal_the_host_form(batches, size, residency):
     w, h = size
     g = batches[size]
     fd, idv, od = dict(host=(0, 0, 0), device=(1, 1, 1), frames_on_device=(1, 0, 0), lists_and_out_on_device=(0, 1, 1))[residency]
-    _assert_images(_draw(g, w, h, fd, idv, od))
+    assert_images(_draw(g, w, h, fd, idv, od))
 
 
 @pytest.mark.parametrize("size", oc.SIZES)
@@ -124,7 +72,7 @@ def test_strides_above_the_minimum(batches, size, pads):
     w, h = size
     g = batches[size]
     for res in ((1, 1, 1), (0, 0, 0)):
-        _assert_images(_draw(g, w, h, *res, seq_pad=pads[0], item_pad=pads[1], out_pad=pads[2]))
+        assert_images(_draw(g, w, h, *res, seq_pad=pads[0], item_pad=pads[1], out_pad=pads[2]))
 
 
 def test_patch_without_an_array_and_single_image():
@@ -259,13 +207,6 @@ def assert_clear_of_half_integers(rounded):
     assert (np.abs(v - np.floor(v) - 0.5) > 1e-6).all(), "a rounded coordinate lies within 1e-6 of a half-integer: choose another seed"
 
 
-def assert_lists_equal(got, want, what):
-    assert got.size == want.size, (what, got.size, want.size, got["kind"].tolist(), want["kind"].tolist())
-    for name in ("kind", "label", "a", "patch", "rgb", "pad"):
-        assert np.array_equal(got[name], want[name]), (what, name, got[name].tolist(), want[name].tolist())
-    assert got["q"].tobytes() == want["q"].tobytes(), (what, "q", got["q"].tolist(), want["q"].tolist())
-
-
 def check_engine(e, frames, seq0, nseq, layers, marked=None, rounded_out=None):
     """sl2_overlay_items against the builder, sl2_draw_overlays against the builder's lists put through the host form."""
     lists = e.overlay_items(seq0, nseq, layers, marked)
@@ -375,6 +316,27 @@ def test_marked_labels_null_and_a_range_that_starts_late(scene):
     shifted["patch"][shifted["kind"] == oc.PATCH] -= e.max_features
     assert_lists_equal(late[0], shifted, "seq0 = 1")
     assert 0 <= late[0]["patch"].max() < e.max_features
+
+
+@pytest.fixture(scope="module")
+def large_map():
+    for e, state, cam in dh.large_map():
+        yield dict(e=e, cam=cam)
+
+
+def test_large_map_two_rounds_of_slots_the_patches_count_on(large_map):
+    """70 fully initialised features in front of the camera, one sequence: the second round of 64 slots has 6 live lanes, and its
+    patches are numbered on from the 64 live features of the first.  The drawing equals the host form on the device's own list."""
+    e, cam = large_map["e"], large_map["cam"]
+    frames = oc.frame_of(cam["width"], cam["height"], seed=5)[None]
+    marked = np.array([66], np.int32)
+    built, imgs = check_engine(e, frames, 0, 1, overlay.SL2_OVERLAY_ALL, marked)
+    b = built[0]
+    assert b["kind"].tolist() == [oc.PATCH] * 70          # (never stepped: nothing is selected, no search region)
+    assert b["patch"].tolist() == list(range(70)) and b["label"].tolist() == list(range(70))          # slot order across the two rounds
+    assert tuple(b[66]["rgb"]) == oc.GREEN and tuple(b[65]["rgb"]) == oc.YELLOW
+    own = e.overlay_items(0, 1, overlay.SL2_OVERLAY_ALL, marked)[0]
+    assert np.array_equal(imgs[0], overlay.draw_items_host(frames[0], own, patch_array(e, 0, 1)))
 
 
 def test_device_forms_equal_the_host_forms(scene):

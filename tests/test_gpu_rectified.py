@@ -16,16 +16,14 @@ sl2_rectify_frame_host followed by sl2_draw_items_host on the device's own list.
 import numpy as np
 import pytest
 
+import display_helpers as dh
 import overlay_cases as oc
 import rectified_cases as rc
-import rectified_scenes as rs
-from mapping_helpers import make_mapping_sequence
+from display_helpers import SENTINEL, assert_images, assert_lists_equal, engine_state
 from scenelib2_amd import Engine, _lib, overlay, rectified, synth
 from slam_helpers import Pair
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
 
 
 # ------------------------------------------------------------------------------------------------- the line primitive
@@ -45,52 +43,9 @@ def seg_batches():
     return out
 
 
-def _draw(g, w, h, frames_dev, items_dev, out_dev, seq_pad=0, item_pad=0, out_pad=0):
-    """One sl2_draw_items_batch call over a whole size; returns the images [n][h][w][3] after checking the guard bytes."""
-    L = _lib.load()
-    if not items_dev:          # a host-resident list with an item of unknown kind is refused (tests/test_rectified_host.py): that case goes by device lists
-        keep = [i for i, name in enumerate(g["names"]) if not name.startswith("seg_other_kinds")]
-        g = dict(names=[g["names"][i] for i in keep], lists=[g["lists"][i] for i in keep], frames=g["frames"][keep], want=g["want"][keep],
-                 patches=g["patches"])
-    n = len(g["lists"])
-    seq_stride, out_stride = w * h + seq_pad, 3 * w * h + out_pad
-    stride = max(a.size for a in g["lists"]) + item_pad
-    items = np.zeros((n, stride), oc.ITEM)
-    counts = np.zeros(n, np.int32)
-    for i, a in enumerate(g["lists"]):
-        items[i, :a.size] = a
-        items[i, a.size:] = rc.segment(0, 0, w - 1, h - 1, oc.GREEN)          # what lies behind a list's count is not part of it
-        counts[i] = a.size
-    frames = np.full((n, seq_stride), 77, np.uint8)
-    frames[:, :w * h] = g["frames"].reshape(n, -1)
-    out = np.full((n, out_stride), SENTINEL, np.uint8)
-    P = g["patches"]
-    bufs = []
-    def dev(a):
-        b = _lib.DeviceBuffer(a.nbytes)
-        b.upload(a)
-        bufs.append(b)
-        return b
-    fp = dev(frames).ptr if frames_dev else frames.ctypes.data
-    ip, cp, pp = (dev(items).ptr, dev(counts).ptr, dev(P).ptr) if items_dev else (items.ctypes.data, counts.ctypes.data, P.ctypes.data)
-    dout = dev(out) if out_dev else None
-    op = dout.ptr if out_dev else out.ctypes.data
-    vp = _lib.vp
-    _lib.check(L.sl2_draw_items_batch(0, None, vp(fp), int(frames_dev), n, w, h, seq_stride, vp(ip), stride, vp(cp), int(items_dev), vp(pp),
-                                      P.shape[1], P.shape[0], vp(op), out_stride, int(out_dev)), L)
-    if out_dev:
-        out = dout.download(out.shape, np.uint8)          # (a blocking copy on the null stream: behind the launch)
-    for b in bufs:
-        b.free()
-    assert (out[:, 3 * w * h:] == SENTINEL).all(), "bytes between the images were written"
-    return g, out[:, :3 * w * h].reshape(n, h, w, 3)
-
-
-def _assert_images(g_got):
-    g, got = g_got
-    assert len(got) == len(g["names"]) > 20
-    for i, name in enumerate(g["names"]):
-        assert np.array_equal(got[i], g["want"][i]), (name, np.argwhere((got[i] != g["want"][i]).any(axis=2))[:5].tolist())
+def _draw(g, w, h, *residency, **pads):
+    """(A host-resident list with an item of unknown kind is refused, tests/test_rectified_host.py: that case goes by device lists.)"""
+    return dh.draw_items_batch(g, w, h, *residency, filler=rc.segment(0, 0, w - 1, h - 1, oc.GREEN), refused_prefix="seg_other_kinds", **pads)
 
 
 @pytest.mark.parametrize("size", rc.SIZES)
@@ -98,7 +53,7 @@ def _assert_images(g_got):
 def test_segment_cases_equal_the_host_form(seg_batches, size, residency):
     w, h = size
     fd, idv, od = dict(host=(0, 0, 0), device=(1, 1, 1), frames_on_device=(1, 0, 0), lists_and_out_on_device=(0, 1, 1))[residency]
-    _assert_images(_draw(seg_batches[size], w, h, fd, idv, od))
+    assert_images(_draw(seg_batches[size], w, h, fd, idv, od))
 
 
 @pytest.mark.parametrize("size", rc.SIZES)
@@ -106,7 +61,7 @@ def test_segment_cases_with_strides_above_the_minimum(seg_batches, size):
     w, h = size
     for res in ((1, 1, 1), (0, 0, 0)):
         for pads in ((13, 3, 7), (4, 1, 4)):
-            _assert_images(_draw(seg_batches[size], w, h, *res, seq_pad=pads[0], item_pad=pads[1], out_pad=pads[2]))
+            assert_images(_draw(seg_batches[size], w, h, *res, seq_pad=pads[0], item_pad=pads[1], out_pad=pads[2]))
 
 
 # ------------------------------------------------------------------------------------------------- the undistorted frame
@@ -261,28 +216,13 @@ def test_rectify_between_replayed_steps_of_a_captured_graph():
 TRAJ, FEAT, UNC = rectified.SL2_SCENE_TRAJECTORY, rectified.SL2_SCENE_FEATURES, rectified.SL2_SCENE_UNCERTAINTIES
 
 
-def engine_view(e, seq):
-    """What rectified_cases.scene_list wants, from public accessors only."""
-    feats = [dict(label=f["label"], full=f["fully_initialised"], size=f["state_size"], selected=f["selected"], success=f["success"])
-             for f in e.features(seq)]
-    return dict(cam=e.get_cameras(seq, 1)[0], x=e.total_state(seq), P=e.total_covariance(seq), feats=feats, traj=e.trajectory(seq))
-
-
-def assert_lists_equal(got, want, what):
-    assert got.size == want.size, (what, got.size, want.size, got["kind"].tolist(), want["kind"].tolist())
-    for name in ("kind", "label", "a", "patch", "rgb", "pad"):
-        assert np.array_equal(got[name], want[name]), (what, name, got[name].tolist(), want[name].tolist())
-    # the header fixes the order of every operation behind q, so equality is exact
-    assert got["q"].tobytes() == want["q"].tobytes(), (what, "q", got["q"].tolist(), want["q"].tolist())
-
-
 def check_scene(e, frames, seq0, nseq, layers, marked=None, draw=True):
     """sl2_scene_items against the builder (every field, no skips: asserted); sl2_draw_rectified against sl2_rectify_frame_host
     followed by sl2_draw_items_host on the device's own list."""
     lists = e.scene_items(seq0, nseq, layers, marked)
     built = []
     for i in range(nseq):
-        want, rounded = rc.scene_list(engine_view(e, seq0 + i), layers, -1 if marked is None else int(marked[i]))
+        want, rounded = rc.scene_list(engine_state(e, seq0 + i), layers, -1 if marked is None else int(marked[i]))
         assert rc.skipped_fields(rounded) == 0, "a rounded coordinate lies within 1e-6 of a half-integer: choose another scene"
         assert_lists_equal(lists[i], want, "sequence %d, layers %d" % (seq0 + i, layers))
         assert want.size <= e.scene_item_bound()
@@ -299,44 +239,23 @@ def check_scene(e, frames, seq0, nseq, layers, marked=None, draw=True):
 
 @pytest.fixture(scope="module")
 def shipped_scene():
-    """The shipped four-feature scene after a few steps, three sequences with three cameras' worth of distortion for the frame
-    (the scene's projection uses fku, fkv, u0, v0 alone).  Sequence 1 is then seen from half a metre further back, so that its
-    trajectory lies in front of it; sequence 2 sits out the last step."""
-    pr = Pair(4, rs.SHIPPED_STEPS + 1, batch=3)
-    e = pr.engine
-    for k in range(rs.SHIPPED_STEPS):
-        if k == rs.SHIPPED_STEPS - 1:
-            e.set_active([1, 1, 0])
-        e.go_one_step(pr.frame_batch(k), save_trajectory=True)
-    e.set_active([1, 1, 1])
-    xv, Pxx = e.get_vehicle_state(1, 1)
-    xv[0, 2] -= 0.5
-    e.set_vehicle_state(xv, Pxx, seq0=1)
-    e.set_cameras([dict(pr.cam, kd1=4e-5), dict(pr.cam, kd1=-2e-5, u0=150.25)], seq0=1)
-    yield dict(e=e, frames=pr.frame_batch(rs.SHIPPED_STEPS - 1), pr=pr)
-    e.close()
+    """display_helpers.shipped_scene with three cameras' worth of distortion for the frame (the scene's projection uses fku, fkv,
+    u0, v0 alone)."""
+    for e, pr in dh.shipped_scene():
+        e.set_cameras([dict(pr.cam, kd1=4e-5), dict(pr.cam, kd1=-2e-5, u0=150.25)], seq0=1)
+        yield dict(e=e, frames=pr.frame_batch(dh.SHIPPED_STEPS - 1), pr=pr)
 
 
 @pytest.fixture(scope="module")
 def mapping_scene():
-    """The mapping scene stepped until a partially initialised feature is in flight in both sequences (asserted), batch 2;
-    sequence 1 has one feature deleted by hand on the way, so that the two maps and lists differ."""
-    cam, params, spec, frames, templates = make_mapping_sequence(seed=rs.MAPPING_SEED, n_known=rs.MAPPING_KNOWN, n_frames=rs.MAPPING_FRAMES)
-    B = 2
-    e = Engine(cam, params, B, rs.MAPPING_MAX_FEATURES)
-    e.set_vehicle_state(np.tile(spec.xv0, (B, 1)), np.tile(spec.Pxx0, (B, 1, 1)))
-    e.add_known_features(np.tile(spec.feat_y, (B, 1, 1)), np.tile(spec.xp_org(), (B, 1, 1)), np.tile(templates, (B, 1, 1, 1)))
-    last = 0
-    for k in range(1, rs.MAPPING_FRAMES):
-        if k == 6:
-            assert e.delete_features([-1, 2])[1]
-        e.go_one_step(np.tile(frames[k], (B, 1, 1)), save_trajectory=True, enable_mapping=True)
-        last = k
-        if k >= 8 and all(any(not f["fully_initialised"] for f in e.features(b)) for b in range(B)):
-            break
-    assert all(any(not f["fully_initialised"] for f in e.features(b)) for b in range(B)), "no partial feature in flight"
-    yield dict(e=e, frames=np.tile(frames[last], (B, 1, 1)), cam=cam)
-    e.close()
+    for e, frames, cam in dh.mapping_scene():
+        yield dict(e=e, frames=frames, cam=cam)
+
+
+@pytest.fixture(scope="module")
+def large_map():
+    for e, state, cam in dh.large_map():
+        yield dict(e=e, cam=cam)
 
 
 def test_scene_lists_of_the_shipped_scene(shipped_scene):
@@ -344,9 +263,23 @@ def test_scene_lists_of_the_shipped_scene(shipped_scene):
     built = check_scene(e, frames, 0, 3, TRAJ | FEAT | UNC, np.array([1, -1, 3], np.int32))
     kinds = [b["kind"].tolist() for b in built]
     assert kinds[0] == [rc.RECT, rc.RECT, rc.RING] * 4          # (its trajectory lies behind it: tests/test_rectified_host.py)
-    assert kinds[1][:rs.SHIPPED_STEPS - 1] == [rc.SEGMENT] * (rs.SHIPPED_STEPS - 1) and kinds[1].count(rc.RING) == 4
+    assert kinds[1][:dh.SHIPPED_STEPS - 1] == [rc.SEGMENT] * (dh.SHIPPED_STEPS - 1) and kinds[1].count(rc.RING) == 4
     assert tuple(built[0][built[0]["label"] == 1][0]["rgb"]) == oc.GREEN and tuple(built[2][built[2]["label"] == 3][-1]["rgb"]) == oc.GREEN
     assert all(oc.ring_valid(it["q"]) for b in built for it in b if int(it["kind"]) == rc.RING)
+
+
+def test_large_map_two_rounds_of_slots(large_map):
+    """70 fully initialised features with proper ellipsoids, one sequence: a second round of 64 slots with 6 live lanes, placed
+    behind the first in slot order."""
+    e, cam = large_map["e"], large_map["cam"]
+    frames = oc.frame_of(cam["width"], cam["height"], seed=5)[None]
+    b = check_scene(e, frames, 0, 1, TRAJ | FEAT | UNC, np.array([66], np.int32))[0]
+    kinds = b["kind"].tolist()
+    assert kinds.count(rc.RECT) == 140 and kinds.count(rc.RING) >= 60 and kinds.count(rc.SEGMENT) == 0
+    assert [int(it["label"]) for it in b if int(it["kind"]) == rc.RECT][::2] == list(range(70))          # slot order across the two rounds
+    assert all(oc.ring_valid(it["q"]) for it in b if int(it["kind"]) == rc.RING)
+    assert tuple(b[b["label"] == 66][0]["rgb"]) == oc.GREEN and tuple(b[b["label"] == 65][0]["rgb"]) == oc.YELLOW
+    check_scene(e, frames, 0, 1, UNC, draw=False)
 
 
 @pytest.mark.parametrize("layers", range(8))

@@ -9,28 +9,19 @@ sl2_pick_items_batch against sl2_pick_items_host (which tests/test_world_view_ho
 import numpy as np
 import pytest
 
+import display_helpers as dh
 import overlay_cases as oc
 import rectified_cases as rc
-import rectified_scenes as rs
 import world_view_cases as wc
+from display_helpers import SENTINEL, assert_lists_equal, engine_state
 from mapping_helpers import make_mapping_sequence
-from scenelib2_amd import Engine, _lib, overlay, synth, world_view
+from scenelib2_amd import Engine, _lib, overlay, world_view
 from slam_helpers import Pair
-from test_gpu_rectified import assert_lists_equal
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 ALL = wc.ALL
 SIZES = ((70, 37), (64, 32), (320, 240))
-
-
-def engine_state(e, seq):
-    """What world_view_cases.world_list wants, from public accessors only.  (A partial feature's six states are the entries of
-    the total state at its place in feature_list_ order; sl2_get_partial_feature returns the same six numbers: asserted.)"""
-    feats = [dict(label=f["label"], full=f["fully_initialised"], size=f["state_size"], selected=f["selected"], success=f["success"])
-             for f in e.features(seq)]
-    return dict(x=e.total_state(seq), P=e.total_covariance(seq), feats=feats, traj=e.trajectory(seq))
 
 
 def states_of(e):
@@ -63,64 +54,28 @@ def check_world(S, seq0, nseq, views, layers, marked=None, size=None, background
 
 @pytest.fixture(scope="module")
 def shipped_scene():
-    """The recipe of test_gpu_rectified.py's fixture: the shipped four-feature scene after a few steps, batch 3; sequence 1 is
-    moved half a metre back, sequence 2 sits out the last step."""
-    pr = Pair(4, rs.SHIPPED_STEPS + 1, batch=3)
-    e = pr.engine
-    for k in range(rs.SHIPPED_STEPS):
-        if k == rs.SHIPPED_STEPS - 1:
-            e.set_active([1, 1, 0])
-        e.go_one_step(pr.frame_batch(k), save_trajectory=True)
-    e.set_active([1, 1, 1])
-    xv, Pxx = e.get_vehicle_state(1, 1)
-    xv[0, 2] -= 0.5
-    e.set_vehicle_state(xv, Pxx, seq0=1)
-    yield dict(e=e, states=states_of(e), views=wc.fixed_views(pr.cam), cam=pr.cam)
-    e.close()
+    for e, pr in dh.shipped_scene():
+        yield dict(e=e, states=states_of(e), views=wc.fixed_views(pr.cam), cam=pr.cam)
 
 
 @pytest.fixture(scope="module")
 def mapping_scene():
-    """The recipe of test_gpu_rectified.py's fixture: the mapping scene stepped until a partially initialised feature is in
-    flight in both sequences (asserted), batch 2, max_features 24; sequence 1 has one feature deleted by hand on the way."""
-    cam, params, spec, frames, templates = make_mapping_sequence(seed=rs.MAPPING_SEED, n_known=rs.MAPPING_KNOWN, n_frames=rs.MAPPING_FRAMES)
-    B = 2
-    e = Engine(cam, params, B, rs.MAPPING_MAX_FEATURES)
-    e.set_vehicle_state(np.tile(spec.xv0, (B, 1)), np.tile(spec.Pxx0, (B, 1, 1)))
-    e.add_known_features(np.tile(spec.feat_y, (B, 1, 1)), np.tile(spec.xp_org(), (B, 1, 1)), np.tile(templates, (B, 1, 1, 1)))
-    for k in range(1, rs.MAPPING_FRAMES):
-        if k == 6:
-            assert e.delete_features([-1, 2])[1]
-        e.go_one_step(np.tile(frames[k], (B, 1, 1)), save_trajectory=True, enable_mapping=True)
-        if k >= 8 and all(any(not f["fully_initialised"] for f in e.features(b)) for b in range(B)):
-            break
-    assert all(any(not f["fully_initialised"] for f in e.features(b)) for b in range(B)), "no partial feature in flight"
-    states = states_of(e)
-    for b in range(B):          # the builder's six numbers are sl2_get_partial_feature's
-        st, pos = states[b], 13
-        for f in st["feats"]:
-            if not f["full"]:
-                pf = e.partial_feature(b, 0)["pf"]
-                assert pf is not None and pf["label"] == f["label"] and np.array_equal(pf["y"], st["x"][pos:pos + 6])
-            pos += f["size"]
-    yield dict(e=e, states=states, views=wc.fixed_views(cam), cam=cam)
-    e.close()
+    for e, frames, cam in dh.mapping_scene():
+        states = states_of(e)
+        for b in range(e.batch):          # the builder's six numbers are sl2_get_partial_feature's
+            st, pos = states[b], 13
+            for f in st["feats"]:
+                if not f["full"]:
+                    pf = e.partial_feature(b, 0)["pf"]
+                    assert pf is not None and pf["label"] == f["label"] and np.array_equal(pf["y"], st["x"][pos:pos + 6])
+                pos += f["size"]
+        yield dict(e=e, states=states, views=wc.fixed_views(cam), cam=cam)
 
 
 @pytest.fixture(scope="module")
 def large_map():
-    """70 known features, never stepped, random positive definite Pyy: two rounds of 64 slots, the second with 6 live lanes."""
-    m = wc.large_map()
-    cam = synth.default_camera()
-    e = Engine(cam, synth.default_params(4), 1, 70)
-    e.set_vehicle_state(m["xv"][None], m["Pxx"][None])
-    xo = np.tile(np.array([0.0, 0.0, -0.6, 1.0, 0.0, 0.0, 0.0]), (1, 70, 1))
-    e.add_known_features(m["y"][None], xo, np.full((1, 70, 11, 11), 128, np.uint8))
-    e.set_feature_covariances(m["Pyy"][None])
-    states = states_of(e)
-    assert np.array_equal(states[0]["x"], m["x"]) and np.array_equal(states[0]["P"], m["P"])          # the state tests/test_world_view_host.py checked
-    yield dict(e=e, states=states, views=wc.fixed_views(cam), cam=cam)
-    e.close()
+    for e, state, cam in dh.large_map():
+        yield dict(e=e, states=[state], views=wc.fixed_views(cam), cam=cam)
 
 
 @pytest.fixture(scope="module")
@@ -153,7 +108,7 @@ def test_world_lists_of_the_shipped_scene_through_the_reference_view(shipped_sce
     for b in built:
         kinds, rgbs = b["kind"].tolist(), [tuple(v) for v in b["rgb"].tolist()]
         assert kinds[:16] == [rc.SEGMENT] * 16 and rgbs[:16] == [wc.GREY] * 16 and rgbs[-3:] == [wc.WHITE] * 3
-        assert kinds.count(rc.RECT) == 8 and kinds.count(rc.RING) == 4 and rgbs.count(oc.YELLOW) >= rs.SHIPPED_STEPS - 2
+        assert kinds.count(rc.RECT) == 8 and kinds.count(rc.RING) == 4 and rgbs.count(oc.YELLOW) >= dh.SHIPPED_STEPS - 2
         # (a known feature's Pyy stays 0 until the filter correlates it: its world-frame ellipsoid is a point or nearly one, and a
         # form that is not positive definite is listed and draws nothing - the large map below has proper ellipsoids)
     assert tuple(built[0][built[0]["label"] == 1][0]["rgb"]) == oc.GREEN and tuple(built[2][built[2]["label"] == 3][-1]["rgb"]) == oc.GREEN

@@ -337,7 +337,7 @@ def test_builder_on_the_oracle_s_run_of_the_gpu_scenes_skips_no_field(oracle):
     lies within 1e-6 of a half-integer: the GPU test compares every integer field."""
     from mapping_helpers import make_mapping_sequence, oracle_for
     from slam_helpers import Pair
-    import rectified_scenes as rs
+    import display_helpers as rs
     pr = Pair(4, rs.SHIPPED_STEPS + 1, batch=1, make_engine=False)
     for k in range(rs.SHIPPED_STEPS):
         pr.oracles[0].go_one_step(pr.frames[0][k], True)

@@ -376,7 +376,7 @@ def test_builder_on_the_oracle_s_run_of_the_gpu_scenes_skips_no_field(oracle):
     item appears, the view inside the map cuts and drops what lies behind it, and the view turned away lists nothing."""
     from mapping_helpers import make_mapping_sequence, oracle_for
     from slam_helpers import Pair
-    import rectified_scenes as rs
+    import display_helpers as rs
     pr = Pair(4, rs.SHIPPED_STEPS + 1, batch=1, make_engine=False)
     for k in range(rs.SHIPPED_STEPS):
         pr.oracles[0].go_one_step(pr.frames[0][k], True)
@@ -449,8 +449,18 @@ def test_kernel_source_and_build():
     assert [m.group(1) for m in kernels] == ["k_world_list", "k_pick_items"]
     args = kernels[0].group(2)
     assert "const SeqArrays S" in args and "CameraParams" not in args and "sl2_view view" not in args and "const sl2_view* __restrict__ views" in args
-    for word in ("__ballot", "__shfl_up", "wave_min", "wave_max", "at < item_stride", "launch_draw(", "hipMemsetAsync", "pick_item_hits(", "pick_host_body("):
+    for word in ("wave_min", "wave_max", "hipMemsetAsync", "pick_item_hits(", "pick_host_body(", "list_trajectory(", "list_feature(", "draw_call("):
         assert word in src, word
+    # the list writer the three list kernels share, and the chain the three drawing calls share
+    writer = open(os.path.join(csrc, "sl2_drawlist_dev.hpp")).read()
+    for word in ("__ballot", "__shfl_up", "__device__", "void list_trajectory(", "void list_feature("):
+        assert word in writer, word
+    assert writer.count("at < item_stride") == 1 and "\nSL2_HD " not in writer          # every store goes through the one guarded put(); device code only
+    for name in ("sl2_overlay.hip", "sl2_rectify.hip", "sl2_world_view.hip"):
+        text = open(os.path.join(csrc, name)).read()
+        assert "sl2_drawlist_dev.hpp" in text and "at < item_stride" not in text, name          # no store of its own
+    chain = open(os.path.join(csrc, "sl2_display.hpp")).read()
+    assert "launch_draw(" in chain and "int draw_call(" in chain and "int items_call(" in chain
     dev = open(os.path.join(csrc, "sl2_world_view_dev.hpp")).read()
     assert "SL2_HD bool pick_item_hits" in dev and "overlay_prepare(" in dev and "overlay_hit(" in dev and "scene_conic(" in dev and "scene_segment(" in dev
     mk = open(os.path.join(csrc, "Makefile")).read()
