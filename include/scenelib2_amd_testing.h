@@ -26,6 +26,12 @@ int sl2_debug_set_position_error(sl2_engine* e, int seq, int label, int err);
  * count, one that had to be captured again - because a setter dropped the graphs, or the step's key changed - does. */
 int sl2_debug_graph_captures(sl2_engine* e);
 
+/* The plan launch_update would make now for sequence group `group` of the engine (csrc/sl2_update_plan.hpp: make_update_plan on
+ * the group's shape and the engine's knobs), as update_plan_ints lays it out: build form, threads, nsplit, LDS bytes; Cholesky
+ * form, panel blocks; substitution form, nb, group rows.  n: ints of room in out, at least 9.  Host arithmetic only.  (The plan is this library's: for an engine of
+ * the product library it differs where a step has no product form - which no engine the product library creates reaches.) */
+int sl2_debug_update_plan(sl2_engine* e, int group, int* out, int n);
+
 /* FP64 epilogue of correlate2_warning (improc.cpp:99-133) evaluated ON THE DEVICE
  * for `count` tuples of the five integer sums: checks IEEE div/sqrt parity. */
 int sl2_debug_ncc_score(int device, const int32_t* sums5, int count, double* score, double* sd0, double* sd1);

@@ -12,6 +12,7 @@
 #include "sl2_math.hpp"
 #include "sl2_seq_arrays.hpp"
 #include "sl2_step_plan.hpp"
+#include "sl2_update_plan.hpp"
 
 namespace sl2 {
 
@@ -28,8 +29,6 @@ const char* hip_err_text(hipError_t e);
       return SL2_ERR_HIP;                                                                      \
     }                                                                                          \
   } while (0)
-
-inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // feature flag bits (f_flags)
 enum : int {
@@ -144,10 +143,12 @@ struct sl2_engine : sl2::SeqArrays {
   int mld = 0;       // leading dimension of the innovation system (>= 2 nsel_max, multiple of 32)
   int nblk_max = 0;  // mld / 32
   long long steps_done = 0;
-  int chol_variant = 1;       // 1 = one-launch left-looking Cholesky (k_chol_left; the product's only path); TEST build: 0 = launch-per-block kernels
+  // The dense update's variants: 1 = the product's kernels, 0 = the superseded ones (TEST build).  Which kernel a variant - or
+  // any knob of the update below - selects at which size is make_update_plan's to say (sl2_update_plan.hpp), nobody else's.
+  int chol_variant = 1;       // factorisation: CholForm
   void* chol_trace = nullptr; // development only (SL2_CHOL_TRACE builds): per-wave cycle stamps of k_chol_fused4
-  int build_variant = 1;      // 1 = k_build_AS (A and S in one pass over the measured features' rows of P; the product's only path); TEST build: 0 = k_build_A then k_build_S
-  int fwd_variant = 1;        // forward substitution: 1 = L through LDS + solved rows in registers (<= 8 blocks, default), 0 = operands re-read from memory (any size)
+  int build_variant = 1;      // A and S: BuildForm
+  int fwd_variant = 1;        // forward substitution: FwdForm
   // ---- feature initialisation ----
   int ppos = 0;                          // first column of the partial features' states (13 + 3N); slot k at ppos + 6 k
   int kpart = 1;                         // partial slots per sequence: params.max_features_to_init_at_once, 1 .. kMaxPartial
@@ -166,7 +167,7 @@ struct sl2_engine : sl2::SeqArrays {
   int score_threads = 0;      // once at sl2_create): 0 = the engine's own choice
   int no_ksplit = 0;
   int panel_from = 16;        // systems of more 32-blocks than this are factored panel-wise (launch_chol_panels) ...
-  int group_from = 13;        // ... and substituted in groups of eight block rows (launch_fwdsub_grouped)
+  int group_from = sl2::kFwdLdsMaxBlocks;   // ... and substituted in groups of eight block rows (launch_fwdsub_grouped)
   int fwd_group = 8;          // block rows per group of the grouped substitution (TEST build: SL2_FWD_GROUP = 4 | 8)
   int chol_panel = 8;         // 32-blocks per panel of the large-map Cholesky: 8 (256 columns; 4.3 ms against 5.05 with 4 at
                               // 512 x n = 1513, profiles/r03_c5_chol_panel_ab.txt); TEST build: SL2_CHOL_PANEL = 4 | 8

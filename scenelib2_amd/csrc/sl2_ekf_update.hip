@@ -50,8 +50,6 @@ __device__ __forceinline__ v4d mfma_f64(double a, double b, v4d c) {
 // at 5.0-5.4 TB/s: what bounds it is the 1.5 KB a wavefront keeps in flight, not HBM - k_build_AS_ahead below is the form for
 // launches of one workgroup per sequence; this one serves split launches, smaller batches' ranges and ld > 1024.)
 // ---------------------------------------------------------------------------
-constexpr int kASBatch = 4;   // features per LDS batch (state sizes up to 1024 columns)
-
 // NQ: columns per thread (thread t owns columns t, t + 1024, ...: NQ = 1 for ld <= 1024, 2 up to 2048 - the 1280x720 /
 // 500-feature configuration, ld = 1536); BATCH: features per LDS batch (2 * BATCH * ld doubles of LDS).
 template <int NQ, int BATCH>
@@ -189,12 +187,9 @@ __global__ void __launch_bounds__(1024) k_build_AS(const double* __restrict__ P,
 // a second window (the whole next batch requested before the current one is consumed) needs 93 registers, five wavefronts per
 // SIMD, and is no faster than k_build_AS; coefficients read by all 64 lanes from one LDS address, or the S role's row of H
 // re-read from LDS for each of its eight columns, cost more LDS cycles than the loads they replace.
-// LDS: [2 * BATCH][ld] rows of At, then the table ([tab_cap][kAheadEntry]); one array (launch_update_range keeps the sum inside
+// LDS: [2 * BATCH][ld] rows of At, then the table ([tab_cap][kAheadEntry]); one array (make_update_plan keeps the sum inside
 // kAheadLdsMax so that four workgroups of the headline shape share a CU).
 // ---------------------------------------------------------------------------
-constexpr int kAheadEntry = 24;        // doubles per entry of the measurement table: Hx 0..13, Hy 14..19, nu 20..21, R 22, pos 23 (an integer)
-constexpr int kAheadLdsMax = 40960;    // bytes of LDS per workgroup the form may take (a quarter of the CU's 160 KB)
-
 template <int BATCH>
 struct AheadRows { double v[BATCH][3]; };
 
@@ -891,7 +886,6 @@ __global__ void __launch_bounds__(256, (NB <= 8 ? 3 : 2)) k_fwdsub_lds(const dou
 // their partial sums meet in LDS, and wave 0 applies the inverted diagonal block.  Same sums in a different association
 // (four partial sums): tolerance parity like every other variant.  Up to kKsMaxBlocks 32-blocks.
 // ---------------------------------------------------------------------------
-constexpr int kKsMaxBlocks = 8;
 __global__ void __launch_bounds__(256) k_fwdsub_ksplit(const double* __restrict__ At, double* __restrict__ Vt,
                                                        const double* __restrict__ St, const double* __restrict__ LinvT,
                                                        const int* __restrict__ m_count, int ld, int mld, int nblk_max, int B) {
@@ -1001,17 +995,9 @@ __global__ void __launch_bounds__(256) k_fwdsub_ksplit(const double* __restrict_
   }
 }
 
-static int launch_fwdsub_lds(sl2_engine* e, int B, bool* done) {
-  *done = true;
-  // small batches: the chain-shortening kernel (one 16-column strip per workgroup, products dealt to its four waves)
-  if (e->nblk_max <= kKsMaxBlocks && (long long)B * (e->ld / 16) <= 160 && !e->root->no_ksplit) {
-    LaunchScope ls(e, "k_fwdsub_ksplit", true);
-    hipLaunchKernelGGL(k_fwdsub_ksplit, dim3(xcd_grid(e->ld / 16, B)), dim3(256), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
-                       e->m_gate, e->ld, e->mld, e->nblk_max, B);
-    SL2_HIP(hipGetLastError());
-    return SL2_OK;
-  }
-  if (e->nblk_max > e->root->group_from) { *done = false; return SL2_OK; }     // beyond the register-resident strip (13 blocks): the grouped form
+// the one-launch substitution: k_fwdsub_lds<nb>, nb = the system's blocks (UpdatePlan::fwd_nb)
+static int launch_fwdsub_lds(sl2_engine* e, int nb) {
+  const int B = e->B;
   const dim3 grid(xcd_grid(e->ld / 64, B)), block(256);
   LaunchScope ls(e, "k_fwdsub_lds", true);
 #define SL2_FWD_CASE(NBV)                                                                                           \
@@ -1019,10 +1005,11 @@ static int launch_fwdsub_lds(sl2_engine* e, int B, bool* done) {
     hipLaunchKernelGGL((k_fwdsub_lds<NBV>), grid, block, 0, e->stream, e->At, e->Vt, e->St, e->LinvT, e->m_gate, \
                        e->ld, e->mld, e->nblk_max, B, 0, 0, e->ld / 64, NBV);                                       \
     break;
-  switch (e->nblk_max) {
+  static_assert(kFwdLdsMaxBlocks == 13, "one case per instantiation the plan may name");
+  switch (nb) {
     SL2_FWD_CASE(1) SL2_FWD_CASE(2) SL2_FWD_CASE(3) SL2_FWD_CASE(4) SL2_FWD_CASE(5) SL2_FWD_CASE(6) SL2_FWD_CASE(7)
     SL2_FWD_CASE(8) SL2_FWD_CASE(9) SL2_FWD_CASE(10) SL2_FWD_CASE(11) SL2_FWD_CASE(12) SL2_FWD_CASE(13)
-    default: break;
+    default: set_error("launch_fwdsub_lds: no k_fwdsub_lds of this many blocks"); return SL2_ERR_INVALID;
   }
 #undef SL2_FWD_CASE
   SL2_HIP(hipGetLastError());
@@ -1181,11 +1168,9 @@ __global__ void __launch_bounds__(256) k_chol_syrk(double* __restrict__ St, cons
       }
 }
 
-constexpr int kCholPanelBlocks = 4;
-
-static int launch_chol_panels(sl2_engine* e, int B) {
-  // panel width in 32-blocks: 4 (128 columns) or 8 (256 columns: half as many trailing updates, each with twice the K)
-  const int pb = e->root->chol_panel == 8 ? 8 : kCholPanelBlocks;
+// the large-map Cholesky in panels of pb 32-blocks (UpdatePlan::chol_panel_blocks: kCholPanelBlocks or 8)
+static int launch_chol_panels(sl2_engine* e, int pb) {
+  const int B = e->B;
   for (int p0 = 0; p0 < e->nblk_max; p0 += pb) {
     const int nb = e->nblk_max - p0 < pb ? e->nblk_max - p0 : pb;
     {
@@ -1217,9 +1202,9 @@ static int launch_chol_panels(sl2_engine* e, int B) {
   return SL2_OK;
 }
 
-// substitution in groups of eight (or four: fwd_group) block rows, for systems of more than 13 blocks
-static int launch_fwdsub_grouped(sl2_engine* e, int B) {
-  const int g = e->root->fwd_group == 4 ? 4 : 8;
+// substitution in groups of g = eight or four block rows (UpdatePlan::fwd_group_rows), for systems of more than 13 blocks
+static int launch_fwdsub_grouped(sl2_engine* e, int g) {
+  const int B = e->B;
   for (int J0 = 0; J0 < e->nblk_max; J0 += g) {
     if (J0 > 0) {
       LaunchScope ls(e, "k_fwd_gemm", true);
@@ -1456,150 +1441,96 @@ __global__ void __launch_bounds__(256, 4) k_syrk(const double* __restrict__ Vt, 
     }
 }
 
-#ifdef SL2_TESTING   // section 9 of sl2_ekf_update_testing.inc
+#ifdef SL2_TESTING   // section 9 of sl2_ekf_update_testing.inc: the launchers of the superseded kernels (and a debug GEMM)
 #define SL2_EKF_TEST_SECTION 9
 #include "sl2_ekf_update_testing.inc"
 #undef SL2_EKF_TEST_SECTION
+constexpr bool kSupersededKernels = true;
+#else
+constexpr bool kSupersededKernels = false;
 #endif  // SL2_TESTING
 
+// What make_update_plan takes: the shape of the engine (a sequence group) and the knobs of its root.
+static UpdateShape update_shape(const sl2_engine* e) {
+  const sl2_engine* r = e->root;
+  return {e->B, e->N, e->ld, e->mld, e->nblk_max, e->nsel_max, r->build_variant, r->chol_variant, r->fwd_variant,
+          r->build_split, r->build_ahead, r->build_lds_min, r->no_ksplit, r->panel_from, r->group_from, r->fwd_group,
+          r->chol_panel, kSupersededKernels};
+}
 
+// The update of one sequence group, as its plan says (sl2_update_plan.hpp): build A and S, factor S, substitute, SYRK.  The
+// plan is made per call - a few dozen integer operations - so there is no copy to go stale when a knob changes.
 // Profiling scopes carry the SYMBOL of the kernel they bracket (so that the bench's per-kernel times and rocprofv3's
 // kernel_stats.csv join on the name); "@phase" tells two uses of one kernel apart (k_fwdsub_lds is also the panel solve of
 // the large-map Cholesky).
-static int launch_update_range(sl2_engine* e) {
-  const int B = e->B;     // (succ_idx / m_count, the successful measurements in slot order, come from k_search_score)
-  // Every kernel of the update takes its row count from a pointer and leaves at once on 0 - before it writes anything to x or P
-  // (At / Vt / St / LinvT are rebuilt by every update).  What they are handed is m_gate: m_count for a sequence that takes part in
-  // the step, 0 for a paused one (k_search_score; sl2_set_active_sequences), so a paused sequence costs these kernels one load.
+// Every kernel of the update takes its row count from a pointer and leaves at once on 0 - before it writes anything to x or P
+// (At / Vt / St / LinvT are rebuilt by every update).  What they are handed is m_gate: m_count for a sequence that takes part in
+// the step, 0 for a paused one (k_search_score; sl2_set_active_sequences), so a paused sequence costs these kernels one load.
+// (succ_idx / m_count, the successful measurements in slot order, come from k_search_score.)
+int launch_update(sl2_engine* e) {
+  const UpdatePlan p = make_update_plan(update_shape(e));
+  const int B = e->B;
+  // a step in a form the product has no kernel for: its superseded launcher (TEST build), else the plan's refusal
+  enum { kBuild, kFactor, kSubstitute };
+  auto other_form = [&](int step) -> int {
 #ifdef SL2_TESTING
-  const int build_variant = e->root->build_variant, chol_variant = e->root->chol_variant, fwd_variant = e->root->fwd_variant;
-#else
-  const int chol_variant = 1, fwd_variant = 1;
-#endif
-#ifdef SL2_TESTING
-  if (build_variant == 0) {
-    {
-      LaunchScope ls(e, "k_build_A", true);
-      const int threads = e->ld <= 512 ? e->ld : 512;
-      hipLaunchKernelGGL(k_build_A, dim3(B), dim3(threads), 0, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->succ_idx,
-                         e->m_gate, e->At, e->N, e->ld, e->mld);
-      SL2_HIP(hipGetLastError());
-    }
-    {
-      LaunchScope ls(e, "k_build_S");
-      dim3 grid(e->mld / 32, (e->mld + 255) / 256, B);
-      hipLaunchKernelGGL(k_build_S, grid, dim3(256), 0, e->stream, e->At, e->f_Hx, e->f_Hy, e->f_R, e->succ_idx, e->m_gate,
-                         e->St, e->N, e->ld, e->mld);
-      SL2_HIP(hipGetLastError());
-    }
-  } else
-#endif
-  {
-    // sl2_create admits maps of up to 2048 state columns / 512 measured features
-    LaunchScope ls(e, "k_build_AS", true);
-    // One workgroup per sequence from batch 1024 on (one exact round of four per CU at 1024; it needs the launch in front
-    // of it - k_search_score - to consist of single-wave workgroups, see launch_search).  Smaller batches: ~3000 workgroups
-    // in all, so that the chip is full and a sequence's 25 feature batches are not one chain.
-    int nsplit = B >= 1024 ? 1 : (3072 + B - 1) / B;
-    if (e->root->build_split > 0) nsplit = e->root->build_split;        // experiments (TEST build: SL2_BUILD_SPLIT)
-    if (nsplit < 1) nsplit = 1;
-    const int nbatch_max = (e->N + kASBatch - 1) / kASBatch;
-    if (nsplit > nbatch_max) nsplit = nbatch_max;
-    // One workgroup per sequence, ld <= 1024: the form that keeps a batch of rows in flight (k_build_AS_ahead), with four
-    // features per batch where its LDS (the batch's rows of At + the measurement table of nsel_max entries) stays inside
-    // kAheadLdsMax, else two; where neither does (large maps that also measure many features per frame), k_build_AS.
-    int ahead = 0;
-    if (nsplit == 1 && e->ld <= 1024 && e->root->build_ahead != 0) {
-      const size_t tab = sizeof(double) * kAheadEntry * e->nsel_max;
-      if (sizeof(double) * 2 * 4 * e->ld + tab <= (size_t)kAheadLdsMax) ahead = 4;
-      else if (sizeof(double) * 2 * 2 * e->ld + tab <= (size_t)kAheadLdsMax) ahead = 2;
-    }
-    if (ahead) {
-      size_t shm = sizeof(double) * (2 * ahead * e->ld + kAheadEntry * e->nsel_max);
-      if ((size_t)e->root->build_lds_min > shm) shm = (size_t)e->root->build_lds_min;
-      if (ahead == 4)
-        hipLaunchKernelGGL((k_build_AS_ahead<4>), dim3(B), dim3(e->ld), shm, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->f_R,
-                           e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld, e->nsel_max);
-      else
-        hipLaunchKernelGGL((k_build_AS_ahead<2>), dim3(B), dim3(e->ld), shm, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->f_R,
-                           e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld, e->nsel_max);
-    } else if (e->ld <= 1024) {
-      size_t shm = sizeof(double) * 2 * kASBatch * e->ld;
-      if ((size_t)e->root->build_lds_min > shm) shm = (size_t)e->root->build_lds_min;
-      hipLaunchKernelGGL((k_build_AS<1, kASBatch>), dim3(B, nsplit), dim3(e->ld), shm, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->f_R,
-                         e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld);
-    } else {
-      const size_t shm = sizeof(double) * 2 * 2 * e->ld;      // <= 64 KB
-      hipLaunchKernelGGL((k_build_AS<2, 2>), dim3(B, nsplit), dim3(1024), shm, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->f_R,
-                         e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld);
-    }
-    SL2_HIP(hipGetLastError());
-  }
-  // sl2_create sizes the innovation system so that one of the first two branches always applies (mld a multiple of 128
-  // beyond 16 blocks)
-  if (e->nblk_max > e->root->panel_from && chol_variant >= 1 && e->mld % 64 == 0 && e->nblk_max % kCholPanelBlocks == 0) {
-    int rc = launch_chol_panels(e, B);
-    if (rc != SL2_OK) return rc;
-  } else if (e->nblk_max <= e->root->panel_from && chol_variant == 1) {
-    LaunchScope ls(e, "k_chol_left", true);
-    hipLaunchKernelGGL(k_chol_left, dim3(B), dim3(256), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, 0,
-                       e->nblk_max, (long long*)e->root->chol_trace);
-    SL2_HIP(hipGetLastError());
-  } else {
-#ifdef SL2_TESTING
-    {
-      for (int J = 0; J < e->nblk_max; ++J) {
-        {
-          LaunchScope ls(e, "k_chol_diag");
-          hipLaunchKernelGGL(k_chol_diag, dim3(B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, J);
-          SL2_HIP(hipGetLastError());
-        }
-        const int rem = e->nblk_max - 1 - J;
-        if (rem > 0) {
-          {
-            LaunchScope ls(e, "k_chol_panel");
-            hipLaunchKernelGGL(k_chol_panel, dim3(rem, B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld,
-                               e->nblk_max, J);
-            SL2_HIP(hipGetLastError());
-          }
-          {
-            LaunchScope ls(e, "k_chol_trail");
-            hipLaunchKernelGGL(k_chol_trail, dim3(rem * (rem + 1) / 2, B), dim3(64), 0, e->stream, e->St, e->m_gate, e->mld, J);
-            SL2_HIP(hipGetLastError());
-          }
-        }
-      }
+    switch (step) {
+      case kBuild: if (p.build == BuildForm::kTwoPass) return launch_build_two_pass(e, p.build_threads); break;
+      case kFactor: if (p.chol == CholForm::kPerBlock) return launch_chol_per_block(e); break;
+      case kSubstitute: if (p.fwd == FwdForm::kReread) return launch_fwdsub_reread(e); break;
     }
 #else
-    set_error("launch_update: no factorisation for this system size (sl2_create should have padded it)");
+    (void)step;
+#endif
+    set_error(p.error() ? p.error() : "launch_update: the plan names a kernel this library does not have");
     return SL2_ERR_INVALID;
-#endif
+  };
+  int rc = SL2_OK;
+  // ---- A = P H^T, S = H A + R (sl2_create admits maps of up to 2048 state columns / 512 measured features)
+  const dim3 build_grid(B, p.build_nsplit), build_block(p.build_threads);
+#define SL2_BUILD_CASE(FORM, KERNEL, ...)                                                                                     \
+  case BuildForm::FORM: {                                                                                                     \
+    LaunchScope ls(e, "k_build_AS", true);                                                                                    \
+    hipLaunchKernelGGL(KERNEL, build_grid, build_block, (size_t)p.build_lds_bytes, e->stream, e->P, e->f_Hx, e->f_Hy,         \
+                       e->f_nu, e->f_R, e->succ_idx, e->m_gate, e->At, e->St, e->f_hcol, e->pos_err_any, e->N, e->ld, e->mld, \
+                       ##__VA_ARGS__);                                                                                        \
+    SL2_HIP(hipGetLastError());                                                                                               \
+  } break;
+  switch (p.build) {
+    SL2_BUILD_CASE(kAhead4, (k_build_AS_ahead<4>), e->nsel_max)
+    SL2_BUILD_CASE(kAhead2, (k_build_AS_ahead<2>), e->nsel_max)
+    SL2_BUILD_CASE(kAS14, (k_build_AS<1, kASBatch>))
+    SL2_BUILD_CASE(kAS22, (k_build_AS<2, 2>))
+    default: rc = other_form(kBuild); break;
   }
-  {
-    bool done = false;
-    if (fwd_variant == 1) {
-      int rc = launch_fwdsub_lds(e, B, &done);
-      if (rc != SL2_OK) return rc;
-      // the grouped form works on 64-row tiles: it needs mld to be a multiple of 64 (sl2_create pads systems of more
-      // than 13 blocks to 64, of more than 16 to 128)
-      if (!done && e->mld % 64 == 0) {
-        rc = launch_fwdsub_grouped(e, B);
-        if (rc != SL2_OK) return rc;
-        done = true;
-      }
-    }
-    if (!done) {
-#ifdef SL2_TESTING
-      LaunchScope ls(e, "k_fwdsub", true);
-      hipLaunchKernelGGL(k_fwdsub, dim3(xcd_grid(e->ld / 64, B)), dim3(128), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
+#undef SL2_BUILD_CASE
+  if (rc != SL2_OK) return rc;
+  // ---- S = L L^T
+  switch (p.chol) {
+    case CholForm::kPanels: rc = launch_chol_panels(e, p.chol_panel_blocks); break;
+    case CholForm::kLeft: {
+      LaunchScope ls(e, "k_chol_left", true);
+      hipLaunchKernelGGL(k_chol_left, dim3(B), dim3(256), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, 0,
+                         e->nblk_max, (long long*)e->root->chol_trace);
+      SL2_HIP(hipGetLastError());
+    } break;
+    default: rc = other_form(kFactor); break;
+  }
+  if (rc != SL2_OK) return rc;
+  // ---- V = A L^-T
+  switch (p.fwd) {
+    case FwdForm::kKsplit: {
+      LaunchScope ls(e, "k_fwdsub_ksplit", true);
+      hipLaunchKernelGGL(k_fwdsub_ksplit, dim3(xcd_grid(e->ld / 16, B)), dim3(256), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
                          e->m_gate, e->ld, e->mld, e->nblk_max, B);
       SL2_HIP(hipGetLastError());
-#else
-      set_error("launch_update: no substitution kernel for this system size (sl2_create should have padded it)");
-      return SL2_ERR_INVALID;
-#endif
-    }
+    } break;
+    case FwdForm::kLds: rc = launch_fwdsub_lds(e, p.fwd_nb); break;
+    case FwdForm::kGrouped: rc = launch_fwdsub_grouped(e, p.fwd_group_rows); break;
+    default: rc = other_form(kSubstitute); break;
   }
+  if (rc != SL2_OK) return rc;
+  // ---- P -= V V^T, x += V (L^-1 nu)
   {
     LaunchScope ls(e, "k_syrk", true);
     const int nt = e->ld / 64;
@@ -1615,8 +1546,6 @@ static int launch_update_range(sl2_engine* e) {
   }
   return SL2_OK;
 }
-
-int launch_update(sl2_engine* e) { return launch_update_range(e); }
 
 // k_syrk on the given covariance and V^T, everything else the engine's: sl2_create's placement probe (sl2_engine.hip:
 // place_large_matrices), which fills m_count / n_slots for the occasion - on an engine that holds nothing but zeros the launch

@@ -305,6 +305,64 @@ __global__ void __launch_bounds__(128) k_fwdsub(const double* __restrict__ At, d
 
 #if SL2_EKF_TEST_SECTION == 9
 // ---------------------------------------------------------------------------
+// The launchers of the superseded kernels above: launch_update calls them where the plan (sl2_update_plan.hpp, with
+// UpdateShape::superseded) names their form - BuildForm::kTwoPass, CholForm::kPerBlock, FwdForm::kReread.
+// ---------------------------------------------------------------------------
+static int launch_build_two_pass(sl2_engine* e, int threads) {
+  const int B = e->B;
+  {
+    LaunchScope ls(e, "k_build_A", true);
+    hipLaunchKernelGGL(k_build_A, dim3(B), dim3(threads), 0, e->stream, e->P, e->f_Hx, e->f_Hy, e->f_nu, e->succ_idx,
+                       e->m_gate, e->At, e->N, e->ld, e->mld);
+    SL2_HIP(hipGetLastError());
+  }
+  {
+    LaunchScope ls(e, "k_build_S");
+    dim3 grid(e->mld / 32, (e->mld + 255) / 256, B);
+    hipLaunchKernelGGL(k_build_S, grid, dim3(256), 0, e->stream, e->At, e->f_Hx, e->f_Hy, e->f_R, e->succ_idx, e->m_gate,
+                       e->St, e->N, e->ld, e->mld);
+    SL2_HIP(hipGetLastError());
+  }
+  return SL2_OK;
+}
+
+// three launches per block column
+static int launch_chol_per_block(sl2_engine* e) {
+  const int B = e->B;
+  for (int J = 0; J < e->nblk_max; ++J) {
+    {
+      LaunchScope ls(e, "k_chol_diag");
+      hipLaunchKernelGGL(k_chol_diag, dim3(B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld, e->nblk_max, J);
+      SL2_HIP(hipGetLastError());
+    }
+    const int rem = e->nblk_max - 1 - J;
+    if (rem > 0) {
+      {
+        LaunchScope ls(e, "k_chol_panel");
+        hipLaunchKernelGGL(k_chol_panel, dim3(rem, B), dim3(64), 0, e->stream, e->St, e->LinvT, e->m_gate, e->mld,
+                           e->nblk_max, J);
+        SL2_HIP(hipGetLastError());
+      }
+      {
+        LaunchScope ls(e, "k_chol_trail");
+        hipLaunchKernelGGL(k_chol_trail, dim3(rem * (rem + 1) / 2, B), dim3(64), 0, e->stream, e->St, e->m_gate, e->mld, J);
+        SL2_HIP(hipGetLastError());
+      }
+    }
+  }
+  return SL2_OK;
+}
+
+static int launch_fwdsub_reread(sl2_engine* e) {
+  const int B = e->B;
+  LaunchScope ls(e, "k_fwdsub", true);
+  hipLaunchKernelGGL(k_fwdsub, dim3(xcd_grid(e->ld / 64, B)), dim3(128), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
+                     e->m_gate, e->ld, e->mld, e->nblk_max, B);
+  SL2_HIP(hipGetLastError());
+  return SL2_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Debug GEMM on the same fragment conventions (tests the MFMA layout):
 // C[m][n] = sum_k XT[k][m] YT[k][n], one wave per 32x32 tile.
 // ---------------------------------------------------------------------------
@@ -331,6 +389,13 @@ __global__ void __launch_bounds__(64) k_gemm_kt(const double* __restrict__ XT, i
 
 #if SL2_EKF_TEST_SECTION == 10
 #include "../../include/scenelib2_amd_testing.h"
+extern "C" int sl2_debug_update_plan(sl2_engine* e, int group, int* out, int n) {
+  using namespace sl2;
+  if (!e || !out || group < 0 || group >= (int)e->root->groups.size() || n < kUpdatePlanInts) return SL2_ERR_INVALID;
+  update_plan_ints(make_update_plan(update_shape(e->root->groups[group])), out);
+  return SL2_OK;
+}
+
 extern "C" int sl2_debug_gemm_kt(int device, const double* XT, int ldx, const double* YT, int ldy, int M, int N, int K,
                                  double* C, int ldc) {
   using namespace sl2;

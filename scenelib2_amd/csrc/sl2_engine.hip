@@ -443,30 +443,22 @@ int sl2_create(const sl2_camera* cam, const sl2_params* params, int batch, int m
   if (e->prm.minimum_attempted_measurements_of_feature <= 0) e->prm.minimum_attempted_measurements_of_feature = 10;
   if (!(e->prm.successful_match_fraction > 0.0)) e->prm.successful_match_fraction = 0.5;
   e->B = batch; e->N = max_features;
-  // columns: xv(13), 3 per feature slot, 6 per partially initialised feature in flight (params.max_features_to_init_at_once of
-  // them, the shipped value is 1), 1 for the innovation (At / Vt)
+  // partially initialised features in flight: params.max_features_to_init_at_once of them, the shipped value is 1
   e->kpart = params->max_features_to_init_at_once < 1 ? 1 : (params->max_features_to_init_at_once > kMaxPartial ? kMaxPartial : params->max_features_to_init_at_once);
   e->search_split = srch_split_default(e->cam.width, e->cam.height);
-  e->ld = round_up(13 + 3 * max_features + 6 * e->kpart + 1, 64);
-  e->ppos = 13 + 3 * max_features;
-  int nsel = params->number_of_features_to_select;
-  if (nsel < 1) nsel = 1;
-  if (nsel > max_features) nsel = max_features;
-  e->nsel_max = nsel;
 #ifdef SL2_TESTING   // TEST build: SL2_PANEL_FROM moves the block count from which the panel-wise / grouped forms take over
   if (const char* v = getenv("SL2_PANEL_FROM")) e->panel_from = e->group_from = atoi(v);
 #endif
-  e->mld = round_up(2 * nsel, 32);
-  if (e->mld / 32 > e->group_from) e->mld = round_up(2 * nsel, 64);    // beyond the one-launch substitution: 64-row tiles (k_fwd_gemm)
-  if (e->mld / 32 > e->panel_from) e->mld = round_up(2 * nsel, 128);   // large systems are factored in panels of 128 / 256 columns
-  e->nblk_max = e->mld / 32;
+  // the state's columns and the innovation system's padded rows (sl2_update_plan.hpp)
+  const UpdateSizes sizes = update_sizes(max_features, params->number_of_features_to_select, e->kpart, e->group_from, e->panel_from);
+  e->ld = sizes.ld; e->ppos = sizes.ppos; e->nsel_max = sizes.nsel_max; e->mld = sizes.mld; e->nblk_max = sizes.nblk_max;
   {   // depth particles of the partially initialised feature: any count up to 1024 (the reference loops over any number)
     int np = params->number_of_particles;
     np = np < 1 ? 1 : (np > kMaxParticles ? kMaxParticles : np);
     e->pcap = round_up(np, 64);
   }
 #ifndef SL2_TESTING
-  if (e->ld > 2048 || e->mld > 1024) {   // k_build_AS: two state columns per thread of a 1024-thread workgroup, one H row per thread
+  if (!update_sizes_admitted(sizes)) {
     set_error("sl2_create: at most 676 feature slots (2048 state columns) and 512 features measured per frame");
     return SL2_ERR_CAPACITY;
   }

@@ -566,6 +566,21 @@ class Engine:
         T = _lib.load_testing()
         _lib.check(T.sl2_debug_set_position_error(self.h, seq, label, err), T)
 
+    UPDATE_PLAN_FIELDS = ("build", "build_threads", "build_nsplit", "build_lds_bytes", "chol", "chol_panel_blocks",
+                          "fwd", "fwd_nb", "fwd_group_rows")
+    BUILD_FORMS = ("two-pass", "<1,4>", "<2,2>", "ahead<4>", "ahead<2>")       # sl2_update_plan.hpp: BuildForm, CholForm, FwdForm
+    CHOL_FORMS = ("none", "left", "panels", "per-block")
+    FWD_FORMS = ("none", "ksplit", "lds", "grouped", "re-read")
+
+    def debug_update_plan(self, group=0):
+        # test hook (TEST build only): the plan launch_update would make now for a sequence group, forms by name
+        T = _lib.load_testing()
+        out = np.zeros(len(self.UPDATE_PLAN_FIELDS), dtype=np.int32)
+        _lib.check(T.sl2_debug_update_plan(self.h, group, _lib.ip(out), out.size), T)
+        p = dict(zip(self.UPDATE_PLAN_FIELDS, (int(v) for v in out)))
+        p.update(build=self.BUILD_FORMS[p["build"]], chol=self.CHOL_FORMS[p["chol"]], fwd=self.FWD_FORMS[p["fwd"]])
+        return p
+
     def delete_features(self, labels, seq0=0):
         """mark_feature_by_lab + delete_feature, one label per sequence (-1: none); returns the per-sequence bool."""
         lab = np.ascontiguousarray(labels, dtype=np.int32)

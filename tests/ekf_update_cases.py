@@ -1,16 +1,17 @@
 """The case table of the dense EKF update's edges (sl2_ekf_update.hip): every k_fwdsub_lds<NB> instantiation, the block and
 chunk remainders of m, systems that shrink from one update to the next on one engine, mixed systems in one launch, both sides of
-every dispatch boundary of launch_update_range / launch_fwdsub_lds, the forms of k_build_AS and the live-tile rules of k_syrk.
+every dispatch boundary of the update plan (sl2_update_plan.hpp), the forms of k_build_AS and the live-tile rules of k_syrk.
 Pure numpy and the CPU oracle: tests/test_ekf_update_cases_host.py shows on the oracle alone that every schedule reaches the m
 values it exists for, that the truth of tests/ekf_update_truth.py agrees with the oracle, and that the sizes and kernels written
-in the table follow from the sizing rules; tests/test_gpu_ekf_update_edges.py holds the engine to truth and oracle on them.
+in the table are what the compiled plan makes of the case; tests/test_gpu_ekf_update_edges.py holds the engine to truth and
+oracle on them, and the engine's own plan to the table.
 
 A case is stepped by the seams (predict, auto_select_n_features(n), make_measurements, update, finish_step) with the n of its
 schedule, one entry a frame; feature_sigma = 0.004 everywhere, so P is dense and every live tile changes.  The oracle has no
 seam for the symmetrisation at the end of GoOneStep: its P keeps the rounding-level asymmetry of its update from frame to frame,
 five decades below TOL_P.
 
-Where the table departs from the shapes first proposed for it, the sizing rules are the reason (the host test recomputes them):
+Where the table departs from the shapes first proposed for it, the sizing rules are the reason (the host test asks the plan):
   * sl2_create clamps number_of_features_to_select to the capacity, so nblk_max = NB needs a capacity of at least 16 NB - 15
     slots: group a runs its 24 live features in engines of max(24, 16 NB) slots, and selects min(n, 16 NB) of them;
   * ld = roundup(13 + 3 N + 6 + 1, 64) is 1024 up to N = 334 and 1088 from 335 on: that pair is the k_build_AS<1,4> / <2,2> edge;
@@ -61,7 +62,8 @@ class Case:
         self.env = dict(env or {})                                   # switches of the TEST build, set around sl2_create only
         # what sl2_create and the dispatch must make of it
         self.ld, self.mld, self.nblk_max = ld, mld, mld // 32
-        self.fwd, self.chol, self.build, self.nsplit = fwd, chol, build, nsplit    # fwd: "ksplit", "lds<NB>" or "grouped"
+        # fwd: "ksplit", "lds<NB>" or "grouped"; build: "<1,4>", "<2,2>" (k_build_AS), "ahead<4>" or "ahead<2>" (k_build_AS_ahead)
+        self.fwd, self.chol, self.build, self.nsplit = fwd, chol, build, nsplit
         self.must_run, self.must_not_run = chain
         # what the schedule exists to hit
         self.m = set(m)                                              # values of m, each on some frame of some sequence
@@ -133,8 +135,10 @@ def _cases():
     for N in (5, 6, 7, 8):
         out.append(Case("f_build_N%d" % N, [N, N], N, N, [N, N], ld=64, mld=32, fwd="ksplit", chain=KSPLIT_CHAIN, nsplit=2, m=(2 * N,)))
         out.append(Case("f_build_N%d_one_workgroup" % N, [N, N], N, N, [N, N], ld=64, mld=32, fwd="ksplit", chain=KSPLIT_CHAIN,
-                        env={"SL2_BUILD_SPLIT": "1"}, nsplit=1, m=(2 * N,)))
+                        env={"SL2_BUILD_SPLIT": "1"}, build="ahead<4>", nsplit=1, m=(2 * N,)))
     out.append(Case("f_build_ld1024", [24, 24], 334, 24, [24, 9], ld=1024, mld=64, fwd="ksplit", chain=KSPLIT_CHAIN, build="<1,4>", nsplit=84, m=(48, 18)))
+    out.append(Case("f_build_ld1024_one_workgroup", [24, 24], 334, 24, [24, 9], ld=1024, mld=64, fwd="ksplit", chain=KSPLIT_CHAIN,
+                    env={"SL2_BUILD_SPLIT": "1"}, build="ahead<2>", nsplit=1, m=(48, 18)))
     out.append(Case("f_build_ld1088", [24, 24], 335, 24, [24, 9], ld=1088, mld=64, fwd="ksplit", chain=KSPLIT_CHAIN, build="<2,2>", nsplit=84, m=(48, 18)))
     out.append(Case("f_build_deleted_slot", [12, 12], 12, 12, [12, 12], ld=64, mld=32, fwd="ksplit", chain=KSPLIT_CHAIN, nsplit=3, m=(24, 22),
                     delete={1: 5}, shrinks=True))
@@ -150,38 +154,11 @@ BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 
 
-# ------------------------------------------------------------------------------- the sizing rules, restated from the sources
-def sizing(max_features, n_select, batch, env):
-    """ld, mld, nblk_max (sl2_create) and the kernels launch_update_range / launch_fwdsub_lds choose for them."""
-    up = lambda a, b: (a + b - 1) // b * b
-    ld = up(13 + 3 * max_features + 6 * 1 + 1, 64)                   # max_features_to_init_at_once = 1
-    nsel = min(max(n_select, 1), max_features)
-    panel_from, group_from = 16, 13
-    if "SL2_PANEL_FROM" in env:
-        panel_from = group_from = int(env["SL2_PANEL_FROM"])
-    mld = up(2 * nsel, 32)
-    if mld // 32 > group_from:
-        mld = up(2 * nsel, 64)
-    if mld // 32 > panel_from:
-        mld = up(2 * nsel, 128)
-    nblk = mld // 32
-    if nblk > panel_from and mld % 64 == 0 and nblk % 4 == 0:
-        chol = "panels"
-    else:
-        assert nblk <= panel_from
-        chol = "left"
-    if nblk <= 8 and batch * (ld // 16) <= 160 and "SL2_NO_KSPLIT" not in env:
-        fwd = "ksplit"
-    elif nblk > group_from:
-        assert mld % 64 == 0
-        fwd = "grouped"
-    else:
-        fwd = "lds<%d>" % nblk
-    nsplit = 1 if batch >= 1024 else (3072 + batch - 1) // batch
-    if int(env.get("SL2_BUILD_SPLIT", 0)) > 0:
-        nsplit = int(env["SL2_BUILD_SPLIT"])
-    nsplit = min(max(nsplit, 1), (max_features + 3) // 4)
-    return dict(ld=ld, mld=mld, nblk_max=nblk, chol=chol, fwd=fwd, build="<1,4>" if ld <= 1024 else "<2,2>", nsplit=nsplit)
+# ----------------------------------------------------------------------------------------------- the table and the plan
+def plan_in_table_words(p):
+    """A plan (Engine.debug_update_plan, update_plan_helpers.plan_of_engine) as the table writes it: build, nsplit, chol, fwd."""
+    assert p["chol"] in ("left", "panels") and p["fwd"] in ("ksplit", "lds", "grouped"), p      # the product's forms only
+    return p["build"], p["build_nsplit"], p["chol"], "lds<%d>" % p["fwd_nb"] if p["fwd"] == "lds" else p["fwd"]
 
 
 def chain_of(fwd, chol):

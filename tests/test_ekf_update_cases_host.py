@@ -5,14 +5,15 @@ the schedule through their seams, and
      the case never skips;
   2. the oracle's own posterior lies inside the truth bound at C_BOUND: the bound is sane before a kernel is held to it;
   3. the truth of tests/ekf_update_truth.py reproduces the oracle's posterior at TOL_X and TOL_P (TOL_P_LARGE from n = 613 on);
-  4. ld, mld, nblk_max, the form of k_build_AS and the kernels of the case, recomputed from the sizing rules of sl2_create and
-     launch_update_range / launch_fwdsub_lds, are what the table says.
+  4. ld, mld, nblk_max, the form of k_build_AS and the kernels of the case are what the engine's own sizing and update plan
+     (sl2_update_plan.hpp, compiled for the host) make of the case's arguments.
 No GPU: tests/test_gpu_ekf_update_edges.py holds the engine to the same truth and the same oracles on the same cases."""
 import numpy as np
 import pytest
 
 import ekf_update_cases as uc
 import ekf_update_truth as tr
+import update_plan_helpers as uh
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -47,10 +48,12 @@ def test_truth_on_a_system_with_a_known_answer():
 # --------------------------------------------------------------------------------------------- 4: the sizes and the kernels
 @pytest.mark.parametrize("case", uc.CASES, ids=repr)
 def test_table_follows_from_the_sizing_rules(case):
-    s = uc.sizing(case.max_features, case.n_select, case.batch, case.env)
-    assert (case.ld, case.mld, case.nblk_max, case.chol, case.fwd, case.build, case.nsplit) == (
-        s["ld"], s["mld"], s["nblk_max"], s["chol"], s["fwd"], s["build"], s["nsplit"]), (case, s)
-    run, never = uc.chain_of(s["fwd"], s["chol"])
+    """The rules are the compiled ones: update_sizes and make_update_plan of sl2_update_plan.hpp, built for the host
+    (tests/test_update_plan_host.py holds them to the rules of the code before the plan)."""
+    sizes, plan = uh.plan_of_engine(case.max_features, case.n_select, case.batch, case.env, superseded=bool(case.env))
+    assert sizes["admitted"] and (case.ld, case.mld, case.nblk_max) == (sizes["ld"], sizes["mld"], sizes["nblk_max"]), (case, sizes)
+    assert (case.build, case.nsplit, case.chol, case.fwd) == uc.plan_in_table_words(plan), (case, plan)
+    run, never = uc.chain_of(case.fwd, case.chol)
     assert set(case.must_run) == run and set(case.must_not_run) == never
     assert max(case.counts) <= case.max_features and len(case.schedule) >= 1
 
@@ -66,6 +69,7 @@ def test_table_covers_every_instantiation_and_both_sides_of_every_boundary():
     assert (by["e_select256"].nblk_max, by["e_select257"].nblk_max) == (16, 20)
     assert (by["e_panel_from_2"].nblk_max, by["e_panel_from_2"].chol, by["e_panel_from_2"].fwd) == (12, "panels", "grouped")
     assert (by["f_build_ld1024"].build, by["f_build_ld1088"].build) == ("<1,4>", "<2,2>")
+    assert {c.build for c in uc.CASES} == {"<1,4>", "<2,2>", "ahead<4>", "ahead<2>"}        # both plain forms, both ahead forms
     assert sorted(c.max_features % 4 for c in uc.CASES if c.name.startswith("f_build_N") and not c.env) == [0, 1, 2, 3]
     assert sorted(13 + 3 * c.counts[0] for c in uc.CASES if c.group == "g") == [28, 31, 34, 61, 64, 67]
 

@@ -22,8 +22,10 @@ TOL_X, TOL_P = 1e-12, 1e-11           # tests/test_gpu_slam.py: engine against t
 FEATURE_SIGMA = 0.004                 # a dense P: every live entry of A^T and S changes
 
 
-def twins(pr, batch, max_features, monkeypatch):
-    """(engine with k_build_AS, engine with k_build_AS_ahead), one workgroup per sequence in both."""
+def twins(pr, batch, max_features, monkeypatch, form="ahead<4>"):
+    """(engine with k_build_AS, engine with k_build_AS_ahead), one workgroup per sequence in both: their update plans
+    (sl2_update_plan.hpp, read back through the TEST build's hook) are k_build_AS<1,4> and the given ahead form, the dynamic
+    LDS each form asks for, and otherwise the same plan."""
     lib = _lib.load_testing()
     out = []
     for ahead in ("0", "1"):
@@ -36,6 +38,13 @@ def twins(pr, batch, max_features, monkeypatch):
             monkeypatch.delenv("SL2_BUILD_AHEAD", raising=False)
         e.set_step_fusion(False)
         out.append(e)
+    p0, p1 = (e.debug_update_plan() for e in out)
+    ld = (13 + 3 * max_features + 6 + 1 + 63) // 64 * 64
+    nsel = min(pr.params["number_of_features_to_select"], max_features)
+    assert (p0["build"], p1["build"]) == ("<1,4>", form), (p0, p1)
+    assert p0["build_lds_bytes"] == 8 * 2 * 4 * ld and p1["build_lds_bytes"] == 8 * (2 * int(form[6]) * ld + 24 * nsel), (p0, p1)
+    assert {k for k in p0 if p0[k] != p1[k]} == {"build", "build_lds_bytes"}, (p0, p1)
+    assert p0["build_nsplit"] == 1 and p0["build_threads"] == ld
     return out
 
 
@@ -104,7 +113,7 @@ def test_largest_ld(monkeypatch):
     """334 slots: ld = 1024, the largest the form takes (two features per batch there); 24 live features, m = 48 then 18."""
     B = 2
     pr = Pair(24, 2, batch=B, make_engine=False, feature_sigma=FEATURE_SIGMA)
-    e0, e1 = twins(pr, B, 334, monkeypatch)
+    e0, e1 = twins(pr, B, 334, monkeypatch, form="ahead<2>")
     seen = set()
     for k, n in enumerate((24, 9)):
         seam_frame((e0, e1), pr.frame_batch(k), n)

@@ -49,6 +49,8 @@ def run_case(case, monkeypatch):
     pr = uc.scene(case)
     oracles = uc.fresh_oracles(pr)
     e = uc.make_engine(case, pr, monkeypatch)
+    # the plan launch_update makes for this engine is the table's (one host call; the kernels asserted by name below ran from it)
+    assert uc.plan_in_table_words(e.debug_update_plan()) == (case.build, case.nsplit, case.chol, case.fwd), (case, e.debug_update_plan())
     e.set_profiling(2)
     ms_by_frame, worst = [], dict(P=0.0, x=0.0)
     for k, n in enumerate(case.schedule):

@@ -4,7 +4,8 @@ The form exists to keep more bytes in flight per CU than k_build_AS, so what it 
 (five wavefronts per SIMD; the kernel as measured uses 80, six per SIMD), nothing spilled, and at most 40 KB of LDS per workgroup - four workgroups of the headline shape
 (ld = 320: five wavefronts each) share a CU's 160 KB, twenty wavefronts per CU.  Its LDS is dynamic: 2 * BATCH rows of At of ld
 doubles and the measurement table, kAheadEntry doubles for each of the engine's number_of_features_to_select.
-launch_update_range takes BATCH = 4 where that fits kAheadLdsMax, else 2, else k_build_AS; the rule is restated here."""
+make_update_plan (sl2_update_plan.hpp, where the two constants live) takes BATCH = 4 where that fits kAheadLdsMax, else 2, else
+k_build_AS; the rule is restated here."""
 import os
 import re
 import shutil
@@ -16,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "scenelib2_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 SRC = "sl2_ekf_update.hip"
+PLAN_HDR = "sl2_update_plan.hpp"
 MAX_REGS, MAX_LDS = 96, 40 * 1024
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
@@ -43,13 +45,13 @@ def field(block, name):
 
 
 def constexpr(name):
-    m = re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(CSRC, SRC)).read())
-    assert m, "%s not found in %s" % (name, SRC)
+    m = re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(CSRC, PLAN_HDR)).read())
+    assert m, "%s not found in %s" % (name, PLAN_HDR)
     return int(m.group(1))
 
 
 def launch_choice(ld, nsel):
-    """(BATCH, dynamic LDS bytes) of launch_update_range for one workgroup per sequence, or (0, 0): k_build_AS."""
+    """(BATCH, dynamic LDS bytes) of make_update_plan for one workgroup per sequence, or (0, 0): k_build_AS."""
     entry, cap = constexpr("kAheadEntry"), constexpr("kAheadLdsMax")
     if ld > 1024:
         return 0, 0
