@@ -453,11 +453,31 @@ void sl2_ingest_close(sl2_ingest* g);
  *   pixel  with the column taps (x0, x1, a0, a1) and the row taps (y0, y1, b0, b1), in 32-bit integers: H(y) = g[y][x0] a0 + g[y][x1] a1;
  *          out = (((b0 (H(y0) >> 4)) >> 16) + ((b1 (H(y1) >> 4)) >> 16) + 2) >> 2.
  * It is the identity where source and output size agree and maps a constant image to itself.  The taps are evaluated on the host
- * and uploaded as tables: the kernel and sl2_convert_frame_host do integer work on the same tables and agree byte for byte. */
-enum { SL2_PIX_GRAY8 = 0, SL2_PIX_RGB24 = 1, SL2_PIX_BGR24 = 2, SL2_PIX_UYVY = 3, SL2_PIX_YUYV = 4 };
+ * and uploaded as tables: the kernel and sl2_convert_frame_host do integer work on the same tables and agree byte for byte.
+ *
+ * Machine-vision cameras (GenICam / USB3 Vision / GigE: Mono10 / Mono12 / Mono16, BayerRG8 and its siblings) deliver deep grey or a
+ * raw Bayer mosaic.  Their grey g[y][x] is defined here - no OpenCV exists to compare with: parity with OpenCV unpinned - and both
+ * resize filters then act on it exactly as on the grey of the five formats above:
+ *   deep grey, N = 10, 12, 16   16-bit little-endian words: v = row[2 x] | row[2 x + 1] << 8; g = (v & (2^N - 1)) >> (N - 8): the top
+ *          eight significant bits, truncated; bits above N are ignored.  offset and pitch are even, and so is the address of a raw
+ *          buffer that is on the device.  (Big-endian 16-bit needs no format: truncated to its top byte it is a SL2_PIX_YUYV source.)
+ *   Bayer  one byte a pixel, p[y][x]; the format's name is the 2 x 2 tile at the SOURCE's pixel (0,0), top row then bottom row, so
+ *          the colour of site (x, y) is letter (y & 1) * 2 + (x & 1) of the name, and a region of interest that starts on an odd
+ *          sensor column or row is the matching sibling.  Indices are reflected about the edge pixel (-1 -> 1, S -> S - 2), which
+ *          keeps the colour phase; width and height are at least 2, odd sizes allowed.  With c = p[y][x], h2 = left + right,
+ *          v2 = up + down, cross4 = h2 + v2 and diag4 = the four diagonals, (R4, G4, B4) is
+ *            at a red site (4 c, cross4, diag4), at a blue site (diag4, cross4, 4 c),
+ *            at a green site with red to its left and right (2 h2, 4 c, 2 v2), with blue to its left and right (2 v2, 4 c, 2 h2),
+ *          and g = (4899 R4 + 9617 G4 + 1868 B4 + 32768) >> 16: bilinear demosaic in exact quarters, then the grey weights above,
+ *          one rounding (at most 16384 * 1020 + 32768: 32 bits).  A constant mosaic maps to itself; a mosaic sampled from a flat
+ *          colour (R, G, B) gives the RGB24 grey of (R, G, B) at every pixel.
+ * Not covered: Bayer in 10, 12 or 16-bit containers, packed 10 or 12-bit (Mono12p), edge-aware demosaic, white balance, gamma. */
+enum { SL2_PIX_GRAY8 = 0, SL2_PIX_RGB24 = 1, SL2_PIX_BGR24 = 2, SL2_PIX_UYVY = 3, SL2_PIX_YUYV = 4,      /* 5 .. 15: unassigned */
+       SL2_PIX_GRAY10 = 16, SL2_PIX_GRAY12 = 17, SL2_PIX_GRAY16 = 18,      /* 16-bit little-endian words, the low N bits significant */
+       SL2_PIX_BAYER_RGGB8 = 24, SL2_PIX_BAYER_GRBG8 = 25, SL2_PIX_BAYER_GBRG8 = 26, SL2_PIX_BAYER_BGGR8 = 27 };
 typedef struct sl2_frame_source {        /* 24 bytes */
-  int32_t width, height;                 /* source pixels: 1 .. 4096 by 1 .. 16384; even width for the 4:2:2 formats */
-  int32_t pitch;                         /* bytes from one source row to the next, >= the row's own bytes */
+  int32_t width, height;                 /* source pixels: 1 .. 4096 by 1 .. 16384; even width for the 4:2:2 formats; 2 at least for Bayer */
+  int32_t pitch;                         /* bytes from one source row to the next, >= the row's own bytes; even for the 16-bit formats */
   int32_t format;                        /* SL2_PIX_* */
   uint64_t offset;                       /* of this sequence's first byte inside the raw buffer */
 } sl2_frame_source;
@@ -468,7 +488,8 @@ void sl2_converter_destroy(sl2_converter* c);
 /* The sources of sequences seq0 .. seq0 + nseq - 1.  A setup call: it may wait (for the last conversion queued, which keeps the
  * tables it was queued with) and takes effect for the sl2_convert_frames calls after it.  Two sequences may name the same bytes
  * (one camera feeding two filters).  Refused (SL2_ERR_INVALID, nothing changed, the text names the sequence): width or height
- * below 1 or over the cap, pitch below the bytes of a row, an odd width with a 4:2:2 format, an unknown format.
+ * below 1 or over the cap, pitch below the bytes of a row, an odd width with a 4:2:2 format, an unknown format, a Bayer source
+ * under 2 pixels on an axis, an odd offset or pitch with a 16-bit format.
  * sl2_converter_get_sources returns what was set (SL2_ERR_INVALID for a sequence never set). */
 int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, const sl2_frame_source* src);
 int sl2_converter_get_sources(const sl2_converter* c, int seq0, int nseq, sl2_frame_source* src);
@@ -490,7 +511,7 @@ int sl2_convert_frame_host(const sl2_frame_source* src, const void* raw, size_t 
  * webcam, but it reads two source rows and two source columns per output pixel whatever the reduction, and what lies between them
  * aliases.  SL2_RESIZE_AREA is the exact box average: every source pixel under an output pixel, weighted by the area they share.
  * Integers only, no tables (scenelib2_amd/csrc/sl2_convert_dev.hpp):
- *   grey    g[y][x] as above, all five formats.
+ *   grey    g[y][x] as above, all formats.
  *   weights along an axis of S source and D output pixels, S >= D, in units of 1/D of a source pixel: output d covers
  *           [d S, (d + 1) S), source i covers [i D, (i + 1) D).  The taps of d are i = floor(d S / D) .. floor(((d + 1) S - 1) / D) and
  *           w(d, i) = min((i + 1) D, (d + 1) S) - max(i D, d S): 1 .. D each, summing to S over one output and to D over one source.
@@ -506,6 +527,7 @@ int sl2_convert_frame_host(const sl2_frame_source* src, const void* raw, size_t 
  * set and is smaller than the output on an axis.  sl2_converter_set_sources refuses such a source for a sequence whose filter is
  * SL2_RESIZE_AREA.  sl2_converter_get_filters works for any sequence, its source set or not.
  * sl2_convert_frames then issues one more launch (k_convert_area) for the SL2_RESIZE_AREA sequences; with none it is unchanged.
+ * Deep grey and Bayer sequences likewise have a launch of their own per filter (k_raw_linear, k_raw_area): four launches at most.
  * sl2_convert_frame_host_filtered: the host form; with SL2_RESIZE_LINEAR the bytes of sl2_convert_frame_host.  Its refusals, plus
  * an unknown filter and a source smaller than the output under SL2_RESIZE_AREA. */
 enum { SL2_RESIZE_LINEAR = 0, SL2_RESIZE_AREA = 1 };

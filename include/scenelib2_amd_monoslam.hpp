@@ -217,7 +217,8 @@ class MonoSLAM {
   }
 
   // What the camera delivers (UsbCamGrabber::operator(), usbcamgrabber.cpp:75-113): its size, the bytes from one row to the next and
-  // the pixel format (SL2_PIX_*).  GoOneStepRaw then takes such frames.  The converter and the device frame are created on the
+  // the pixel format (SL2_PIX_*: the webcam's 8-bit formats, or a machine-vision camera's SL2_PIX_GRAY10 / 12 / 16 and
+  // SL2_PIX_BAYER_*8).  GoOneStepRaw then takes such frames.  The converter and the device frame are created on the
   // first call; a later call names another source (a camera that changed its mode).
   void SetFrameSource(int width, int height, int pitch, int format) {
     if (!eng_) throw std::runtime_error("MonoSLAM::SetFrameSource: call Init first");

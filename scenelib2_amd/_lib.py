@@ -99,6 +99,9 @@ class sl2_frame_source(C.Structure):
 
 
 SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_BGR24, SL2_PIX_UYVY, SL2_PIX_YUYV = range(5)
+# machine-vision sources: 16-bit little-endian words with the low N bits significant; Bayer mosaics named by the tile at pixel (0,0)
+SL2_PIX_GRAY10, SL2_PIX_GRAY12, SL2_PIX_GRAY16 = 16, 17, 18
+SL2_PIX_BAYER_RGGB8, SL2_PIX_BAYER_GRBG8, SL2_PIX_BAYER_GBRG8, SL2_PIX_BAYER_BGGR8 = 24, 25, 26, 27
 SL2_RESIZE_LINEAR, SL2_RESIZE_AREA = 0, 1
 # sections of a snapshot blob (sl2_snapshot_batch); the header, xv_ and Pxx_ are always present
 SL2_SNAP_POSE, SL2_SNAP_FEATURES, SL2_SNAP_COV, SL2_SNAP_SELECTION, SL2_SNAP_TRAJ, SL2_SNAP_PARTIAL, SL2_SNAP_PATCHES = 0, 1, 2, 4, 8, 16, 32

@@ -11,10 +11,17 @@ import numpy as np
 
 from . import _lib
 from ._lib import SL2_PIX_BGR24, SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_UYVY, SL2_PIX_YUYV  # noqa: F401
+from ._lib import SL2_PIX_GRAY10, SL2_PIX_GRAY12, SL2_PIX_GRAY16  # noqa: F401
+from ._lib import SL2_PIX_BAYER_BGGR8, SL2_PIX_BAYER_GBRG8, SL2_PIX_BAYER_GRBG8, SL2_PIX_BAYER_RGGB8  # noqa: F401
 
-FORMATS = {"gray8": SL2_PIX_GRAY8, "rgb24": SL2_PIX_RGB24, "bgr24": SL2_PIX_BGR24, "uyvy": SL2_PIX_UYVY, "yuyv": SL2_PIX_YUYV}
+FORMATS = {"gray8": SL2_PIX_GRAY8, "rgb24": SL2_PIX_RGB24, "bgr24": SL2_PIX_BGR24, "uyvy": SL2_PIX_UYVY, "yuyv": SL2_PIX_YUYV,
+           "gray10": SL2_PIX_GRAY10, "gray12": SL2_PIX_GRAY12, "gray16": SL2_PIX_GRAY16,
+           "bayer_rggb8": SL2_PIX_BAYER_RGGB8, "bayer_grbg8": SL2_PIX_BAYER_GRBG8, "bayer_gbrg8": SL2_PIX_BAYER_GBRG8,
+           "bayer_bggr8": SL2_PIX_BAYER_BGGR8}
 FILTERS = {"linear": _lib.SL2_RESIZE_LINEAR, "area": _lib.SL2_RESIZE_AREA}
-BYTES_PER_PIXEL = {SL2_PIX_GRAY8: 1, SL2_PIX_RGB24: 3, SL2_PIX_BGR24: 3, SL2_PIX_UYVY: 2, SL2_PIX_YUYV: 2}
+BYTES_PER_PIXEL = {SL2_PIX_GRAY8: 1, SL2_PIX_RGB24: 3, SL2_PIX_BGR24: 3, SL2_PIX_UYVY: 2, SL2_PIX_YUYV: 2,
+                   SL2_PIX_GRAY10: 2, SL2_PIX_GRAY12: 2, SL2_PIX_GRAY16: 2,
+                   SL2_PIX_BAYER_RGGB8: 1, SL2_PIX_BAYER_GRBG8: 1, SL2_PIX_BAYER_GBRG8: 1, SL2_PIX_BAYER_BGGR8: 1}
 
 
 def _format(f):

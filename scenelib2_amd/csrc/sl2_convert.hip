@@ -6,6 +6,8 @@
 // head and tail where the row's address or length breaks the alignment -, reduces them to grey in LDS, forms the outputs from
 // LDS and stores four output bytes per lane.  Sequences of any source size and format share the launch: the grid is sized by
 // the OUTPUT rows, which are the same for all of them.
+// k_convert_area, k_raw_linear, k_raw_area: the SL2_RESIZE_AREA sequences and those of a deep grey or Bayer format, listed on the
+// device, a launch each where there are any.
 #include "sl2_common.hpp"
 #include "sl2_convert_dev.hpp"
 
@@ -23,6 +25,15 @@ constexpr int kConvLdsBytes = 4 * (kConvertMaxWidth + 16);
 
 // The device copy of a source carries its sequence's filter in its format word (the host copy and the C ABI never see it)
 constexpr int kConvAreaBit = 0x100;
+// ... and whether its format is a deep grey or Bayer one: k_raw_linear's or k_raw_area's sequence, by the filter
+constexpr int kConvRawBit = 0x200;
+constexpr int kConvFormatMask = 0xff;
+
+// Bayer: the grey of a listed row needs raw rows y - 1, y, y + 1, so the raw rows are staged first (as GRAY8 rows, in dynamic LDS
+// sized by the widest Bayer source of the launch) and the grey rows are formed from them, LDS to LDS.  At most kRawSlots raw rows
+// at once (sixteen consecutive grey rows and their halo) and kRawLdsBytes: four raw rows at the width cap, eighteen up to 880.
+constexpr int kRawSlots = 18;
+constexpr int kRawLdsBytes = 4 * (kConvertMaxWidth + 16);
 
 struct ConvArgs {
   const sl2_frame_source* src;   // [nseq]
@@ -39,6 +50,9 @@ template <> struct ConvFmt<SL2_PIX_RGB24> { static constexpr int kGroup = 16, kB
 template <> struct ConvFmt<SL2_PIX_BGR24> { static constexpr int kGroup = 16, kBytes = 48; };
 template <> struct ConvFmt<SL2_PIX_UYVY> { static constexpr int kGroup = 8, kBytes = 16; };
 template <> struct ConvFmt<SL2_PIX_YUYV> { static constexpr int kGroup = 8, kBytes = 16; };
+template <> struct ConvFmt<SL2_PIX_GRAY10> { static constexpr int kGroup = 8, kBytes = 16; };      // a 16-byte load is 8 pixels
+template <> struct ConvFmt<SL2_PIX_GRAY12> { static constexpr int kGroup = 8, kBytes = 16; };
+template <> struct ConvFmt<SL2_PIX_GRAY16> { static constexpr int kGroup = 8, kBytes = 16; };
 
 struct ConvShared {
   alignas(16) uint8_t grey[kConvLdsBytes];
@@ -54,9 +68,10 @@ struct ConvShared {
 
 __device__ __forceinline__ uint32_t conv_byte(const uint32_t* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 
-// Stage the listed source rows as grey bytes: slot k of sh.grey holds row sh.row[k] from byte sh.shift[k] on.
-template <int FMT>
-__device__ __forceinline__ void conv_stage(ConvShared& sh, const uint8_t* __restrict__ base, int pitch, int W, int wpad) {
+// Stage the listed source rows as grey bytes: slot k of grey holds row sh.row[k] from byte sh.shift[k] on.  (ROWS: ConvShared
+// with its own grey, or the RawRows of a Bayer sub-pass with the raw stage.)
+template <int FMT, typename ROWS>
+__device__ __forceinline__ void conv_stage(ROWS& sh, uint8_t* grey, const uint8_t* __restrict__ base, int pitch, int W, int wpad) {
   constexpr int G = ConvFmt<FMT>::kGroup, VB = ConvFmt<FMT>::kBytes;
   const int tid = threadIdx.x;
   const int nslots = sh.nslots;
@@ -70,10 +85,10 @@ __device__ __forceinline__ void conv_stage(ConvShared& sh, const uint8_t* __rest
       head = (int)(((0u - a) * 11u) & 15u); first = 3 * head;      // a + 3 head = 0 mod 16 (3 * 11 = 1 mod 16)
     } else {
       first = (int)((0u - a) & 15u);
-      head = (first - (FMT == SL2_PIX_UYVY ? 1 : 0) + 1) >> 1;     // pixels whose Y byte lies before `first`
+      head = (first - (FMT == SL2_PIX_UYVY ? 1 : 0) + 1) >> 1;     // pixels whose Y byte lies before `first` (deep grey: `first` is even)
     }
     if (head >= W) { head = W; groups = 0; }
-    else if (convert_is_422(FMT)) groups = row_bytes > first ? (row_bytes - first) / 16 : 0;
+    else if (convert_is_422(FMT) || convert_is_deep(FMT)) groups = row_bytes > first ? (row_bytes - first) / 16 : 0;
     else groups = (W - head) / G;
     sh.head[tid] = head; sh.first[tid] = first; sh.groups[tid] = groups; sh.shift[tid] = (G - head % G) % G;
   }
@@ -84,7 +99,7 @@ __device__ __forceinline__ void conv_stage(ConvShared& sh, const uint8_t* __rest
     const int k = idx / gmax, c = idx - k * gmax;
     if (c >= sh.groups[k]) continue;
     const uint8_t* rp = base + (size_t)sh.row[k] * (size_t)pitch + sh.first[k] + c * VB;
-    uint8_t* dst = sh.grey + k * wpad + sh.shift[k] + sh.head[k] + c * G;
+    uint8_t* dst = grey + k * wpad + sh.shift[k] + sh.head[k] + c * G;
     if (FMT == SL2_PIX_GRAY8) {
       *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(rp);
     } else if (FMT == SL2_PIX_UYVY || FMT == SL2_PIX_YUYV) {
@@ -95,6 +110,15 @@ __device__ __forceinline__ void conv_stage(ConvShared& sh, const uint8_t* __rest
       uint2 o;
       o.x = (t0 & 255u) | ((t0 >> 8) & 0xff00u) | ((t1 & 255u) << 16) | ((t1 << 8) & 0xff000000u);
       o.y = (t2 & 255u) | ((t2 >> 8) & 0xff00u) | ((t3 & 255u) << 16) | ((t3 << 8) & 0xff000000u);
+      *reinterpret_cast<uint2*>(dst) = o;
+    } else if (convert_is_deep(FMT)) {
+      const uint4 v = *reinterpret_cast<const uint4*>(rp);      // eight words of 16 bits
+      constexpr int N = FMT == SL2_PIX_GRAY10 ? 10 : FMT == SL2_PIX_GRAY12 ? 12 : 16;
+      uint2 o;
+      o.x = (uint32_t)convert_deep_grey(N, v.x) | ((uint32_t)convert_deep_grey(N, v.x >> 16) << 8) |
+            ((uint32_t)convert_deep_grey(N, v.y) << 16) | ((uint32_t)convert_deep_grey(N, v.y >> 16) << 24);
+      o.y = (uint32_t)convert_deep_grey(N, v.z) | ((uint32_t)convert_deep_grey(N, v.z >> 16) << 8) |
+            ((uint32_t)convert_deep_grey(N, v.w) << 16) | ((uint32_t)convert_deep_grey(N, v.w >> 16) << 24);
       *reinterpret_cast<uint2*>(dst) = o;
     } else {
       uint32_t w[12];
@@ -117,14 +141,113 @@ __device__ __forceinline__ void conv_stage(ConvShared& sh, const uint8_t* __rest
     const int p = j < 16 ? j : sh.head[k] + sh.groups[k] * G + (j - 16);
     if (j < 16 ? p >= sh.head[k] : p >= W) continue;
     const uint8_t* rp = base + (size_t)sh.row[k] * (size_t)pitch;
-    sh.grey[k * wpad + sh.shift[k] + p] = (uint8_t)convert_grey(FMT, rp, p);
+    grey[k * wpad + sh.shift[k] + p] = (uint8_t)convert_grey(FMT, rp, p);
   }
 }
 
-__global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvArgs A) {
-  __shared__ ConvShared sh;
+// The raw rows of a Bayer sub-pass, under the names conv_stage reads, and where each grey slot finds its three
+struct RawRows {
+  int row[kRawSlots], head[kRawSlots], first[kRawSlots], groups[kRawSlots], shift[kRawSlots];
+  int nb[kConvSlots][3];      // the raw slots of rows y - 1, y, y + 1 (reflected) of a grey slot
+  int nslots, k1;             // raw rows listed; the first grey slot this sub-pass does not form
+};
+
+// What the two raw kernels add to a workgroup's LDS: the dynamic part holds the raw stage (raw_lds bytes: 0 with no Bayer source)
+struct RawStage {
+  RawRows* rows;
+  uint8_t* bytes;
+  int raw_lds;
+};
+
+// Bayer: grey rows sh.row[0 .. nslots) of source columns xs .. xs + Wp - 1 into the slots of sh.grey, pixel xs at byte 0 of its
+// slot.  src0: the source's pixel (0,0).  In sub-passes of as many grey slots as their raw rows fit the raw stage (each raw row
+// once per sub-pass: a row two sub-passes share is read again, from L2): thread 0 lists the raw rows, conv_stage brings them in as
+// GRAY8 rows - columns xs - 1 .. xs + Wp where the image has them, every load inside the row -, and a lane forms four grey pixels
+// from the 3 x 6 raw bytes around them.  Reflection is in the indices: nothing outside the image is ever addressed.
+__device__ __forceinline__ void raw_stage_bayer(ConvShared& sh, const RawStage& rs, const uint8_t* __restrict__ src0, int pitch, int W, int H,
+                                                int xs, int Wp, int wpad, int fmt) {
   const int tid = threadIdx.x;
-  const int s = blockIdx.x / A.bands, band = blockIdx.x - s * A.bands;
+  RawRows& rr = *rs.rows;
+  const int rx0 = xs > 0 ? xs - 1 : 0, rx1 = xs + Wp < W ? xs + Wp : W - 1;      // the raw columns staged
+  const int Wr = rx1 - rx0 + 1, rpad = (Wr + 15 + 15) & ~15;
+  const int fit = rs.raw_lds / rpad;                                             // raw rows the stage holds: at least 4
+  const int rcap = fit < kRawSlots ? fit : kRawSlots;
+  const int nslots = sh.nslots;
+  const int nq = (Wp + 3) >> 2;
+  if (tid < nslots) sh.shift[tid] = 0;
+  for (int k0 = 0; k0 < nslots;) {
+    if (tid == 0) {
+      int n = 0, k = k0;
+      for (; k < nslots; ++k) {
+        const int y = sh.row[k];
+        const int ys[3] = {convert_reflect(y - 1, H), y, convert_reflect(y + 1, H)};
+        int m = n, at[3];
+        bool fits = true;
+        for (int j = 0; j < 3 && fits; ++j) {
+          int f = -1;
+          for (int i = m - 1; i >= 0 && i >= m - 4; --i) if (rr.row[i] == ys[j]) f = i;      // the listed rows only move forward
+          if (f < 0) { if (m == rcap) { fits = false; break; } rr.row[m] = ys[j]; f = m++; }
+          at[j] = f;
+        }
+        if (!fits) break;      // (never the sub-pass's first slot: three rows fit an empty stage)
+        n = m;
+        rr.nb[k][0] = at[0]; rr.nb[k][1] = at[1]; rr.nb[k][2] = at[2];
+      }
+      rr.nslots = n; rr.k1 = k;
+    }
+    __syncthreads();
+    const int k1 = rr.k1;
+    conv_stage<SL2_PIX_GRAY8>(rr, rs.bytes, src0 + rx0, pitch, Wr, rpad);
+    __syncthreads();
+    for (int idx = tid; idx < (k1 - k0) * nq; idx += kConvThreads) {
+      const int k = k0 + idx / nq, q = idx - (k - k0) * nq;
+      const int y = sh.row[k], x4 = xs + 4 * q;
+      int col[6];      // where raw columns x4 - 1 .. x4 + 4 sit in a staged row (the padding past the row's end: any staged column)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        int x = x4 - 1 + j;
+        x = x < xs + Wp ? convert_reflect(x, W) : convert_reflect(xs + Wp, W);
+        col[j] = x - rx0;
+      }
+      int p[3][6];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const int a = rr.nb[k][r];
+        const uint8_t* row = rs.bytes + a * rpad + rr.shift[a];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) p[r][j] = row[col[j]];
+      }
+      uint32_t packed = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int g = convert_bayer_grey(fmt, p[1][i + 1], p[1][i] + p[1][i + 2], p[0][i + 1] + p[2][i + 1],
+                                         p[0][i] + p[0][i + 2] + p[2][i] + p[2][i + 2], x4 + i, y);
+        packed |= (uint32_t)g << (8 * i);
+      }
+      *reinterpret_cast<uint32_t*>(sh.grey + k * wpad + 4 * q) = packed;      // wpad >= Wp + 15: the word stays in its slot
+    }
+    __syncthreads();      // the next sub-pass overwrites the raw stage
+    k0 = k1;
+  }
+}
+
+// The listed grey rows of a deep grey or Bayer source: what conv_stage is to the other formats
+__device__ __forceinline__ void raw_stage(ConvShared& sh, const RawStage& rs, const uint8_t* __restrict__ src0, int pitch, int W, int H, int xs,
+                                          int Wp, int wpad, int fmt) {
+  switch (fmt) {
+    case SL2_PIX_GRAY10: conv_stage<SL2_PIX_GRAY10>(sh, sh.grey, src0 + 2 * (size_t)xs, pitch, Wp, wpad); break;
+    case SL2_PIX_GRAY12: conv_stage<SL2_PIX_GRAY12>(sh, sh.grey, src0 + 2 * (size_t)xs, pitch, Wp, wpad); break;
+    case SL2_PIX_GRAY16: conv_stage<SL2_PIX_GRAY16>(sh, sh.grey, src0 + 2 * (size_t)xs, pitch, Wp, wpad); break;
+    default: raw_stage_bayer(sh, rs, src0, pitch, W, H, xs, Wp, wpad, fmt); break;
+  }
+}
+
+// The linear kernels' body.  RAW: k_raw_linear's (deep grey and Bayer sequences), else k_convert_frames' (the five 8-bit formats);
+// each leaves the other's sequences, and the area kernels', on the scalar branch after its record load.  (A and rs by value: by
+// reference k_convert_frames came out with two more scalars parked in vector lanes than it had as a kernel of its own.)
+template <bool RAW>
+__device__ __forceinline__ void conv_linear(ConvShared& sh, const ConvArgs A, int s, int band, const RawStage rs) {
+  const int tid = threadIdx.x;
   const uint32_t* __restrict__ ctab = A.taps + (size_t)s * A.tap_stride;
   const uint32_t* __restrict__ rtab = ctab + A.col_taps;
   const int band0 = band * kConvBandRows;
@@ -139,8 +262,9 @@ __global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvAr
   uint4 ct_first = make_uint4(0, 0, 0, 0);
   if (tr < rl) ct_first = *reinterpret_cast<const uint4*>(ctab + 4 * tq);
   const sl2_frame_source src = A.src[s];
-  const int W = src.width, H = src.height, pitch = src.pitch, fmt = src.format;
-  if (fmt & kConvAreaBit) return;                                              // k_convert_area's sequence (uniform: a scalar branch)
+  const int W = src.width, H = src.height, pitch = src.pitch, fmt = RAW ? src.format & kConvFormatMask : src.format;
+  // another kernel's sequence (uniform: a scalar branch): k_convert_area's, or one whose format is the other linear kernel's
+  if ((src.format & (kConvAreaBit | kConvRawBit)) != (RAW ? kConvRawBit : 0)) return;
   const uint8_t* __restrict__ base = A.raw + src.offset;
   uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
   const int wpad = (W + 15 + 15) & ~15;
@@ -166,12 +290,13 @@ __global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvAr
       sh.nslots = n;
     }
     __syncthreads();
-    switch (fmt) {
-      case SL2_PIX_GRAY8: conv_stage<SL2_PIX_GRAY8>(sh, base, pitch, W, wpad); break;
-      case SL2_PIX_RGB24: conv_stage<SL2_PIX_RGB24>(sh, base, pitch, W, wpad); break;
-      case SL2_PIX_BGR24: conv_stage<SL2_PIX_BGR24>(sh, base, pitch, W, wpad); break;
-      case SL2_PIX_UYVY: conv_stage<SL2_PIX_UYVY>(sh, base, pitch, W, wpad); break;
-      default: conv_stage<SL2_PIX_YUYV>(sh, base, pitch, W, wpad); break;
+    if (RAW) raw_stage(sh, rs, base, pitch, W, H, 0, W, wpad, fmt);
+    else switch (fmt) {
+      case SL2_PIX_GRAY8: conv_stage<SL2_PIX_GRAY8>(sh, sh.grey, base, pitch, W, wpad); break;
+      case SL2_PIX_RGB24: conv_stage<SL2_PIX_RGB24>(sh, sh.grey, base, pitch, W, wpad); break;
+      case SL2_PIX_BGR24: conv_stage<SL2_PIX_BGR24>(sh, sh.grey, base, pitch, W, wpad); break;
+      case SL2_PIX_UYVY: conv_stage<SL2_PIX_UYVY>(sh, sh.grey, base, pitch, W, wpad); break;
+      default: conv_stage<SL2_PIX_YUYV>(sh, sh.grey, base, pitch, W, wpad); break;
     }
     __syncthreads();
     if (tr < rl) {
@@ -209,6 +334,25 @@ __global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvAr
     }
     __syncthreads();      // the next pass overwrites the slots
   }
+}
+
+__global__ void __launch_bounds__(kConvThreads, 8) k_convert_frames(const ConvArgs A) {
+  __shared__ ConvShared sh;
+  const int s = blockIdx.x / A.bands;
+  conv_linear<false>(sh, A, s, blockIdx.x - s * A.bands, RawStage{nullptr, nullptr, 0});
+}
+
+// k_raw_linear: the same for the listed sequences, those of a deep grey or Bayer format under SL2_RESIZE_LINEAR.  Only the staging
+// differs (conv_stage's deep grey forms: a 16-byte load is 8 pixels; raw_stage_bayer).  Budget: ConvShared and RawRows, 17 KB of
+// static LDS, plus the raw stage (dynamic: eighteen raw rows of the widest listed Bayer source, 16.1 KB at most, none without a
+// Bayer source) and at most 80 registers: six workgroups a CU without a Bayer source, five with one of 640 columns, four from
+// 880 columns on.  At the width cap a pass forms two output rows from four grey rows, a sub-pass one or two of those from four raw rows.
+__global__ void __launch_bounds__(kConvThreads, 6) k_raw_linear(const ConvArgs A, const int32_t* __restrict__ list, int raw_lds) {
+  __shared__ ConvShared sh;
+  __shared__ RawRows rows;
+  extern __shared__ __attribute__((aligned(16))) uint8_t raw_dyn[];
+  const int li = blockIdx.x / A.bands;
+  conv_linear<true>(sh, A, list[li], blockIdx.x - li * A.bands, RawStage{&rows, raw_dyn, raw_lds});
 }
 
 // k_convert_area: SL2_RESIZE_AREA.  A workgroup owns one sequence of the area list and a band of kConvBandRows output rows, and
@@ -249,9 +393,9 @@ __device__ __forceinline__ void area_vertical(const uint8_t* __restrict__ grey, 
   }
 }
 
-template <typename ACC>
+template <typename ACC, bool RAW>
 __device__ __forceinline__ void area_band(ConvShared& sh, uint32_t* __restrict__ colsum, const AreaArgs& A, const sl2_frame_source& src, int fmt,
-                                          uint8_t* __restrict__ out, int band0, int band_end) {
+                                          uint8_t* __restrict__ out, int band0, int band_end, const RawStage& rs) {
   const int tid = threadIdx.x;
   const int W = src.width, H = src.height, pitch = src.pitch;
   const int bpp = convert_bpp(fmt);
@@ -277,12 +421,13 @@ __device__ __forceinline__ void area_band(ConvShared& sh, uint32_t* __restrict__
       if (tid < nrows) sh.row[tid] = c0 + tid;
       if (tid == 0) sh.nslots = nrows;
       __syncthreads();
-      switch (fmt) {
-        case SL2_PIX_GRAY8: conv_stage<SL2_PIX_GRAY8>(sh, base, pitch, Wp, wpad); break;
-        case SL2_PIX_RGB24: conv_stage<SL2_PIX_RGB24>(sh, base, pitch, Wp, wpad); break;
-        case SL2_PIX_BGR24: conv_stage<SL2_PIX_BGR24>(sh, base, pitch, Wp, wpad); break;
-        case SL2_PIX_UYVY: conv_stage<SL2_PIX_UYVY>(sh, base, pitch, Wp, wpad); break;
-        default: conv_stage<SL2_PIX_YUYV>(sh, base, pitch, Wp, wpad); break;
+      if (RAW) raw_stage(sh, rs, A.raw + src.offset, pitch, W, H, xs, Wp, wpad, fmt);
+      else switch (fmt) {
+        case SL2_PIX_GRAY8: conv_stage<SL2_PIX_GRAY8>(sh, sh.grey, base, pitch, Wp, wpad); break;
+        case SL2_PIX_RGB24: conv_stage<SL2_PIX_RGB24>(sh, sh.grey, base, pitch, Wp, wpad); break;
+        case SL2_PIX_BGR24: conv_stage<SL2_PIX_BGR24>(sh, sh.grey, base, pitch, Wp, wpad); break;
+        case SL2_PIX_UYVY: conv_stage<SL2_PIX_UYVY>(sh, sh.grey, base, pitch, Wp, wpad); break;
+        default: conv_stage<SL2_PIX_YUYV>(sh, sh.grey, base, pitch, Wp, wpad); break;
       }
       __syncthreads();
       while (cur < band_end) {
@@ -345,13 +490,36 @@ __global__ void __launch_bounds__(kConvThreads, 6) k_convert_area(const AreaArgs
   const int li = blockIdx.x / A.bands, band = blockIdx.x - li * A.bands;
   const int s = A.list[li];
   const sl2_frame_source src = A.src[s];
-  if (!(src.format & kConvAreaBit) || src.width < A.out_w || src.height < A.out_h) return;      // never listed (the host refuses such sources)
+  // never listed (the host refuses such sources, and lists those of a deep grey or Bayer format for k_raw_area)
+  if ((src.format & (kConvAreaBit | kConvRawBit)) != kConvAreaBit || src.width < A.out_w || src.height < A.out_h) return;
   const int fmt = src.format & (kConvAreaBit - 1);
   uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
   const int band0 = band * kConvBandRows;
   const int band_end = band0 + kConvBandRows < A.out_h ? band0 + kConvBandRows : A.out_h;
-  if (convert_area_wide(src.width, src.height)) area_band<uint64_t>(sh, area_colsum, A, src, fmt, out, band0, band_end);
-  else area_band<uint32_t>(sh, area_colsum, A, src, fmt, out, band0, band_end);
+  const RawStage none{nullptr, nullptr, 0};
+  if (convert_area_wide(src.width, src.height)) area_band<uint64_t, false>(sh, area_colsum, A, src, fmt, out, band0, band_end, none);
+  else area_band<uint32_t, false>(sh, area_colsum, A, src, fmt, out, band0, band_end, none);
+}
+
+// k_raw_area: the same for the listed sequences, those of a deep grey or Bayer format under SL2_RESIZE_AREA: area_band over
+// raw_stage.  A Bayer band stages raw rows y_first - 1 .. y_last + 1 (reflected); an output wider than 1024 stages, per panel, the
+// raw columns either side of the panel's own.  Dynamic LDS: colsum (colsum_bytes, a multiple of 16), then the raw stage.  At
+// most 80 registers; with a 1280-column Bayer source 16.5 + 0.6 + 5 + 16.1 KB: four workgroups a CU, three at the width cap.
+__global__ void __launch_bounds__(kConvThreads, 6) k_raw_area(const AreaArgs A, int colsum_bytes, int raw_lds) {
+  __shared__ ConvShared sh;
+  __shared__ RawRows rows;
+  extern __shared__ __attribute__((aligned(16))) uint32_t raw_area_dyn[];
+  const int li = blockIdx.x / A.bands, band = blockIdx.x - li * A.bands;
+  const int s = A.list[li];
+  const sl2_frame_source src = A.src[s];
+  if ((src.format & (kConvAreaBit | kConvRawBit)) != (kConvAreaBit | kConvRawBit) || src.width < A.out_w || src.height < A.out_h) return;
+  const int fmt = src.format & kConvFormatMask;
+  uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
+  const int band0 = band * kConvBandRows;
+  const int band_end = band0 + kConvBandRows < A.out_h ? band0 + kConvBandRows : A.out_h;
+  const RawStage rs{&rows, reinterpret_cast<uint8_t*>(raw_area_dyn) + colsum_bytes, raw_lds};
+  if (convert_area_wide(src.width, src.height)) area_band<uint64_t, true>(sh, raw_area_dyn, A, src, fmt, out, band0, band_end, rs);
+  else area_band<uint32_t, true>(sh, raw_area_dyn, A, src, fmt, out, band0, band_end, rs);
 }
 
 static std::string seq_text(int seq, const char* what) {
@@ -373,8 +541,11 @@ struct sl2_converter {
   std::vector<uint8_t> have;
   std::vector<int32_t> filter;           // SL2_RESIZE_* of every sequence
   std::vector<int32_t> area;             // the sequences with a source and SL2_RESIZE_AREA: k_convert_area's list
-  int32_t* d_area = nullptr;             // [nseq]
+  std::vector<int32_t> raw_linear, raw_area;      // the sequences of a deep grey or Bayer format, by filter: k_raw_linear's and k_raw_area's lists
+  int32_t* d_area = nullptr;             // [nseq]: the three lists, one after the other (they share no sequence)
   size_t area_lds = 0;                   // k_convert_area's dynamic LDS: a word per source column of the widest listed source
+  size_t raw_area_colsum = 0;            // the same for k_raw_area ...
+  int raw_linear_stage = 0, raw_area_stage = 0;      // ... and the raw stage of the two raw kernels: bytes, 0 with no Bayer source listed
   std::vector<uint32_t> taps;            // host copy of one sequence's table while it is built
   sl2_frame_source* d_src = nullptr;
   uint32_t* d_taps = nullptr;
@@ -438,14 +609,34 @@ static int converter_upload(sl2_converter* c, int seq0, int nseq) {
     if (first < 0) first = s;
     dev.push_back(c->src[s]);
     if (c->filter[s] == SL2_RESIZE_AREA) dev.back().format |= kConvAreaBit;
+    if (convert_is_raw(c->src[s].format)) dev.back().format |= kConvRawBit;
   }
   if (first >= 0) SL2_HIP(hipMemcpy(c->d_src + first, dev.data(), dev.size() * sizeof(sl2_frame_source), hipMemcpyHostToDevice));
-  c->area.clear();
-  int widest = 0;
-  for (int s = 0; s < c->nseq; ++s)
-    if (c->have[s] && c->filter[s] == SL2_RESIZE_AREA) { c->area.push_back(s); if (c->src[s].width > widest) widest = c->src[s].width; }
+  c->area.clear(); c->raw_linear.clear(); c->raw_area.clear();
+  int widest = 0, raw_widest = 0;
+  c->raw_linear_stage = c->raw_area_stage = 0;
+  for (int s = 0; s < c->nseq; ++s) {
+    if (!c->have[s]) continue;
+    const sl2_frame_source& src = c->src[s];
+    const bool area = c->filter[s] == SL2_RESIZE_AREA;
+    if (!convert_is_raw(src.format)) {
+      if (area) { c->area.push_back(s); if (src.width > widest) widest = src.width; }
+      continue;
+    }
+    (area ? c->raw_area : c->raw_linear).push_back(s);
+    if (area && src.width > raw_widest) raw_widest = src.width;
+    if (convert_is_bayer(src.format)) {
+      const int want = kRawSlots * ((src.width + 15 + 15) & ~15);
+      int& stage = area ? c->raw_area_stage : c->raw_linear_stage;
+      stage = std::max(stage, std::min(want, kRawLdsBytes));
+    }
+  }
   c->area_lds = sizeof(uint32_t) * (size_t)round_up(widest, 4);
-  if (!c->area.empty()) SL2_HIP(hipMemcpy(c->d_area, c->area.data(), c->area.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->raw_area_colsum = sizeof(uint32_t) * (size_t)round_up(raw_widest, 4);
+  std::vector<int32_t> lists(c->area);
+  lists.insert(lists.end(), c->raw_linear.begin(), c->raw_linear.end());
+  lists.insert(lists.end(), c->raw_area.begin(), c->raw_area.end());
+  if (!lists.empty()) SL2_HIP(hipMemcpy(c->d_area, lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   return SL2_OK;
 }
 
@@ -512,6 +703,7 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
   for (int s = 0; s < c->nseq; ++s) {
     if (!c->have[s]) { set_error("sl2_convert_frames: " + seq_text(s, "its source was never set")); return SL2_ERR_INVALID; }
     const char* why = convert_source_fault(c->src[s], raw_bytes, true);
+    if (!why && raw_on_device && convert_is_deep(c->src[s].format) && ((uintptr_t)raw & 1)) why = "odd address of the raw buffer with a 16-bit format";
     if (why) { set_error("sl2_convert_frames: " + seq_text(s, why)); return SL2_ERR_INVALID; }
   }
   SL2_HIP(hipSetDevice(c->device));
@@ -531,12 +723,21 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
   A.src = c->d_src; A.taps = c->d_taps; A.raw = d_raw; A.out = d_frames; A.seq_stride = seq_stride;
   A.out_w = c->out_w; A.out_h = c->out_h; A.col_taps = c->col_taps; A.tap_stride = c->tap_stride;
   A.bands = (c->out_h + kConvBandRows - 1) / kConvBandRows;
-  if ((int)c->area.size() < c->nseq) hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
-  if (!c->area.empty()) {
-    AreaArgs B;
-    B.src = c->d_src; B.list = c->d_area; B.raw = d_raw; B.out = d_frames; B.seq_stride = seq_stride;
-    B.out_w = c->out_w; B.out_h = c->out_h; B.bands = A.bands;
+  // a kernel per (format family, filter) that has a sequence: one launch for the reference's webcam, four at most
+  const int listed = (int)(c->area.size() + c->raw_linear.size() + c->raw_area.size());
+  if (listed < c->nseq) hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
+  AreaArgs B;
+  B.src = c->d_src; B.list = c->d_area; B.raw = d_raw; B.out = d_frames; B.seq_stride = seq_stride;
+  B.out_w = c->out_w; B.out_h = c->out_h; B.bands = A.bands;
+  if (!c->area.empty())
     hipLaunchKernelGGL(k_convert_area, dim3((unsigned)(B.bands * (int)c->area.size())), dim3(kConvThreads), c->area_lds, st, B);
+  if (!c->raw_linear.empty())
+    hipLaunchKernelGGL(k_raw_linear, dim3((unsigned)(A.bands * (int)c->raw_linear.size())), dim3(kConvThreads), (size_t)c->raw_linear_stage, st,
+                       A, (const int32_t*)(c->d_area + c->area.size()), c->raw_linear_stage);
+  if (!c->raw_area.empty()) {
+    B.list = c->d_area + c->area.size() + c->raw_linear.size();
+    hipLaunchKernelGGL(k_raw_area, dim3((unsigned)(B.bands * (int)c->raw_area.size())), dim3(kConvThreads),
+                       c->raw_area_colsum + (size_t)c->raw_area_stage, st, B, (int)c->raw_area_colsum, c->raw_area_stage);
   }
   SL2_HIP(hipGetLastError());
   SL2_HIP(hipEventRecord(c->done, st));

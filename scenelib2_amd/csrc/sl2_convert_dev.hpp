@@ -16,24 +16,66 @@ namespace sl2 {
 constexpr int kConvertMaxWidth = 4096;     // source pixels per row: what the kernel's LDS staging holds (sl2_convert.hip)
 constexpr int kConvertMaxHeight = 16384;   // source rows: what a packed tap's index field holds
 constexpr int kConvertMaxOut = 4096;       // output pixels per axis
-constexpr int kConvertFormats = 5;
+constexpr int kConvertFormats = 5;          // the contiguous 8-bit formats of the reference's webcam: ids 0 .. 4
+
+// Machine-vision sources (scenelib2_amd.h, "raw camera frames"; parity with OpenCV unpinned: this text is the definition).
+// Deep grey, N = 10, 12, 16: 16-bit little-endian words, g = (v & (2^N - 1)) >> (N - 8); offset and pitch even.
+// Bayer: one byte a pixel, the name is the 2 x 2 tile at the source's pixel (0,0); see convert_bayer_grey.
+SL2_HD bool convert_is_deep(int format) { return format >= SL2_PIX_GRAY10 && format <= SL2_PIX_GRAY16; }
+SL2_HD bool convert_is_bayer(int format) { return format >= SL2_PIX_BAYER_RGGB8 && format <= SL2_PIX_BAYER_BGGR8; }
+SL2_HD bool convert_is_raw(int format) { return convert_is_deep(format) || convert_is_bayer(format); }
+SL2_HD bool convert_format_known(int format) { return (format >= 0 && format < kConvertFormats) || convert_is_raw(format); }
+SL2_HD int convert_deep_bits(int format) { return format == SL2_PIX_GRAY10 ? 10 : format == SL2_PIX_GRAY12 ? 12 : 16; }
 
 // bytes per source pixel
-SL2_HD int convert_bpp(int format) { return format == SL2_PIX_GRAY8 ? 1 : (format == SL2_PIX_RGB24 || format == SL2_PIX_BGR24) ? 3 : 2; }
+SL2_HD int convert_bpp(int format) {
+  return format == SL2_PIX_GRAY8 || convert_is_bayer(format) ? 1 : (format == SL2_PIX_RGB24 || format == SL2_PIX_BGR24) ? 3 : 2;
+}
 SL2_HD bool convert_is_422(int format) { return format == SL2_PIX_UYVY || format == SL2_PIX_YUYV; }
 
 // cvtColor's RGB -> grey, 14-bit coefficients (they sum to 16384)
 SL2_HD int convert_rgb_grey(int r, int g, int b) { return (4899 * r + 9617 * g + 1868 * b + 8192) >> 14; }
 
-// Grey value of pixel x of a source row
+// Deep grey: the top eight of the low `bits` bits of a 16-bit word
+SL2_HD int convert_deep_grey(int bits, uint32_t v) { return (int)((v & ((1u << bits) - 1u)) >> (bits - 8)); }
+
+// Grey value of pixel x of a source row (every format whose grey needs one row: all but Bayer)
 SL2_HD int convert_grey(int format, const uint8_t* row, int x) {
   switch (format) {
     case SL2_PIX_RGB24: return convert_rgb_grey(row[3 * x], row[3 * x + 1], row[3 * x + 2]);
     case SL2_PIX_BGR24: return convert_rgb_grey(row[3 * x + 2], row[3 * x + 1], row[3 * x]);
     case SL2_PIX_UYVY: return row[2 * x + 1];
     case SL2_PIX_YUYV: return row[2 * x];
+    case SL2_PIX_GRAY10: case SL2_PIX_GRAY12: case SL2_PIX_GRAY16:
+      return convert_deep_grey(convert_deep_bits(format), (uint32_t)row[2 * x] | ((uint32_t)row[2 * x + 1] << 8));
     default: return row[x];
   }
+}
+
+// Bayer: index i of an axis of S >= 2 pixels, reflected about the edge pixel (-1 -> 1, S -> S - 2): the colour phase survives
+SL2_HD int convert_reflect(int i, int S) { return i < 0 ? -i : i >= S ? 2 * (S - 1) - i : i; }
+
+// Bayer grey of site (x, y) from its value c, h2 = left + right, v2 = up + down and d4 = the four diagonals: bilinear demosaic in
+// exact quarters (R4, G4, B4), then the weights of convert_rgb_grey with ONE rounding; at most 16384 * 1020 + 32768.  The colour
+// of a site is letter (y & 1) * 2 + (x & 1) of the format's name: red sits at parity (format & 1, format >> 1 & 1).
+// A constant mosaic maps to itself, and a mosaic of a flat colour (R, G, B) to convert_rgb_grey(R, G, B):
+// (4 X + 32768) >> 16 == (X + 8192) >> 14.
+SL2_HD int convert_bayer_grey(int format, int c, int h2, int v2, int d4, int x, int y) {
+  const int px = (x ^ format) & 1, py = (y ^ (format >> 1)) & 1;      // 0: red's column / row
+  int r4, g4, b4;
+  if (px == py) { g4 = h2 + v2; r4 = px ? d4 : 4 * c; b4 = px ? 4 * c : d4; }      // a red or a blue site
+  else { g4 = 4 * c; r4 = py ? 2 * v2 : 2 * h2; b4 = py ? 2 * h2 : 2 * v2; }      // green: red to its left and right in red's rows
+  return (4899 * r4 + 9617 * g4 + 1868 * b4 + 32768) >> 16;
+}
+
+// Grey value of pixel (x, y) of a W x H source whose pixel (0,0) is at base: any format
+SL2_HD int convert_grey_at(int format, const uint8_t* base, int pitch, int W, int H, int x, int y) {
+  if (!convert_is_bayer(format)) return convert_grey(format, base + (size_t)y * (size_t)pitch, x);
+  const int xl = convert_reflect(x - 1, W), xr = convert_reflect(x + 1, W);
+  const uint8_t* ru = base + (size_t)convert_reflect(y - 1, H) * (size_t)pitch;
+  const uint8_t* rc = base + (size_t)y * (size_t)pitch;
+  const uint8_t* rd = base + (size_t)convert_reflect(y + 1, H) * (size_t)pitch;
+  return convert_bayer_grey(format, rc[x], rc[xl] + rc[xr], ru[x] + rd[x], ru[xl] + ru[xr] + rd[xl] + rd[xr], x, y);
 }
 
 // The two taps of output position d along an axis of S source and D output pixels: source indices i and min(i + 1, S - 1)
@@ -77,11 +119,13 @@ SL2_HD uint64_t convert_source_end(const sl2_frame_source& s) {
 
 // Why a source cannot be converted (nullptr: it can).  check_reach: also that it ends inside the raw_bytes of the raw buffer.
 inline const char* convert_source_fault(const sl2_frame_source& s, uint64_t raw_bytes, bool check_reach) {
-  if (s.format < 0 || s.format >= kConvertFormats) return "unknown pixel format";
+  if (!convert_format_known(s.format)) return "unknown pixel format";
   if (s.width < 1 || s.height < 1) return "width or height below 1";
   if (s.width > kConvertMaxWidth) return "width over 4096";
   if (s.height > kConvertMaxHeight) return "height over 16384";
   if (convert_is_422(s.format) && (s.width & 1)) return "odd width with a 4:2:2 format";
+  if (convert_is_bayer(s.format) && (s.width < 2 || s.height < 2)) return "a Bayer source under 2 pixels on an axis";
+  if (convert_is_deep(s.format) && ((s.offset | (uint64_t)(uint32_t)s.pitch) & 1)) return "odd offset or pitch with a 16-bit format";
   if (s.pitch < 0 || (uint64_t)s.pitch < convert_row_bytes(s)) return "pitch below the bytes of a row";
   if (check_reach && (s.offset > raw_bytes || convert_source_end(s) - s.offset > raw_bytes - s.offset)) return "source reaches past the raw buffer";
   return nullptr;
@@ -94,10 +138,8 @@ SL2_HD uint8_t convert_pixel(int format, const uint8_t* base, int pitch, int wid
   convert_unpack_tap(rtap, &y0, &b0, &b1);
   const int x1 = x0 + 1 < width ? x0 + 1 : width - 1;
   const int y1 = y0 + 1 < height ? y0 + 1 : height - 1;
-  const uint8_t* r0 = base + (size_t)y0 * (size_t)pitch;
-  const uint8_t* r1 = base + (size_t)y1 * (size_t)pitch;
-  const int h0 = convert_hpass(convert_grey(format, r0, x0), convert_grey(format, r0, x1), a0, a1);
-  const int h1 = convert_hpass(convert_grey(format, r1, x0), convert_grey(format, r1, x1), a0, a1);
+  const int h0 = convert_hpass(convert_grey_at(format, base, pitch, width, height, x0, y0), convert_grey_at(format, base, pitch, width, height, x1, y0), a0, a1);
+  const int h1 = convert_hpass(convert_grey_at(format, base, pitch, width, height, x0, y1), convert_grey_at(format, base, pitch, width, height, x1, y1), a0, a1);
   return convert_vpass(h0, h1, b0, b1);
 }
 
@@ -178,8 +220,7 @@ inline void convert_frame_host_area_body(const sl2_frame_source& s, const uint8_
     for (int x = 0; x < out_w; ++x) acc[x] = 0;
     const int y0 = convert_area_first(s.height, out_h, dy), y1 = convert_area_last(s.height, out_h, dy);
     for (int y = y0; y <= y1; ++y) {
-      const uint8_t* row = base + (size_t)y * (size_t)s.pitch;
-      for (int x = 0; x < s.width; ++x) grey[x] = (uint8_t)convert_grey(s.format, row, x);
+      for (int x = 0; x < s.width; ++x) grey[x] = (uint8_t)convert_grey_at(s.format, base, s.pitch, s.width, s.height, x, y);
       const uint32_t wy = (uint32_t)convert_area_weight(s.height, out_h, dy, y);
       for (int x = 0; x < out_w; ++x) acc[x] += (uint64_t)(wy * convert_area_hsum<uint32_t>(grey, 0, cols[x], out_w));      // wy h < 2^32
     }

@@ -834,7 +834,7 @@ class MonoSLAM:
 
     def SetFrameSource(self, width, height, pitch, format):
         """What the camera delivers (UsbCamGrabber, usbcamgrabber.cpp:75-113): its size, row pitch in bytes and pixel format
-        (convert.SL2_PIX_* or "uyvy", "rgb24" ...).  GoOneStepRaw converts such frames to the engine's grey image on the
+        (convert.SL2_PIX_* or a name of convert.FORMATS: "uyvy", "rgb24", "gray12", "bayer_rggb8" ...).  GoOneStepRaw converts such frames to the engine's grey image on the
         device.  The converter and the device frame are created on the first call."""
         from . import convert
         if self._converter is None:

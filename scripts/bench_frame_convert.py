@@ -17,6 +17,13 @@ output.  Rates are those bytes over the time.  The result is checked against sl2
 whole source.  --linear-json / --linear-parent-json name the results of two --filter linear runs of the same session, this
 commit's library and its parent's (SL2_LIB_PATH): they are recorded beside the area runs, with whether every convert_ms of this
 commit lies inside the parent's spread_ms.
+
+--filter raw times k_raw_linear and k_raw_area (the machine-vision formats) instead: 640 x 480 BAYER_RGGB8 under LINEAR, 1280 x 960
+BAYER_RGGB8 and 1280 x 960 GRAY12 under AREA, and writes profiles/frame_convert_raw_bench.json.  Beside the flat copy, every source
+is timed against a GRAY8 source of the same size under the same filter through the existing kernel, in the same run: it moves the
+same bytes for Bayer and half the bytes for deep grey, so the difference is the demosaic or the narrowing itself.
+--ab-out FILE with --linear-json / --linear-parent-json / --area-json / --area-parent-json (four runs of one session, this commit's
+library and its parent's under both filters) writes only the comparison of the existing kernels to FILE and times nothing.
 """
 import argparse
 import json
@@ -35,6 +42,8 @@ SOURCES = [("640x480 UYVY", 640, 480, "uyvy"), ("640x480 RGB24", 640, 480, "rgb2
            ("320x240 GRAY8 (native copy)", 320, 240, "gray8")]
 AREA_SOURCES = [("640x480 UYVY", 640, 480, "uyvy"), ("1280x960 GRAY8", 1280, 960, "gray8"), ("1920x1080 YUYV", 1920, 1080, "yuyv"),
                 ("960x720 RGB24", 960, 720, "rgb24")]
+RAW_SOURCES = [("640x480 BAYER_RGGB8", 640, 480, "bayer_rggb8", "linear"), ("1280x960 BAYER_RGGB8", 1280, 960, "bayer_rggb8", "area"),
+               ("1280x960 GRAY12", 1280, 960, "gray12", "area")]
 STEP_MS = 1.45          # the headline step (README) the conversion sits in front of
 
 
@@ -46,12 +55,28 @@ def commit():
         return open(p).read().strip() if os.path.exists(p) else "unknown"
 
 
-def rows_read(src_h, out_h):
-    """Source rows that some row tap names (the definition of include/scenelib2_amd.h, in float32 like it)."""
+def rows_read(src_h, out_h, halo=False):
+    """Source rows that some row tap names (the definition of include/scenelib2_amd.h, in float32 like it); halo: and the rows
+    above and below them, which a Bayer grey row needs."""
     d = np.arange(out_h, dtype=np.float64)
     f = ((d + 0.5) * (np.float64(src_h) / np.float64(out_h)) - 0.5).astype(np.float32)
     i = np.clip(np.floor(f).astype(np.int64), 0, src_h - 1)
-    return int(np.unique(np.concatenate([i, np.minimum(i + 1, src_h - 1)])).size)
+    rows = np.unique(np.concatenate([i, np.minimum(i + 1, src_h - 1)]))
+    if halo:
+        rows = np.unique(np.clip(np.concatenate([rows - 1, rows, rows + 1]), 0, src_h - 1))
+    return int(rows.size)
+
+
+def unchanged(this_json, parent_json):
+    """The runs of this commit's library beside those of its parent's: is every convert_ms inside the parent's spread?"""
+    this, parent = json.load(open(this_json)), json.load(open(parent_json))
+    pick = lambda r: dict(source=r["source"], convert_ms=r["convert_ms"], spread_ms=r["spread_ms"]["convert"],
+                          convert_over_memcpy_same_traffic=r["convert_over_memcpy_same_traffic"])
+    rows = [dict(this_commit=pick(a), parent=pick(b), inside_parent_spread=b["spread_ms"]["convert"][0] <= a["convert_ms"] <= b["spread_ms"]["convert"][1],
+                 at_most_parent_slowest=a["convert_ms"] <= b["spread_ms"]["convert"][1])
+            for a, b in zip(this["runs"], parent["runs"])]
+    return dict(parent_library=parent.get("library"), runs=rows, all_inside=all(r["inside_parent_spread"] for r in rows),
+                none_slower=all(r["at_most_parent_slowest"] for r in rows))
 
 
 def main():
@@ -59,14 +84,25 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--filter", choices=("linear", "area"), default="linear")
+    ap.add_argument("--filter", choices=("linear", "area", "raw"), default="linear")
     ap.add_argument("--out", default=None)
     ap.add_argument("--linear-json", default=None)
     ap.add_argument("--linear-parent-json", default=None)
+    ap.add_argument("--area-json", default=None)
+    ap.add_argument("--area-parent-json", default=None)
+    ap.add_argument("--ab-out", default=None)
     args = ap.parse_args()
-    area = args.filter == "area"
+    if args.ab_out:
+        res = dict(commit=commit(), linear_unchanged=unchanged(args.linear_json, args.linear_parent_json),
+                   area_unchanged=unchanged(args.area_json, args.area_parent_json))
+        with open(args.ab_out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res))
+        return
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "frame_convert_area_bench.json" if area else "frame_convert_bench.json")
+        args.out = os.path.join(ROOT, "profiles", {"linear": "frame_convert_bench.json", "area": "frame_convert_area_bench.json",
+                                                   "raw": "frame_convert_raw_bench.json"}[args.filter])
     if _lib.device_count() < 1:
         raise SystemExit("bench_frame_convert: no HIP device (there is no CPU fallback)")
     B, ow, oh = args.batch, 320, 240
@@ -88,7 +124,13 @@ def main():
 
     med = lambda v: float(np.median(np.asarray(v)))
     runs = []
-    for name, w, h, fmt in (AREA_SOURCES if area else SOURCES):
+    todo = []
+    for src in {"linear": SOURCES, "area": AREA_SOURCES, "raw": RAW_SOURCES}[args.filter]:
+        todo.append(src if len(src) == 5 else src + (args.filter,))
+        if args.filter == "raw":          # the yardstick through the existing kernel: GRAY8 of the same size under the same filter
+            todo.append(("%dx%d GRAY8 (%s)" % (src[1], src[2], src[4]), src[1], src[2], "gray8", src[4]))
+    for name, w, h, fmt, flt in todo:
+        area = flt == "area"
         bpp = convert.BYTES_PER_PIXEL[convert.FORMATS[fmt]]
         frame = w * h * bpp
         g = torch.Generator(device="cuda")
@@ -105,7 +147,7 @@ def main():
             want = convert.convert_frame_host(dict(width=w, height=h, format=fmt), raw[s * frame:(s + 1) * frame].cpu().numpy(), ow, oh,
                                               **(dict(filter="area") if area else {}))
             assert np.array_equal(out[s * ow * oh:(s + 1) * ow * oh].cpu().numpy().reshape(oh, ow), want), (name, s)
-        src_rows = h if area else rows_read(h, oh)          # the area filter reads every source byte
+        src_rows = h if area else rows_read(h, oh, halo=fmt.startswith("bayer"))          # the area filter reads every source byte
         read = B * src_rows * w * bpp
         touched = read + B * ow * oh
         conv_ms = timed(go)
@@ -119,7 +161,7 @@ def main():
             return fn
 
         full_ms, half_ms = timed(d2d(touched)), timed(d2d(touched // 2))
-        runs.append(dict(source=name, raw_bytes=B * frame, bytes_read=read, bytes_written=B * ow * oh, bytes_touched=touched,
+        runs.append(dict(source=name, filter=flt, raw_bytes=B * frame, bytes_read=read, bytes_written=B * ow * oh, bytes_touched=touched,
                          source_rows_read=src_rows, convert_ms=med(conv_ms), convert_TBps=touched / med(conv_ms) / 1e9,
                          memcpy_touched_ms=med(full_ms), memcpy_same_traffic_ms=med(half_ms),
                          memcpy_same_traffic_TBps=touched / med(half_ms) / 1e9,
@@ -135,15 +177,13 @@ def main():
                headline_step_ms=STEP_MS, runs=runs,
                note="bytes_touched below 256 MiB (the native copy) can live in the Infinity Cache between repeats: for the "
                     "conversion and for the copy alike")
+    if args.filter == "raw":          # each new source over the GRAY8 source timed right after it
+        res["over_gray8"] = [dict(source=a["source"], filter=a["filter"], convert_ms=a["convert_ms"], gray8_ms=b["convert_ms"],
+                                  convert_over_gray8=a["convert_ms"] / b["convert_ms"],
+                                  convert_over_memcpy_same_traffic=a["convert_over_memcpy_same_traffic"])
+                             for a, b in zip(runs[0::2], runs[1::2])]
     if args.linear_json and args.linear_parent_json:
-        this, parent = json.load(open(args.linear_json)), json.load(open(args.linear_parent_json))
-        pick = lambda r: dict(source=r["source"], convert_ms=r["convert_ms"], spread_ms=r["spread_ms"]["convert"],
-                              convert_over_memcpy_same_traffic=r["convert_over_memcpy_same_traffic"])
-        rows = [dict(this_commit=pick(a), parent=pick(b), inside_parent_spread=b["spread_ms"]["convert"][0] <= a["convert_ms"] <= b["spread_ms"]["convert"][1],
-                     at_most_parent_slowest=a["convert_ms"] <= b["spread_ms"]["convert"][1])
-                for a, b in zip(this["runs"], parent["runs"])]
-        res["linear_unchanged"] = dict(parent_library=parent.get("library"), runs=rows, all_inside=all(r["inside_parent_spread"] for r in rows),
-                                       none_slower=all(r["at_most_parent_slowest"] for r in rows))
+        res["linear_unchanged"] = unchanged(args.linear_json, args.linear_parent_json)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
