@@ -1,6 +1,6 @@
 // The diagonal-block routine of the blocked Cholesky (Eigen::LLT + matrixL().inverse() of kalman.cpp:104-107 for one 32x32
 // block): d_column<0>(...) turns [A; I] into [L; L^-T] by column Cholesky in the registers of ONE wavefront, a row per lane
-// (lanes 0..31: the diagonal tile, lanes 32..63: the identity).  Shared by k_chol_left (sl2_ekf_update.hip) and by the fused
+// (lanes 0..31: the diagonal tile, lanes 32..63: the identity).  Shared by k_chol_left (sl2_update_chol.hip) and by the fused
 // small-map kernel k_small_back (sl2_small.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -300,7 +300,20 @@ int launch_search_score(sl2_engine* e);
 int launch_small_front(sl2_engine* e, int n);                 // predict + feature prediction + selection in one launch
 int launch_small_back(sl2_engine* e, int save_trajectory, int panel_w);   // (GroupPlan::panel_w) scoring + EKF update + normalise / delete / symmetrise in one launch
 int launch_update(sl2_engine* e);
+// the phases launch_update walks, a translation unit each (sl2_update_build.hip, sl2_update_chol.hip, sl2_update_fwdsub.hip,
+// sl2_update_syrk.hip): the plan's form of the phase, or kNoProductForm where the unit holds no kernel for it
+constexpr int kNoProductForm = -1;
+int launch_build(sl2_engine* e, const UpdatePlan& p);
+int launch_factor(sl2_engine* e, const UpdatePlan& p);
+int launch_substitute(sl2_engine* e, const UpdatePlan& p);
+int launch_product(sl2_engine* e);
+int launch_panel_solve(sl2_engine* e, int pb, int p0, int c0, int ntile, int nb);   // sl2_update_fwdsub.hip, for the panel-wise Cholesky: X = S[below][panel] L_dd^-T
 int launch_syrk_on(sl2_engine* e, const double* Vt, double* P);
+UpdateShape update_shape(const sl2_engine* e);   // sl2_ekf_update.hip: what make_update_plan takes of an engine
+// sl2_update_testing.hip (the TEST library only): the superseded forms
+int launch_build_two_pass(sl2_engine* e, int threads);
+int launch_chol_per_block(sl2_engine* e);
+int launch_fwdsub_reread(sl2_engine* e);
 int launch_finalize(sl2_engine* e, int save_trajectory);
 int launch_mapping(sl2_engine* e, const TailPlan& tp);
 int launch_manual_init(sl2_engine* e, const int* d_uv);

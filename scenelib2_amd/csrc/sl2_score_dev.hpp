@@ -105,7 +105,7 @@ __device__ __forceinline__ void search_score_body(const int b, const int* __rest
   // The successful measurements, compacted in SLOT order (= feature_list_ order).  The reference stacks them in
   // selected_feature_list_ order (construct_total_measurement_stuff, monoslam.cpp:548-572); any order of the rows of H gives
   // the same update, and with this one the features of a 64-column tile of P are consecutive rows of A^T and consecutive
-  // rows / columns of S, which is what lets k_build_AS_tiles write whole blocks (sl2_ekf_update.hip).
+  // rows / columns of S, which is what lets k_build_AS_tiles write whole blocks (sl2_update_build.hip).
   int base = 0;
   for (int i0 = 0; i0 < N; i0 += (int)blockDim.x) {
     const int i = i0 + tid;

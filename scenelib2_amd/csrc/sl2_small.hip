@@ -14,7 +14,7 @@
 //                   A^T = (P H^T)^T and S = H A + R in LDS, S = L L^T and L^-1 by the D-wave routine of the blocked Cholesky
 //                   (sl2_chol_diag.hpp) on one wavefront, V = L^-1 A^T in place (a column per thread, the column in
 //                   registers), P -= V^T V and x += V^T (L^-1 nu) straight on the covariance in memory - the algebra of
-//                   sl2_ekf_update.hip (W S W^T = V^T V), no workspace in HBM at all.
+//                   sl2_ekf_update.hip's head (W S W^T = V^T V), no workspace in HBM at all.
 //
 // Compiled with -ffp-contract=off like every translation unit that holds model math; the update's FMAs are spelled out.
 #include "sl2_frontend_dev.hpp"

@@ -4,7 +4,7 @@
 //
 // Nothing is computed ahead of the question.  Every form of the update leaves, per sequence b with m = 2 m_gate[b] rows,
 //   Vt[b][r][ld - 1]       = w_r, w = L^-1 nu      (the innovation rides through the substitution as the last column of A^T:
-//                            k_fwdsub_ksplit, k_fwdsub_lds<NB>, the grouped form with k_fwd_gemm - sl2_ekf_update.hip; the fused
+//                            k_fwdsub_ksplit, k_fwdsub_lds<NB>, the grouped form with k_fwd_gemm - sl2_update_fwdsub.hip; the fused
 //                            small-map step stores it from its LDS panel - sl2_small.hip)
 //   LinvT[b][r / 32][r % 32][r % 32] = 1 / L_rr    (k_chol_left keeps the diagonal blocks of L in LDS and writes only their
 //                            inverses, one launch or panel-wise; St's diagonal blocks still hold S there, so the pivot is taken

@@ -1,4 +1,4 @@
-// What the dense EKF update (sl2_ekf_update.hip) launches, decided ONCE: the sizes sl2_create gives the innovation system, and the
+// What the dense EKF update (launch_update, sl2_ekf_update.hip, and the phase units sl2_update_*.hip) launches, decided ONCE: the sizes sl2_create gives the innovation system, and the
 // update plan - the form of every step of the update (build A and S, factor S, substitute; the SYRK has one form) with the launch
 // parameters that depend on the shape.  launch_update makes the plan per call from the engine's shape and knobs and walks it;
 // the launchers take their widths from it and compare nothing themselves.

@@ -1,9 +1,22 @@
-// TEST build only (libscenelib2_amd_test.so, -DSL2_TESTING): the superseded kernel variants of sl2_ekf_update.hip and its test /
-// calibration entry points, kept out of the product translation unit's text.  sl2_ekf_update.hip includes this file once per
-// section, at the place where the section's code used to stand (the sections use helpers defined between them), with
-// SL2_EKF_TEST_SECTION set; see include/scenelib2_amd_testing.h and scripts/variants.sh for what selects these kernels.
+// TEST build only (libscenelib2_amd_test.so, -DSL2_TESTING): the superseded kernel variants of the dense EKF update with their
+// launchers, and the update's test / calibration entry points - a translation unit of its own, linked into the TEST library
+// alone.  launch_update (sl2_ekf_update.hip, its -DSL2_TESTING build) calls the launchers where the plan names their form; see
+// include/scenelib2_amd_testing.h and scripts/variants.sh for what selects these kernels.
+#include "sl2_update_dev.hpp"
+#include "sl2_chol_diag.hpp"
+#include "../../include/scenelib2_amd_testing.h"
 
-#if SL2_EKF_TEST_SECTION == 1
+namespace sl2 {
+
+// ---------------------------------------------------------------------------
+// k_build_A: At[a][i] = (P H^T)[i][a], a = 2j+r for the j-th successful feature.
+// Column ld-1 carries the innovation nu (so that L^-1 nu and W nu fall out of the
+// same substitution / SYRK).  Rows of padding up to a multiple of 32 are zeroed.
+// One workgroup per sequence; a thread keeps the 7 pose entries of its column in
+// registers and loops over the features (3 coalesced row reads of P + 2 coalesced row
+// writes of At per feature, each a full contiguous row for the workgroup).
+// (Maps beyond what k_build_AS takes are not built by the product - sl2_create rejects them: SL2_BUILD_VARIANT=0.)
+// ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(512) k_build_A(const double* __restrict__ P, const double* __restrict__ f_Hx,
                                                  const double* __restrict__ f_Hy, const double* __restrict__ f_nu,
                                                  const int* __restrict__ succ_idx, const int* __restrict__ m_count,
@@ -45,10 +58,13 @@ __global__ void __launch_bounds__(512) k_build_A(const double* __restrict__ P, c
     }
   }
 }
-#endif  // section 1
 
-
-#if SL2_EKF_TEST_SECTION == 3
+// ---------------------------------------------------------------------------
+// k_build_S: S = H A + R, stored St[c][r] = S[r][c] (32x32 blocks on and below the block
+// diagonal; the factorisation reads r >= c plus the full diagonal blocks).  Padding: identity.  A thread owns one row
+// a of H (its 10 non-zeros in registers) and loops over 32 columns bb: per column
+// 7 wave-uniform loads (pose part of At row bb) + 3 gathered loads within that row.
+// ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_build_S(const double* __restrict__ At, const double* __restrict__ f_Hx,
                                                  const double* __restrict__ f_Hy, const double* __restrict__ f_R,
                                                  const int* __restrict__ succ_idx, const int* __restrict__ m_count,
@@ -96,9 +112,35 @@ __global__ void __launch_bounds__(256) k_build_S(const double* __restrict__ At, 
     Sb[(size_t)bb * mld + a] = v;
   }
 }
-#endif  // section 3
 
-#if SL2_EKF_TEST_SECTION == 4
+// ---------------------------------------------------------------------------
+// Blocked Cholesky of S (right-looking over 32x32 blocks, three launches per
+// block column J): diag -> panel -> trailing update.
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ double fast_rcp(double p) {
+  double r = __builtin_amdgcn_rcp(p);
+  r = __builtin_fma(__builtin_fma(-p, r, 1.0), r, r);
+  r = __builtin_fma(__builtin_fma(-p, r, 1.0), r, r);
+  return r;
+}
+__device__ __forceinline__ double fast_rsqrt(double p) {
+  double y = __builtin_amdgcn_rsq(p);
+  y = y * __builtin_fma(-0.5 * p * y, y, 1.5);
+  y = y * __builtin_fma(-0.5 * p * y, y, 1.5);
+  return y;
+}
+
+// k_chol_diag: one wave per sequence factors the (already updated) 32x32 diagonal
+// block entirely in registers: lane r holds row r; pivots and column entries are
+// broadcast with v_readlane (scalar operands of the FP64 FMAs), so there is no LDS
+// round trip in the 32-step dependency chain.  Then the triangle is inverted row-wise
+// (lane k solves X[k][:] L = e_k) and both L_JJ (in place) and LinvT are written
+// with coalesced stores.
+// (Measured alternatives on MI355X, per launch at batch 1024: LDS-resident block with one
+// row per lane 67 us; column broadcast through LDS 43 us; 256-thread cooperative version with
+// two barriers per column 36 us; single wave, element-parallel in LDS 47 us; this one 35 us —
+// every variant is bound by the ~1 us dependent chain per column, not by throughput.)
 __global__ void __launch_bounds__(64) k_chol_diag(double* __restrict__ St, double* __restrict__ LinvT,
                                                   const int* __restrict__ m_count, int mld, int nblk_max, int J) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -147,9 +189,9 @@ __global__ void __launch_bounds__(64) k_chol_diag(double* __restrict__ St, doubl
     }
   }
 }
-#endif  // section 4
 
-#if SL2_EKF_TEST_SECTION == 5
+// k_chol_panel: L[I][J] = S[I][J] * L_JJ^-T for every block row I > J; one wave
+// per 32x32 tile.  In k-major storage: new[k][i] = sum_p Linv[k][p] * St[J+p][I+i].
 __global__ void __launch_bounds__(64) k_chol_panel(double* __restrict__ St, const double* __restrict__ LinvT,
                                                    const int* __restrict__ m_count, int mld, int nblk_max, int J) {
   const int b = blockIdx.y, lane = threadIdx.x;
@@ -182,9 +224,8 @@ __global__ void __launch_bounds__(64) k_chol_panel(double* __restrict__ St, cons
       for (int r = 0; r < 4; ++r)
         Sb[(size_t)(J * 32 + 16 * kt + hi + 4 * r) * mld + I * 32 + 16 * it + lo] = acc[kt][it][r];
 }
-#endif  // section 5
 
-#if SL2_EKF_TEST_SECTION == 6
+// k_chol_trail: S[I][K] -= L[I][J] L[K][J]^T for J < K <= I; one wave per tile.
 __global__ void __launch_bounds__(64) k_chol_trail(double* __restrict__ St, const int* __restrict__ m_count, int mld, int J) {
   const int b = blockIdx.y, lane = threadIdx.x;
   const int cnt = m_count[b];
@@ -223,10 +264,22 @@ __global__ void __launch_bounds__(64) k_chol_trail(double* __restrict__ St, cons
       for (int r = 0; r < 4; ++r)
         Sb[(size_t)(K * 32 + 16 * jt + hi + 4 * r) * mld + I * 32 + 16 * it + lo] = acc[jt][it][r];
 }
-#endif  // section 6
 
-
-#if SL2_EKF_TEST_SECTION == 8
+// ---------------------------------------------------------------------------
+// k_fwdsub: Vt = L^-1 At by blocked forward substitution.  Columns are
+// independent: each wave owns 16 columns and walks the block rows J in order,
+//   acc = At[J] - sum_{K<J} L[J][K] Vt[K] ;  Vt[J] = L_JJ^-1 acc.
+// A lane re-reads only Vt elements it stored itself (D fragment == B fragment).
+// The chain is latency-bound (every k-step needs 3 L2-resident operands); what hides
+// it is occupancy (64 VGPRs -> 7 waves per SIMD) plus the unrolled k-loop, which puts
+// 8 k-steps of loads in flight ahead of their MFMAs.  A last block whose upper 16
+// rows are all padding skips them.  32 columns per wave give four independent
+// accumulator chains and 4 MFMAs per 3 fragment loads.
+// (Tried and measured slower on MI355X, batch 1024: L blocks through LDS with a 4-wave
+// barrier per block, 0.72 ms; V^T resident in LDS with one wave per workgroup, 2.1 ms;
+// an explicit two-stage register pipeline, 1.04 ms at 256 VGPRs — each loses the
+// occupancy that hides the chain's latency.  This version: see profiles/.)
+// ---------------------------------------------------------------------------
 template <bool HALF>
 __device__ __forceinline__ void fwd_kloop(v4d acc[2][2], const double* __restrict__ lrow, const double* vrow, int mld, int ld,
                                           int kend) {
@@ -301,14 +354,12 @@ __global__ void __launch_bounds__(128) k_fwdsub(const double* __restrict__ At, d
     }
   }
 }
-#endif  // section 8
 
-#if SL2_EKF_TEST_SECTION == 9
 // ---------------------------------------------------------------------------
 // The launchers of the superseded kernels above: launch_update calls them where the plan (sl2_update_plan.hpp, with
 // UpdateShape::superseded) names their form - BuildForm::kTwoPass, CholForm::kPerBlock, FwdForm::kReread.
 // ---------------------------------------------------------------------------
-static int launch_build_two_pass(sl2_engine* e, int threads) {
+int launch_build_two_pass(sl2_engine* e, int threads) {
   const int B = e->B;
   {
     LaunchScope ls(e, "k_build_A", true);
@@ -327,7 +378,7 @@ static int launch_build_two_pass(sl2_engine* e, int threads) {
 }
 
 // three launches per block column
-static int launch_chol_per_block(sl2_engine* e) {
+int launch_chol_per_block(sl2_engine* e) {
   const int B = e->B;
   for (int J = 0; J < e->nblk_max; ++J) {
     {
@@ -353,7 +404,7 @@ static int launch_chol_per_block(sl2_engine* e) {
   return SL2_OK;
 }
 
-static int launch_fwdsub_reread(sl2_engine* e) {
+int launch_fwdsub_reread(sl2_engine* e) {
   const int B = e->B;
   LaunchScope ls(e, "k_fwdsub", true);
   hipLaunchKernelGGL(k_fwdsub, dim3(xcd_grid(e->ld / 64, B)), dim3(128), 0, e->stream, e->At, e->Vt, e->St, e->LinvT,
@@ -385,10 +436,9 @@ __global__ void __launch_bounds__(64) k_gemm_kt(const double* __restrict__ XT, i
     for (int jt = 0; jt < 2; ++jt)
       for (int r = 0; r < 4; ++r) C[(size_t)(i0 + 16 * it + hi + 4 * r) * ldc + j0 + 16 * jt + lo] = acc[it][jt][r];
 }
-#endif  // section 9
 
-#if SL2_EKF_TEST_SECTION == 10
-#include "../../include/scenelib2_amd_testing.h"
+}  // namespace sl2
+
 extern "C" int sl2_debug_update_plan(sl2_engine* e, int group, int* out, int n) {
   using namespace sl2;
   if (!e || !out || group < 0 || group >= (int)e->root->groups.size() || n < kUpdatePlanInts) return SL2_ERR_INVALID;
@@ -563,4 +613,3 @@ extern "C" int sl2_debug_microbench(int device, int which, double* result) {
   hipEventDestroy(e0); hipEventDestroy(e1);
   return SL2_OK;
 }
-#endif  // section 10

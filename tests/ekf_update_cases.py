@@ -1,4 +1,4 @@
-"""The case table of the dense EKF update's edges (sl2_ekf_update.hip): every k_fwdsub_lds<NB> instantiation, the block and
+"""The case table of the dense EKF update's edges (sl2_ekf_update.hip and its phase units sl2_update_*.hip): every k_fwdsub_lds<NB> instantiation, the block and
 chunk remainders of m, systems that shrink from one update to the next on one engine, mixed systems in one launch, both sides of
 every dispatch boundary of the update plan (sl2_update_plan.hpp), the forms of k_build_AS and the live-tile rules of k_syrk.
 Pure numpy and the CPU oracle: tests/test_ekf_update_cases_host.py shows on the oracle alone that every schedule reaches the m

@@ -1,4 +1,4 @@
-"""k_build_AS_ahead against k_build_AS, bit for bit (sl2_ekf_update.hip).
+"""k_build_AS_ahead against k_build_AS, bit for bit (sl2_update_build.hip).
 
 The form that keeps a batch of rows of P in flight computes every entry of A^T and S by the expression of k_build_AS, so two
 engines on the same inputs that differ in nothing but the form (TEST build: SL2_BUILD_SPLIT=1 gives one workgroup per sequence

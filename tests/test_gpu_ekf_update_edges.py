@@ -1,4 +1,4 @@
-"""The dense EKF update (sl2_ekf_update.hip: k_build_AS -> k_chol_left | panels -> k_fwdsub_ksplit | k_fwdsub_lds<NB> | grouped ->
+"""The dense EKF update (sl2_ekf_update.hip walking sl2_update_{build,chol,fwdsub,syrk}.hip: k_build_AS -> k_chol_left | panels -> k_fwdsub_ksplit | k_fwdsub_lds<NB> | grouped ->
 k_syrk) held to an extended-precision truth and to the oracle on every case of tests/ekf_update_cases.py: each of the thirteen
 k_fwdsub_lds<NB>, partly and fully live; m at every remainder of the 32-row block and of k_syrk's 16-row chunk, falling and
 rising on one engine so that rows of a larger system sit in the padding of the workspaces; mixed systems and a paused sequence

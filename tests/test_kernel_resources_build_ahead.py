@@ -1,4 +1,4 @@
-"""Resource budget of k_build_AS_ahead (sl2_ekf_update.hip), checked at build time like tests/test_kernel_resources.py.
+"""Resource budget of k_build_AS_ahead (sl2_update_build.hip), checked at build time like tests/test_kernel_resources.py.
 
 The form exists to keep more bytes in flight per CU than k_build_AS, so what it may spend is fixed: at most 96 registers
 (five wavefronts per SIMD; the kernel as measured uses 80, six per SIMD), nothing spilled, and at most 40 KB of LDS per workgroup - four workgroups of the headline shape
@@ -16,7 +16,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "scenelib2_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SRC = "sl2_ekf_update.hip"
+SRC = "sl2_update_build.hip"
 PLAN_HDR = "sl2_update_plan.hpp"
 MAX_REGS, MAX_LDS = 96, 40 * 1024
 
