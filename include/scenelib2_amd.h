@@ -52,7 +52,9 @@ extern "C" {
  * SL2_ITEM_SEGMENT, sl2_rectify_frames, sl2_rectify_frame_host, sl2_scene_items, sl2_scene_item_bound, sl2_draw_rectified,
  * SL2_SCENE_* (the rectified view of GraphicTool::DrawRectifiedAR: a line primitive, the undistorted frame, the 3-D scene);
  * sl2_view, sl2_view_look_at, sl2_world_items, sl2_world_item_bound, sl2_draw_world, SL2_WORLD_*, sl2_pick_items_batch,
- * sl2_pick_items_host (the world view of GraphicTool::Draw3dScene from a free camera, and GraphicTool::Picker). */
+ * sl2_pick_items_host (the world view of GraphicTool::Draw3dScene from a free camera, and GraphicTool::Picker);
+ * sl2_converter_set_map, sl2_converter_set_remaps, sl2_converter_get_remaps, sl2_remap_frame_host, SL2_REMAP_BORDER, sl2_lens,
+ * SL2_LENS_*, sl2_lens_map_host, sl2_lens_pinhole_camera (the lens remap: OpenCV and fisheye cameras through a per-pixel map). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -541,6 +543,92 @@ int sl2_convert_frame_host_filtered(const sl2_frame_source* src, int filter, con
  * survives a uniform scale only: in->width * out_height != in->height * out_width is refused (SL2_ERR_INVALID) - the
  * conversion itself accepts any aspect ratio.  Host only. */
 int sl2_scale_camera(const sl2_camera* in, int out_width, int out_height, sl2_camera* out);
+
+/* ---- the lens remap (additions within SL2_API_VERSION 5): a sequence follows a per-pixel map instead of a resize filter ----
+ * The filter knows one lens model, the reference's single-coefficient radial one (sl2_camera.kd1; Camera::Project / Unproject,
+ * camera.cpp:90-154).  Calibrations come as OpenCV's k1 k2 p1 p2 k3 [k4 k5 k6] or its fisheye k1 .. k4.  A map brings such a
+ * camera's frames into an image the filter's model describes: cv::initUndistortRectifyMap plus cv::remap, for the whole batch in
+ * one launch in front of the step.  The map is the general primitive: a rotated or mirrored mount, a crop, a stereo
+ * rectification or a lens model of the caller's own are maps too (sl2_lens_map_host below builds the ones from calibrations).
+ *
+ * A map belongs to a source size W x H and to the converter's output size: int32_t xy[out_height][out_width][2].  (X, Y) is the
+ * position in the source's grey plane in 1/32 of a source pixel; pixel centres sit on integers, X = 32 x is column x (the
+ * convention of sl2_rectify_frames); X == SL2_REMAP_BORDER means no source (Y is then ignored).  Per output pixel, in 32-bit integers
+ * (scenelib2_amd/csrc/sl2_convert_dev.hpp, remap_pixel):
+ *   a border entry gives 0.  Otherwise fx = X & 31, ix = (X - fx) / 32, fy = Y & 31, iy = (Y - fy) / 32 (two's complement: fx, fy
+ *   in 0 .. 31 and ix, iy the floors, for negative positions too);
+ *   a tap p(ix, iy) is g[iy][ix] where 0 <= ix < W and 0 <= iy < H, else 0; g is the grey defined above for the source's format -
+ *   for Bayer the demosaic, with its own reflection for the neighbours of an in-image tap; a neighbour whose weight is 0 is not read
+ *   (it needs no source pixel: X = 32 (W - 1) is the last column itself; both forms fetch the byte of a tap that does not count
+ *   from the clamped, in-image coordinate and discard it, so nothing outside the W x H source is ever addressed);
+ *   out = ((32 - fx)(32 - fy) p(ix, iy) + fx (32 - fy) p(ix + 1, iy) + (32 - fx) fy p(ix, iy + 1) + fx fy p(ix + 1, iy + 1) + 512) >> 10.
+ * It is the identity for the identity map (X = 32 x, Y = 32 y at equal sizes) and maps a constant source to the same constant
+ * wherever all four taps lie inside.  It applies NO anti-aliasing: two taps an axis whatever the map's local scale, so a map that
+ * reduces by much more than two aliases like SL2_RESIZE_LINEAR (reduce with a larger output, or remap a source the camera bins).
+ *
+ * sl2_converter_set_map: the converter has nseq map slots, 0 .. nseq - 1, empty after create.  The call fills or replaces one
+ * slot with a map for sources of src_width x src_height; xy is consumed before it returns; xy == NULL empties the slot.  A setup
+ * call like sl2_converter_set_sources: it may wait for the last conversion queued, which keeps the map it was queued with.  An
+ * entry that can reach no source pixel with a weight above 0 is kept as the border entry (the result is 0 either way).
+ * Refused (SL2_ERR_INVALID, nothing changed): a slot outside the range; a size outside the source caps (1 .. 4096 by 1 .. 16384);
+ * emptying a slot, or changing the size of one, that a sequence still uses (the text names the first such sequence).
+ * sl2_converter_set_remaps / sl2_converter_get_remaps: the slot of each sequence of seq0 .. seq0 + nseq - 1, or -1 for none (the
+ * state after create).  Many sequences may share a slot: a fleet of identical cameras.  A sequence with a map ignores its resize
+ * filter; the filter stays set (and stays checked against the source) and acts again once the slot is -1.  Refused (SL2_ERR_INVALID, no
+ * sequence of the range changes, the text names the sequence): a slot outside -1 .. nseq - 1, an empty slot, a sequence whose
+ * source is set with another size than the map's.  sl2_converter_set_sources likewise refuses a source whose size differs from
+ * its sequence's map.
+ * sl2_convert_frames then issues one more launch (k_convert_remap) for the mapped sequences, which leave the other kernels'
+ * lists; with no mapped sequence nothing new is launched and no existing launch changes.
+ * sl2_remap_frame_host: the host form for one sequence (no GPU needed); the map is one for src->width x src->height.  The
+ * refusals of sl2_convert_frame_host, and xy == NULL.
+ * Not covered: an anti-aliased remap; maps on the device (a map is set from host memory). */
+#define SL2_REMAP_BORDER INT32_MIN
+int sl2_converter_set_map(sl2_converter* c, int slot, int src_width, int src_height, const int32_t* xy);
+int sl2_converter_set_remaps(sl2_converter* c, int seq0, int nseq, const int32_t* slots);
+int sl2_converter_get_remaps(const sl2_converter* c, int seq0, int nseq, int32_t* slots);
+int sl2_remap_frame_host(const sl2_frame_source* src, const int32_t* xy, const void* raw, size_t raw_bytes, int out_width,
+                         int out_height, uint8_t* out);
+
+/* ---- maps from calibrations (additions within SL2_API_VERSION 5; host only, no device) ----
+ * sl2_lens_map_host fills xy[target->height][target->width][2] with the map that takes an image `target` would have seen and
+ * reads it out of the lens's image (lens->width x lens->height, the map's source size).  `target` is the calibration the engine
+ * will run with (sl2_create / sl2_set_cameras); its width and height are the converter's output size.  Any target is accepted.
+ * FP64, no contraction into fused multiply-adds, every line in the order written, parentheses included.  For target pixel (x, y):
+ *   cx = x - u0;  cy = y - v0;  f = 1 - (2 kd1) (cx cx + cy cy);  if f > 0 does not hold the entry is the border;
+ *   s = sqrt(f);  a = (cx / s) / fku;  b = (cy / s) / fkv.
+ * (a, b) are image-plane coordinates, x to the right and y down: OpenCV's x', y'.  The reference's camera axes point the other way
+ * (u = u0 - fku X / Z), but both conventions put u at u0 + fku x', so the image is neither mirrored nor turned.
+ * With (fx, fy, cx, cy) and k[] now the LENS's, the source position (us, vs) is
+ *   SL2_LENS_RADIAL1 (the reference's own model, k[0] = kd1):  px = fx a;  py = fy b;  q = 1 + (2 k[0]) (px px + py py);
+ *     if q > 0 does not hold the entry is the border;  s = sqrt(q);  us = px / s + cx;  vs = py / s + cy.
+ *   SL2_LENS_BROWN (OpenCV's order: k[0..7] = k1 k2 p1 p2 k3 k4 k5 k6):  r2 = a a + b b;  r4 = r2 r2;  r6 = r4 r2;
+ *     num = ((1 + k1 r2) + k2 r4) + k3 r6;  den = ((1 + k4 r2) + k5 r4) + k6 r6;  den == 0 is the border;  rad = num / den;  ab = a b;
+ *     xd = (a rad + (2 p1) ab) + p2 (r2 + 2 (a a));  yd = (b rad + p1 (r2 + 2 (b b))) + (2 p2) ab;  us = fx xd + cx;  vs = fy yd + cy.
+ *   SL2_LENS_FISHEYE (Kannala-Brandt as OpenCV's fisheye, k[0..3] = k1 .. k4):  r = sqrt(a a + b b);  r == 0 gives (cx, cy);  else
+ *     th = atan(r);  t2 = th th;  t4 = t2 t2;  t6 = t4 t2;  t8 = t4 t4;  thd = th ((((1 + k1 t2) + k2 t4) + k3 t6) + k4 t8);
+ *     sc = thd / r;  us = fx (a sc) + cx;  vs = fy (b sc) + cy.
+ * A position that is not finite or lies beyond +-2^20 is the border.  Otherwise X = floor(us 32 + 0.5), Y = floor(vs 32 + 0.5).
+ * Only atan is not correctly rounded everywhere: a FISHEYE entry may differ by one unit between two C libraries where
+ * us 32 + 0.5 lies within an ulp or so of an integer; RADIAL1 and BROWN are exact (+ - x / sqrt).
+ * What the target costs: sl2_lens_pinhole_camera (kd1 = 0) is the obvious one, but a wide lens keeps its field better under a
+ * target with kd1 > 0 - a pinhole target of the same focal length stretches the periphery, one of a shorter focal length gives
+ * the centre fewer pixels.  Where the map leaves the lens's image the output is the border (0), which the filter sees as texture.
+ * Refused (SL2_ERR_INVALID): a NULL, an unknown model, a lens size outside the source caps, a target size outside 1 .. 4096.
+ * Not covered: a polynomial that folds back beyond the calibrated field maps far target pixels onto near source pixels (the
+ * caller's problem: OpenCV does not guard it either); parity with OpenCV itself is unpinned - none exists where this was
+ * written; this text is the definition.
+ * sl2_lens_pinhole_camera: the pinhole target that sees the lens's image plane resized to out_width x out_height: kd1 = 0,
+ * fku = fx out_width / width, fkv = fy out_height / height (the product first), u0 = (cx + 0.5) out_width / width - 0.5, v0
+ * likewise with the heights; sd as given.  With a zero-distortion lens the map is then the plain resize's. */
+enum { SL2_LENS_RADIAL1 = 0, SL2_LENS_BROWN = 1, SL2_LENS_FISHEYE = 2 };
+typedef struct sl2_lens {                /* 112 bytes */
+  int32_t model, width, height;          /* SL2_LENS_*; the size of the lens's image: the map's source size */
+  double fx, fy, cx, cy;                 /* pixels, OpenCV's camera matrix (pixel centres on integers) */
+  double k[8];                           /* by model, see above; the rest ignored */
+} sl2_lens;
+int sl2_lens_map_host(const sl2_lens* lens, const sl2_camera* target, int32_t* xy);
+int sl2_lens_pinhole_camera(const sl2_lens* lens, int out_width, int out_height, int sd, sl2_camera* out);
 
 /* ----------------------------------------------------------------- state access */
 

@@ -222,17 +222,29 @@ class MonoSLAM {
   // first call; a later call names another source (a camera that changed its mode).
   void SetFrameSource(int width, int height, int pitch, int format) {
     if (!eng_) throw std::runtime_error("MonoSLAM::SetFrameSource: call Init first");
-    if (!converter_) {
-      check(sl2_converter_create(device_, 1, camera_->width_, camera_->height_, &converter_), "sl2_converter_create");
-      void* p = nullptr;
-      check(sl2_dev_malloc(device_, (size_t)camera_->width_ * camera_->height_, &p), "sl2_dev_malloc");
-      frame_dev_ = (uint8_t*)p;
-      const int32_t f = frame_filter_;
-      check(sl2_converter_set_filters(converter_, 0, 1, &f), "sl2_converter_set_filters");
-    }
+    ensure_converter();
     sl2_frame_source src;
     src.width = width; src.height = height; src.pitch = pitch; src.format = format; src.offset = 0;
     check(sl2_converter_set_sources(converter_, 0, 1, &src), "sl2_converter_set_sources");
+  }
+
+  // A camera whose lens the filter's model does not describe - OpenCV's k1 k2 p1 p2 k3 [k4 k5 k6], or its fisheye k1 .. k4:
+  // GoOneStepRaw then reads every frame through the map from `target` into the lens's image (sl2_lens_map_host; the
+  // cv::initUndistortRectifyMap + cv::remap a caller would otherwise run per frame on the host), in place of the resize filter, and
+  // the filter runs with `target` (SetCameraParameters).  target's size is the engine's; sl2_lens_pinhole_camera gives the obvious
+  // one, a target with kd1 > 0 keeps more of a wide lens's field.  Before or after SetFrameSource, whose size must be the lens's.
+  void SetLens(const sl2_lens& lens, const sl2_camera& target) {
+    if (!eng_) throw std::runtime_error("MonoSLAM::SetLens: call Init first");
+    if (target.width != camera_->width_ || target.height != camera_->height_)
+      throw std::runtime_error("MonoSLAM::SetLens: the target's size is not the engine's image size");
+    std::vector<int32_t> xy((size_t)2 * (size_t)target.width * (size_t)target.height);
+    check(sl2_lens_map_host(&lens, &target, xy.data()), "sl2_lens_map_host");
+    ensure_converter();
+    const int32_t none = -1, slot = 0;
+    check(sl2_converter_set_remaps(converter_, 0, 1, &none), "sl2_converter_set_remaps");      // (a slot in use keeps its size)
+    check(sl2_converter_set_map(converter_, 0, lens.width, lens.height, xy.data()), "sl2_converter_set_map");
+    check(sl2_converter_set_remaps(converter_, 0, 1, &slot), "sl2_converter_set_remaps");
+    SetCameraParameters(target.width, target.height, target.fku, target.fkv, target.u0, target.v0, target.kd1, target.sd);
   }
 
   // How GoOneStepRaw brings the camera's frame to the engine's size: SL2_RESIZE_LINEAR (the reference's plain INTER_LINEAR, the
@@ -516,6 +528,16 @@ class MonoSLAM {
  private:
   static void check(int rc, const char* what) {
     if (rc != SL2_OK) throw std::runtime_error(std::string(what) + ": " + sl2_last_error());
+  }
+  // The converter and the device frame of GoOneStepRaw, created by whichever of SetFrameSource and SetLens comes first
+  void ensure_converter() {
+    if (converter_) return;
+    check(sl2_converter_create(device_, 1, camera_->width_, camera_->height_, &converter_), "sl2_converter_create");
+    void* p = nullptr;
+    check(sl2_dev_malloc(device_, (size_t)camera_->width_ * camera_->height_, &p), "sl2_dev_malloc");
+    frame_dev_ = (uint8_t*)p;
+    const int32_t f = frame_filter_;
+    check(sl2_converter_set_filters(converter_, 0, 1, &f), "sl2_converter_set_filters");
   }
   static std::map<std::string, std::string> parse_vars(const std::string& path) {
     std::ifstream in(path);

@@ -103,6 +103,18 @@ SL2_PIX_GRAY8, SL2_PIX_RGB24, SL2_PIX_BGR24, SL2_PIX_UYVY, SL2_PIX_YUYV = range(
 SL2_PIX_GRAY10, SL2_PIX_GRAY12, SL2_PIX_GRAY16 = 16, 17, 18
 SL2_PIX_BAYER_RGGB8, SL2_PIX_BAYER_GRBG8, SL2_PIX_BAYER_GBRG8, SL2_PIX_BAYER_BGGR8 = 24, 25, 26, 27
 SL2_RESIZE_LINEAR, SL2_RESIZE_AREA = 0, 1
+# the lens remap: a map entry without a source, the lens models of sl2_lens_map_host
+SL2_REMAP_BORDER = -2 ** 31
+SL2_LENS_RADIAL1, SL2_LENS_BROWN, SL2_LENS_FISHEYE = 0, 1, 2
+
+
+class sl2_lens(C.Structure):
+    """A calibrated lens (convert.lens_map): OpenCV's camera matrix and the coefficients of its model."""
+    _fields_ = [("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 8)]
+
+
+assert C.sizeof(sl2_lens) == 112
 # sections of a snapshot blob (sl2_snapshot_batch); the header, xv_ and Pxx_ are always present
 SL2_SNAP_POSE, SL2_SNAP_FEATURES, SL2_SNAP_COV, SL2_SNAP_SELECTION, SL2_SNAP_TRAJ, SL2_SNAP_PARTIAL, SL2_SNAP_PATCHES = 0, 1, 2, 4, 8, 16, 32
 SL2_SNAP_ALL = 63
@@ -168,6 +180,8 @@ EXPORTED_SYMBOLS = [
     "sl2_overlay_item_bound", "sl2_overlay_items", "sl2_draw_items_batch", "sl2_draw_overlays", "sl2_draw_items_host",
     "sl2_rectify_frames", "sl2_rectify_frame_host", "sl2_scene_item_bound", "sl2_scene_items", "sl2_draw_rectified",
     "sl2_view_look_at", "sl2_world_item_bound", "sl2_world_items", "sl2_draw_world", "sl2_pick_items_batch", "sl2_pick_items_host",
+    "sl2_converter_set_map", "sl2_converter_set_remaps", "sl2_converter_get_remaps", "sl2_remap_frame_host",
+    "sl2_lens_map_host", "sl2_lens_pinhole_camera",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures",
@@ -306,6 +320,13 @@ def _bind(L):
         L.sl2_converter_get_filters.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         L.sl2_convert_frame_host_filtered.argtypes = [C.POINTER(sl2_frame_source), C.c_int, vp, C.c_size_t, C.c_int, C.c_int, c_u8p]
         L.sl2_scale_camera.argtypes = [C.POINTER(sl2_camera), C.c_int, C.c_int, C.POINTER(sl2_camera)]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_converter_set_map"):
+        L.sl2_converter_set_map.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.sl2_converter_set_remaps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.sl2_converter_get_remaps.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.sl2_remap_frame_host.argtypes = [C.POINTER(sl2_frame_source), C.POINTER(C.c_int32), vp, C.c_size_t, C.c_int, C.c_int, c_u8p]
+        L.sl2_lens_map_host.argtypes = [C.POINTER(sl2_lens), C.POINTER(sl2_camera), C.POINTER(C.c_int32)]
+        L.sl2_lens_pinhole_camera.argtypes = [C.POINTER(sl2_lens), C.c_int, C.c_int, C.c_int, C.POINTER(sl2_camera)]
     if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_snapshot_batch"):      # (an older build under test, scripts/ab_libs.sh)
         L.sl2_snapshot_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.sl2_snapshot_bound.restype = C.c_size_t

@@ -3,7 +3,8 @@
 The reference's UsbCamGrabber reduces whatever the camera delivers to 8-bit grey and resizes it to the filter's image size
 before GoOneStep sees it.  FrameConverter does that for a whole batch in one launch on the device: every sequence has its own
 source size, row pitch and pixel format.  convert_frame_host is the same arithmetic for one sequence on the host, and
-scale_camera the calibration that goes with the resized image.
+scale_camera the calibration that goes with the resized image.  A camera whose lens the filter's model does not describe
+follows a per-pixel map instead (lens_map, pinhole_camera, FrameConverter.set_map / set_remaps, remap_frame_host).
 """
 import ctypes as C
 
@@ -86,6 +87,31 @@ class FrameConverter:
         _lib.check(self.L.sl2_converter_get_filters(self.h, int(seq0), nseq, arr), self.L)
         return list(arr)
 
+    def set_map(self, slot, src_width=0, src_height=0, xy=None):
+        """Fill or replace map slot `slot` (0 .. nseq - 1) with xy: int32 [out_height][out_width][2], positions in the grey plane
+        of a src_width x src_height source in 1/32 pixel, SL2_REMAP_BORDER in X for no source (lens_map builds one from a
+        calibration).  xy=None empties the slot.  A setup call: it may wait; xy is consumed before it returns."""
+        if xy is None:
+            _lib.check(self.L.sl2_converter_set_map(self.h, int(slot), int(src_width), int(src_height), None), self.L)
+            return
+        a = np.ascontiguousarray(xy, dtype=np.int32)
+        assert a.shape == (self.out_height, self.out_width, 2), a.shape
+        _lib.check(self.L.sl2_converter_set_map(self.h, int(slot), int(src_width), int(src_height), _lib.ip(a)), self.L)
+
+    def set_remaps(self, slots, seq0=0):
+        """The map slot of sequences seq0 ..., -1 (or None) for none; one value stands for a list of one.  A sequence with a map
+        ignores its resize filter, which acts again once its slot is -1.  A setup call like set_sources."""
+        if slots is None or isinstance(slots, int):
+            slots = [slots]
+        arr = (C.c_int32 * len(slots))(*[-1 if s is None else int(s) for s in slots])
+        _lib.check(self.L.sl2_converter_set_remaps(self.h, int(seq0), len(slots), arr), self.L)
+
+    def get_remaps(self, seq0=0, nseq=None):
+        nseq = self.nseq - seq0 if nseq is None else int(nseq)
+        arr = (C.c_int32 * nseq)()
+        _lib.check(self.L.sl2_converter_get_remaps(self.h, int(seq0), nseq, arr), self.L)
+        return list(arr)
+
     def convert(self, raw, d_frames, seq_stride=0, stream=None, raw_bytes=None):
         """raw: a uint8 array in host memory (copied to the converter's staging buffer on `stream`; keep it alive and
         unchanged until the stream has passed the copy), or a (device pointer, bytes) pair.  d_frames: a device pointer
@@ -129,6 +155,59 @@ def convert_frame_host(src, raw, out_width, out_height, raw_bytes=None, filter="
         _lib.check(L.sl2_convert_frame_host_filtered(C.byref(s), f, a.ctypes.data_as(_lib.vp), n, int(out_width), int(out_height),
                                                      _lib.u8p(out)), L)
     return out
+
+
+LENS_MODELS = {"radial1": _lib.SL2_LENS_RADIAL1, "brown": _lib.SL2_LENS_BROWN, "fisheye": _lib.SL2_LENS_FISHEYE}
+SL2_REMAP_BORDER = _lib.SL2_REMAP_BORDER
+
+
+def _camera_dict(c):
+    return dict(width=c.width, height=c.height, fku=c.fku, fkv=c.fkv, u0=c.u0, v0=c.v0, kd1=c.kd1, sd=c.sd)
+
+
+def make_lens(lens):
+    """dict(model, width, height, fx, fy, cx, cy[, k]) -> sl2_lens; model: "radial1" (k = [kd1]), "brown" (OpenCV's k1 k2 p1 p2 k3
+    k4 k5 k6) or "fisheye" (k1 .. k4), or SL2_LENS_*; missing coefficients are 0."""
+    if isinstance(lens, _lib.sl2_lens):
+        return lens
+    m = lens["model"]
+    k = [float(v) for v in lens.get("k", ())]
+    assert len(k) <= 8
+    return _lib.sl2_lens(LENS_MODELS[m.lower()] if isinstance(m, str) else int(m), int(lens["width"]), int(lens["height"]),
+                         float(lens["fx"]), float(lens["fy"]), float(lens["cx"]), float(lens["cy"]), (C.c_double * 8)(*(k + [0.0] * (8 - len(k)))))
+
+
+def remap_frame_host(src, xy, raw, raw_bytes=None):
+    """One sequence through the map xy (int32 [out_height][out_width][2], for a source of src's size) on the host (no GPU
+    needed): uint8 [out_height][out_width]."""
+    L = _lib.load()
+    a = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+    n = a.size if raw_bytes is None else int(raw_bytes)
+    m = np.ascontiguousarray(xy, dtype=np.int32)
+    assert m.ndim == 3 and m.shape[2] == 2, m.shape
+    out = np.zeros(m.shape[:2], np.uint8)
+    s = make_source(src)
+    _lib.check(L.sl2_remap_frame_host(C.byref(s), _lib.ip(m), a.ctypes.data_as(_lib.vp), n, m.shape[1], m.shape[0], _lib.u8p(out)), L)
+    return out
+
+
+def lens_map(lens, target):
+    """The map that reads an image the camera `target` (a dict as for Engine: the calibration the engine runs with, its width and
+    height the output size) would have seen out of the image of `lens` (make_lens): int32 [height][width][2].  Host only."""
+    L = _lib.load()
+    ln, cam = make_lens(lens), _lib.make_camera(target)
+    xy = np.zeros((max(cam.height, 0), max(cam.width, 0), 2), np.int32)
+    _lib.check(L.sl2_lens_map_host(C.byref(ln), C.byref(cam), _lib.ip(xy)), L)
+    return xy
+
+
+def pinhole_camera(lens, out_width, out_height, sd=1):
+    """The pinhole target (kd1 = 0) that sees the lens's image plane resized to out_width x out_height, as a camera dict."""
+    L = _lib.load()
+    ln = make_lens(lens)
+    out = _lib.sl2_camera()
+    _lib.check(L.sl2_lens_pinhole_camera(C.byref(ln), int(out_width), int(out_height), int(sd), C.byref(out)), L)
+    return _camera_dict(out)
 
 
 def scale_camera(cam, out_width, out_height):

@@ -8,8 +8,11 @@
 // the OUTPUT rows, which are the same for all of them.
 // k_convert_area, k_raw_linear, k_raw_area: the SL2_RESIZE_AREA sequences and those of a deep grey or Bayer format, listed on the
 // device, a launch each where there are any.
+// k_convert_remap (sl2_convert_remap.hip, a unit of its own so that this unit's device code is the same with and without it): the
+// sequences that follow a per-pixel map (the lens remap), listed likewise; a gather, nothing staged.
 #include "sl2_common.hpp"
 #include "sl2_convert_dev.hpp"
+#include "sl2_convert_remap.hpp"
 
 namespace sl2 {
 
@@ -28,6 +31,11 @@ constexpr int kConvAreaBit = 0x100;
 // ... and whether its format is a deep grey or Bayer one: k_raw_linear's or k_raw_area's sequence, by the filter
 constexpr int kConvRawBit = 0x200;
 constexpr int kConvFormatMask = 0xff;
+// ... and whether it follows a map: k_convert_remap's sequence (kConvRemapBit, sl2_convert_remap.hpp).  Such a record carries the
+// other two bits as well, whatever its filter and format: they are what keeps the four kernels of this unit off it
+// (k_convert_frames leaves a record with either bit set, the listed kernels never see a sequence that is not on their list).
+static_assert(kRemapThreads == kConvThreads && kRemapBandRows == kConvBandRows && kRemapFormatMask == kConvFormatMask &&
+              (kConvRemapBit & (kConvAreaBit | kConvRawBit | kConvFormatMask)) == 0, "sl2_convert_remap.hpp restates this unit's constants");
 
 // Bayer: the grey of a listed row needs raw rows y - 1, y, y + 1, so the raw rows are staged first (as GRAY8 rows, in dynamic LDS
 // sized by the widest Bayer source of the launch) and the grey rows are formed from them, LDS to LDS.  At most kRawSlots raw rows
@@ -542,11 +550,17 @@ struct sl2_converter {
   std::vector<int32_t> filter;           // SL2_RESIZE_* of every sequence
   std::vector<int32_t> area;             // the sequences with a source and SL2_RESIZE_AREA: k_convert_area's list
   std::vector<int32_t> raw_linear, raw_area;      // the sequences of a deep grey or Bayer format, by filter: k_raw_linear's and k_raw_area's lists
-  int32_t* d_area = nullptr;             // [nseq]: the three lists, one after the other (they share no sequence)
+  int32_t* d_area = nullptr;             // [nseq]: the three lists and the remap list, one after the other (they share no sequence)
   size_t area_lds = 0;                   // k_convert_area's dynamic LDS: a word per source column of the widest listed source
   size_t raw_area_colsum = 0;            // the same for k_raw_area ...
   int raw_linear_stage = 0, raw_area_stage = 0;      // ... and the raw stage of the two raw kernels: bytes, 0 with no Bayer source listed
   std::vector<uint32_t> taps;            // host copy of one sequence's table while it is built
+  // the lens remap: nseq map slots (d_map nullptr: empty), the slot of every sequence (-1: none), k_convert_remap's list
+  struct MapSlot { int width = 0, height = 0, xbits = 0; uint32_t* d_map = nullptr; };
+  std::vector<MapSlot> slots;
+  std::vector<int32_t> remap, remap_list;
+  RemapSlotDev* d_slots = nullptr;       // [nseq]
+  int32_t* d_remap = nullptr;            // [nseq]
   sl2_frame_source* d_src = nullptr;
   uint32_t* d_taps = nullptr;
   uint8_t* stage = nullptr;              // raw frames from host memory land here (grown on demand)
@@ -570,10 +584,15 @@ extern "C" int sl2_converter_create(int device, int nseq, int out_width, int out
   c->col_taps = round_up(out_width, 4);
   c->tap_stride = round_up(c->col_taps + out_height, 4);      // every table starts on a 16-byte boundary
   c->src.resize(nseq); c->have.assign(nseq, 0); c->taps.assign(c->tap_stride, 0); c->filter.assign(nseq, SL2_RESIZE_LINEAR);
+  c->slots.resize(nseq); c->remap.assign(nseq, -1);
   hipError_t e = hipMalloc(&c->d_src, (size_t)nseq * sizeof(sl2_frame_source));
   if (e == hipSuccess) e = hipMalloc(&c->d_area, (size_t)nseq * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc(&c->d_taps, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->d_taps, 0, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&c->d_slots, (size_t)nseq * sizeof(RemapSlotDev));
+  if (e == hipSuccess) e = hipMemset(c->d_slots, 0, (size_t)nseq * sizeof(RemapSlotDev));
+  if (e == hipSuccess) e = hipMalloc(&c->d_remap, (size_t)nseq * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemset(c->d_remap, 0xff, (size_t)nseq * sizeof(int32_t));
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
   if (e != hipSuccess) {
     set_error(std::string("sl2_converter_create: ") + hipGetErrorString(e));
@@ -593,6 +612,9 @@ extern "C" void sl2_converter_destroy(sl2_converter* c) {
   if (c->d_taps) hipFree(c->d_taps);
   if (c->d_area) hipFree(c->d_area);
   if (c->stage) hipFree(c->stage);
+  for (auto& m : c->slots) if (m.d_map) hipFree(m.d_map);
+  if (c->d_slots) hipFree(c->d_slots);
+  if (c->d_remap) hipFree(c->d_remap);
   delete c;
 }
 
@@ -610,13 +632,16 @@ static int converter_upload(sl2_converter* c, int seq0, int nseq) {
     dev.push_back(c->src[s]);
     if (c->filter[s] == SL2_RESIZE_AREA) dev.back().format |= kConvAreaBit;
     if (convert_is_raw(c->src[s].format)) dev.back().format |= kConvRawBit;
+    if (c->remap[s] >= 0) dev.back().format |= kConvRemapBit | kConvAreaBit | kConvRawBit;
   }
   if (first >= 0) SL2_HIP(hipMemcpy(c->d_src + first, dev.data(), dev.size() * sizeof(sl2_frame_source), hipMemcpyHostToDevice));
-  c->area.clear(); c->raw_linear.clear(); c->raw_area.clear();
+  if (nseq > 0) SL2_HIP(hipMemcpy(c->d_remap + seq0, c->remap.data() + seq0, (size_t)nseq * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->area.clear(); c->raw_linear.clear(); c->raw_area.clear(); c->remap_list.clear();
   int widest = 0, raw_widest = 0;
   c->raw_linear_stage = c->raw_area_stage = 0;
   for (int s = 0; s < c->nseq; ++s) {
     if (!c->have[s]) continue;
+    if (c->remap[s] >= 0) { c->remap_list.push_back(s); continue; }      // a mapped sequence is on no other list
     const sl2_frame_source& src = c->src[s];
     const bool area = c->filter[s] == SL2_RESIZE_AREA;
     if (!convert_is_raw(src.format)) {
@@ -636,6 +661,7 @@ static int converter_upload(sl2_converter* c, int seq0, int nseq) {
   std::vector<int32_t> lists(c->area);
   lists.insert(lists.end(), c->raw_linear.begin(), c->raw_linear.end());
   lists.insert(lists.end(), c->raw_area.begin(), c->raw_area.end());
+  lists.insert(lists.end(), c->remap_list.begin(), c->remap_list.end());
   if (!lists.empty()) SL2_HIP(hipMemcpy(c->d_area, lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   return SL2_OK;
 }
@@ -645,6 +671,8 @@ extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, c
   for (int i = 0; i < nseq; ++i) {
     const char* why = convert_source_fault(src[i], 0, false);
     if (!why && c->filter[seq0 + i] == SL2_RESIZE_AREA) why = convert_area_fault(src[i], c->out_w, c->out_h);
+    if (!why && c->remap[seq0 + i] >= 0 && (src[i].width != c->slots[c->remap[seq0 + i]].width || src[i].height != c->slots[c->remap[seq0 + i]].height))
+      why = "its map is for another source size";
     if (why) { set_error("sl2_converter_set_sources: " + seq_text(seq0 + i, why)); return SL2_ERR_INVALID; }
   }
   if (nseq == 0) return SL2_OK;
@@ -724,7 +752,7 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
   A.out_w = c->out_w; A.out_h = c->out_h; A.col_taps = c->col_taps; A.tap_stride = c->tap_stride;
   A.bands = (c->out_h + kConvBandRows - 1) / kConvBandRows;
   // a kernel per (format family, filter) that has a sequence: one launch for the reference's webcam, four at most
-  const int listed = (int)(c->area.size() + c->raw_linear.size() + c->raw_area.size());
+  const int listed = (int)(c->area.size() + c->raw_linear.size() + c->raw_area.size() + c->remap_list.size());
   if (listed < c->nseq) hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
   AreaArgs B;
   B.src = c->d_src; B.list = c->d_area; B.raw = d_raw; B.out = d_frames; B.seq_stride = seq_stride;
@@ -738,6 +766,12 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
     B.list = c->d_area + c->area.size() + c->raw_linear.size();
     hipLaunchKernelGGL(k_raw_area, dim3((unsigned)(B.bands * (int)c->raw_area.size())), dim3(kConvThreads),
                        c->raw_area_colsum + (size_t)c->raw_area_stage, st, B, (int)c->raw_area_colsum, c->raw_area_stage);
+  }
+  if (!c->remap_list.empty()) {
+    RemapArgs R;
+    R.src = c->d_src; R.list = c->d_area + c->area.size() + c->raw_linear.size() + c->raw_area.size(); R.slot_of = c->d_remap; R.slots = c->d_slots;
+    R.raw = d_raw; R.out = d_frames; R.seq_stride = seq_stride; R.out_w = c->out_w; R.out_h = c->out_h; R.bands = A.bands;
+    convert_remap_launch(R, (int)c->remap_list.size(), st);
   }
   SL2_HIP(hipGetLastError());
   SL2_HIP(hipEventRecord(c->done, st));
@@ -791,6 +825,136 @@ extern "C" int sl2_scale_camera(const sl2_camera* in, int out_width, int out_hei
   r.fku = in->fku / s; r.fkv = in->fkv / s;
   r.u0 = (in->u0 + 0.5) / s - 0.5; r.v0 = (in->v0 + 0.5) / s - 0.5;
   r.kd1 = in->kd1 * s * s;
+  *out = r;
+  return SL2_OK;
+}
+
+// ---- the lens remap
+
+// The first sequence that follows `slot`, -1: none
+static int converter_slot_user(const sl2_converter* c, int slot) {
+  for (int s = 0; s < c->nseq; ++s) if (c->remap[s] == slot) return s;
+  return -1;
+}
+
+extern "C" int sl2_converter_set_map(sl2_converter* c, int slot, int src_width, int src_height, const int32_t* xy) {
+  if (!c) { set_error("sl2_converter_set_map: bad arguments"); return SL2_ERR_INVALID; }
+  if (slot < 0 || slot >= c->nseq) { set_error("sl2_converter_set_map: slot outside 0 .. nseq - 1"); return SL2_ERR_INVALID; }
+  sl2_converter::MapSlot& m = c->slots[slot];
+  const int user = converter_slot_user(c, slot);
+  if (!xy) {
+    if (user >= 0) { set_error("sl2_converter_set_map: " + seq_text(user, "still uses the slot that would be emptied")); return SL2_ERR_INVALID; }
+  } else {
+    if (src_width < 1 || src_height < 1 || src_width > kConvertMaxWidth || src_height > kConvertMaxHeight) {
+      set_error("sl2_converter_set_map: a source size of 1 .. 4096 by 1 .. 16384 is required");
+      return SL2_ERR_INVALID;
+    }
+    if (user >= 0 && (src_width != m.width || src_height != m.height)) {
+      set_error("sl2_converter_set_map: " + seq_text(user, "still uses the slot, whose source size would change"));
+      return SL2_ERR_INVALID;
+    }
+  }
+  SL2_HIP(hipSetDevice(c->device));
+  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its map
+  RemapSlotDev dev = {nullptr, 0, 0, 0, 0};
+  if (!xy) {
+    if (m.d_map) { SL2_HIP(hipFree(m.d_map)); }
+    m = sl2_converter::MapSlot();
+  } else {
+    // the device form: entries that reach no source pixel become the border, the rest one word each where the size allows
+    const size_t n = (size_t)c->out_w * (size_t)c->out_h;
+    const int xbits = remap_packed_xbits(src_width, src_height);
+    std::vector<uint32_t> words(xbits ? n : 2 * n);
+    for (size_t i = 0; i < n; ++i) {
+      const int32_t X = xy[2 * i], Y = xy[2 * i + 1];
+      const bool live = remap_reaches(src_width, src_height, X, Y);
+      if (xbits) words[i] = live ? remap_pack(xbits, X, Y) : kRemapBorderWord;
+      else { words[2 * i] = (uint32_t)(live ? X : SL2_REMAP_BORDER); words[2 * i + 1] = live ? (uint32_t)Y : 0u; }
+    }
+    uint32_t* d_new = nullptr;
+    SL2_HIP(hipMalloc(&d_new, words.size() * sizeof(uint32_t)));
+    hipError_t e = hipMemcpy(d_new, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(d_new); set_error(std::string("sl2_converter_set_map: ") + hipGetErrorString(e)); return SL2_ERR_HIP; }
+    if (m.d_map) { SL2_HIP(hipFree(m.d_map)); }
+    m.d_map = d_new; m.width = src_width; m.height = src_height; m.xbits = xbits;
+    dev.map = d_new; dev.width = src_width; dev.height = src_height; dev.xbits = xbits;
+  }
+  SL2_HIP(hipMemcpy(c->d_slots + slot, &dev, sizeof(dev), hipMemcpyHostToDevice));
+  return SL2_OK;
+}
+
+extern "C" int sl2_converter_set_remaps(sl2_converter* c, int seq0, int nseq, const int32_t* slots) {
+  if (!c || !slots) { set_error("sl2_converter_set_remaps: bad arguments"); return SL2_ERR_INVALID; }
+  if (seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) {
+    set_error("sl2_converter_set_remaps: " + seq_text(seq0 < 0 ? seq0 : c->nseq, "outside the converter"));
+    return SL2_ERR_INVALID;
+  }
+  for (int i = 0; i < nseq; ++i) {
+    const char* why = nullptr;
+    const int k = slots[i];
+    if (k < -1 || k >= c->nseq) why = "slot outside -1 .. nseq - 1";
+    else if (k >= 0 && !c->slots[k].d_map) why = "its map slot is empty";
+    else if (k >= 0 && c->have[seq0 + i] && (c->src[seq0 + i].width != c->slots[k].width || c->src[seq0 + i].height != c->slots[k].height))
+      why = "its source has another size than the map's";
+    if (why) { set_error("sl2_converter_set_remaps: " + seq_text(seq0 + i, why)); return SL2_ERR_INVALID; }
+  }
+  if (nseq == 0) return SL2_OK;
+  SL2_HIP(hipSetDevice(c->device));
+  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its lists
+  for (int i = 0; i < nseq; ++i) c->remap[seq0 + i] = slots[i];
+  return converter_upload(c, seq0, nseq);
+}
+
+extern "C" int sl2_converter_get_remaps(const sl2_converter* c, int seq0, int nseq, int32_t* slots) {
+  if (!c || !slots || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_get_remaps: bad arguments"); return SL2_ERR_INVALID; }
+  for (int i = 0; i < nseq; ++i) slots[i] = c->remap[seq0 + i];
+  return SL2_OK;
+}
+
+extern "C" int sl2_remap_frame_host(const sl2_frame_source* src, const int32_t* xy, const void* raw, size_t raw_bytes, int out_width,
+                                    int out_height, uint8_t* out) {
+  if (!src || !xy || !raw || !out || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+    set_error("sl2_remap_frame_host: bad arguments");
+    return SL2_ERR_INVALID;
+  }
+  const char* why = convert_source_fault(*src, raw_bytes, true);
+  if (why) { set_error("sl2_remap_frame_host: " + seq_text(0, why)); return SL2_ERR_INVALID; }
+  remap_frame_host_body(*src, xy, (const uint8_t*)raw, out_width, out_height, out);
+  return SL2_OK;
+}
+
+static const char* lens_fault(const sl2_lens& l) {
+  if (l.model != SL2_LENS_RADIAL1 && l.model != SL2_LENS_BROWN && l.model != SL2_LENS_FISHEYE) return "unknown lens model";
+  if (l.width < 1 || l.height < 1 || l.width > kConvertMaxWidth || l.height > kConvertMaxHeight) return "a lens image of 1 .. 4096 by 1 .. 16384 is required";
+  return nullptr;
+}
+
+extern "C" int sl2_lens_map_host(const sl2_lens* lens, const sl2_camera* target, int32_t* xy) {
+  if (!lens || !target || !xy) { set_error("sl2_lens_map_host: bad arguments"); return SL2_ERR_INVALID; }
+  const char* why = lens_fault(*lens);
+  if (!why && (target->width < 1 || target->height < 1 || target->width > kConvertMaxOut || target->height > kConvertMaxOut))
+    why = "a target size of 1 .. 4096 per axis is required";
+  if (why) { set_error(std::string("sl2_lens_map_host: ") + why); return SL2_ERR_INVALID; }
+  for (int y = 0; y < target->height; ++y)
+    for (int x = 0; x < target->width; ++x) {
+      int32_t* e = xy + 2 * ((size_t)y * target->width + x);
+      lens_map_entry(*lens, *target, x, y, &e[0], &e[1]);
+    }
+  return SL2_OK;
+}
+
+extern "C" int sl2_lens_pinhole_camera(const sl2_lens* lens, int out_width, int out_height, int sd, sl2_camera* out) {
+  if (!lens || !out) { set_error("sl2_lens_pinhole_camera: bad arguments"); return SL2_ERR_INVALID; }
+  const char* why = lens_fault(*lens);
+  if (!why && (out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut)) why = "an output size of 1 .. 4096 per axis is required";
+  if (why) { set_error(std::string("sl2_lens_pinhole_camera: ") + why); return SL2_ERR_INVALID; }
+  sl2_camera r;
+  r.width = out_width; r.height = out_height;
+  r.fku = lens->fx * (double)out_width / (double)lens->width;
+  r.fkv = lens->fy * (double)out_height / (double)lens->height;
+  r.u0 = (lens->cx + 0.5) * (double)out_width / (double)lens->width - 0.5;
+  r.v0 = (lens->cy + 0.5) * (double)out_height / (double)lens->height - 0.5;
+  r.kd1 = 0.0; r.sd = sd;
   *out = r;
   return SL2_OK;
 }

@@ -228,4 +228,156 @@ inline void convert_frame_host_area_body(const sl2_frame_source& s, const uint8_
   }
 }
 
+// ---- The lens remap (scenelib2_amd.h, "the lens remap"): a sequence follows a per-pixel map into its source's grey plane, the
+// equivalent of cv::remap over cv::initUndistortRectifyMap's map.  A map belongs to a source size W x H and to the output size:
+// int32 xy[out_h][out_w][2], (X, Y) the position in the source grey plane in 1/32 of a source pixel, pixel centres on integers
+// (X = 32 x is column x: rectify_source's convention), X == SL2_REMAP_BORDER meaning no source.  Per output pixel, in 32-bit
+// integers: a border entry gives 0; else fx = X & 31, ix = (X - fx) / 32 (two's complement: the floor), fy and iy likewise; a
+// tap is g[iy][ix] where 0 <= ix < W and 0 <= iy < H, else 0, g being convert_grey_at's grey of the source's format (for Bayer
+// the demosaic, the neighbours of an in-image tap reflected as everywhere); a neighbour whose weight is 0 is not read;
+//   out = ((32 - fx)(32 - fy) p00 + fx (32 - fy) p10 + (32 - fx) fy p01 + fx fy p11 + 512) >> 10.
+// rectify_pixel's arithmetic (sl2_rectify_dev.hpp) over convert_grey_at: the identity for the identity map, a constant source
+// stays constant wherever all four taps lie inside.  NO anti-aliasing: two taps an axis whatever the map's local scale, so a map
+// that reduces by much more than two aliases like SL2_RESIZE_LINEAR.
+//
+// remap_pixel is that rule without a branch, because on the device a branch around a load is a round trip to memory that the
+// next load waits for: a tap that does not count - outside the image, a neighbour of weight 0, any tap of a border entry (ix =
+// -2^26: none is inside) - gets the weight 0, and the byte fetched for it comes from the clamped, in-image coordinate and is
+// discarded.  So "is not read" holds in the sense that matters: nothing outside the W x H source is ever addressed, whatever the
+// entry.  Bayer: the 3 x 3 neighbourhoods of the four taps overlap in a 4 x 4 block, columns reflect(ix - 1 + j) and rows
+// reflect(iy - 1 + i) (clamped where the tap they serve is itself outside): sixteen bytes instead of thirty-six, and for an
+// in-image tap exactly the bytes convert_grey_at names.
+SL2_HD int remap_clamp(int i, int S) { return i < 0 ? 0 : i >= S ? S - 1 : i; }
+
+SL2_HD uint8_t remap_pixel(int format, const uint8_t* base, int pitch, int W, int H, int32_t X, int32_t Y) {
+  const int fx = X & 31, fy = Y & 31;
+  const int ix = (X - fx) / 32, iy = (Y - fy) / 32;      // X - fx is a multiple of 32 and no smaller than INT32_MIN
+  const bool cx0 = ix >= 0 && ix < W, cx1 = fx != 0 && ix + 1 >= 0 && ix + 1 < W;
+  const bool cy0 = iy >= 0 && iy < H, cy1 = fy != 0 && iy + 1 >= 0 && iy + 1 < H;
+  const int w00 = cx0 && cy0 ? (32 - fx) * (32 - fy) : 0, w10 = cx1 && cy0 ? fx * (32 - fy) : 0;
+  const int w01 = cx0 && cy1 ? (32 - fx) * fy : 0, w11 = cx1 && cy1 ? fx * fy : 0;
+  int p00, p10, p01, p11;
+  if (!convert_is_bayer(format)) {
+    const int x0 = remap_clamp(ix, W), x1 = remap_clamp(ix + 1, W);
+    const uint8_t* r0 = base + (size_t)remap_clamp(iy, H) * (size_t)pitch;
+    const uint8_t* r1 = base + (size_t)remap_clamp(iy + 1, H) * (size_t)pitch;
+    p00 = convert_grey(format, r0, x0); p10 = convert_grey(format, r0, x1);
+    p01 = convert_grey(format, r1, x0); p11 = convert_grey(format, r1, x1);
+  } else {
+    int p[4][4];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 4; ++i) {
+      const uint8_t* row = base + (size_t)remap_clamp(convert_reflect(iy - 1 + i, H), H) * (size_t)pitch;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int j = 0; j < 4; ++j) p[i][j] = row[remap_clamp(convert_reflect(ix - 1 + j, W), W)];
+    }
+    // the tap at column ix + a, row iy + b has its centre at p[b + 1][a + 1]
+#define SL2_REMAP_BAYER(a, b)                                                                                        \
+  convert_bayer_grey(format, p[b + 1][a + 1], p[b + 1][a] + p[b + 1][a + 2], p[b][a + 1] + p[b + 2][a + 1],          \
+                     p[b][a] + p[b][a + 2] + p[b + 2][a] + p[b + 2][a + 2], ix + a, iy + b)
+    p00 = SL2_REMAP_BAYER(0, 0); p10 = SL2_REMAP_BAYER(1, 0); p01 = SL2_REMAP_BAYER(0, 1); p11 = SL2_REMAP_BAYER(1, 1);
+#undef SL2_REMAP_BAYER
+  }
+  return (uint8_t)((w00 * p00 + w10 * p10 + w01 * p01 + w11 * p11 + 512) >> 10);
+}
+
+// Whether an entry can reach a source pixel with a weight above 0: columns ix (always weighed) and ix + 1 (where fx != 0), rows likewise
+SL2_HD bool remap_reaches(int W, int H, int32_t X, int32_t Y) {
+  if (X == SL2_REMAP_BORDER) return false;
+  const int fx = X & 31, fy = Y & 31;
+  const int ix = (X - fx) / 32, iy = (Y - fy) / 32;
+  const bool col = (ix >= 0 && ix < W) || (fx && ix == -1), row = (iy >= 0 && iy < H) || (fy && iy == -1);
+  return col && row;
+}
+
+// The device form of a map ("the lens remap").  sl2_converter_set_map turns every entry that reaches no
+// source pixel into the border, so a live entry has X + 32 in 1 .. 32 (W + 1) - 1 and Y + 32 in 1 .. 32 (H + 1) - 1.  Where the
+// bits of those two ranges sum to 32 or less - every source up to 2046 x 2046, 4096 x 511 ... - an entry is ONE word, X + 32 in
+// the low xbits bits and Y + 32 above them, the border all ones (never a live entry's word: checked when the form is chosen).  Else it is two words,
+// X and Y as they are: 38 bits at the caps.
+constexpr uint32_t kRemapBorderWord = 0xffffffffu;
+SL2_HD int remap_bits(int S) { int b = 0; while (((32u * ((uint32_t)S + 1u) - 1u) >> b) != 0u) ++b; return b; }
+// xbits of the one-word form, 0: the source needs the two-word form
+SL2_HD int remap_packed_xbits(int W, int H) {
+  const int bx = remap_bits(W), by = remap_bits(H);
+  if (bx + by > 32) return 0;
+  const uint32_t top = ((32u * ((uint32_t)H + 1u) - 1u) << bx) | (32u * ((uint32_t)W + 1u) - 1u);      // the largest live word
+  return top == kRemapBorderWord ? 0 : bx;
+}
+SL2_HD uint32_t remap_pack(int xbits, int32_t X, int32_t Y) { return (uint32_t)(X + 32) | ((uint32_t)(Y + 32) << xbits); }
+SL2_HD void remap_unpack(int xbits, uint32_t w, int32_t* X, int32_t* Y) {
+  if (w == kRemapBorderWord) { *X = SL2_REMAP_BORDER; *Y = 0; return; }
+  *X = (int32_t)(w & ((1u << xbits) - 1u)) - 32;
+  *Y = (int32_t)(w >> xbits) - 32;
+}
+
+// The host form's body: one source through the map xy[out_h][out_w][2] into out[out_h][out_w]
+inline void remap_frame_host_body(const sl2_frame_source& s, const int32_t* xy, const uint8_t* raw, int out_w, int out_h, uint8_t* out) {
+  const uint8_t* base = raw + s.offset;
+  for (size_t i = 0; i < (size_t)out_w * (size_t)out_h; ++i)
+    out[i] = remap_pixel(s.format, base, s.pitch, s.width, s.height, xy[2 * i], xy[2 * i + 1]);
+}
+
+// ---- Maps from calibrations (scenelib2_amd.h, "maps from calibrations"): host only, FP64, -ffp-contract=off.  Every line is
+// the header's, in its order of operations.
+constexpr double kLensSourceMax = 1048576.0;      // a source position beyond +-2^20 is the border (so that 32 us fits an int)
+
+// Image-plane coordinates (a, b) of target pixel (x, y): x to the right, y down (OpenCV's x', y').  False: the border.
+inline bool lens_target_ray(const sl2_camera& t, int x, int y, double* a, double* b) {
+  const double cx = (double)x - t.u0, cy = (double)y - t.v0;
+  const double f = 1.0 - (2.0 * t.kd1) * (cx * cx + cy * cy);
+  if (!(f > 0.0)) return false;
+  const double s = sqrt(f);
+  *a = (cx / s) / t.fku;
+  *b = (cy / s) / t.fkv;
+  return true;
+}
+
+// Where the lens images (a, b): the source position in pixels.  False: the border.
+inline bool lens_project(const sl2_lens& l, double a, double b, double* us, double* vs) {
+  const double* k = l.k;
+  if (l.model == SL2_LENS_RADIAL1) {
+    const double px = l.fx * a, py = l.fy * b;
+    const double q = 1.0 + (2.0 * k[0]) * (px * px + py * py);
+    if (!(q > 0.0)) return false;
+    const double s = sqrt(q);
+    *us = px / s + l.cx; *vs = py / s + l.cy;
+    return true;
+  }
+  if (l.model == SL2_LENS_BROWN) {
+    const double r2 = a * a + b * b, r4 = r2 * r2, r6 = r4 * r2;
+    const double num = ((1.0 + k[0] * r2) + k[1] * r4) + k[4] * r6;
+    const double den = ((1.0 + k[5] * r2) + k[6] * r4) + k[7] * r6;
+    if (den == 0.0) return false;
+    const double rad = num / den, ab = a * b;
+    const double xd = (a * rad + (2.0 * k[2]) * ab) + k[3] * (r2 + 2.0 * (a * a));
+    const double yd = (b * rad + k[2] * (r2 + 2.0 * (b * b))) + (2.0 * k[3]) * ab;
+    *us = l.fx * xd + l.cx; *vs = l.fy * yd + l.cy;
+    return true;
+  }
+  // SL2_LENS_FISHEYE
+  const double r = sqrt(a * a + b * b);
+  if (r == 0.0) { *us = l.cx; *vs = l.cy; return true; }
+  const double th = atan(r);
+  const double t2 = th * th, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+  const double thd = th * ((((1.0 + k[0] * t2) + k[1] * t4) + k[2] * t6) + k[3] * t8);
+  const double sc = thd / r;
+  *us = l.fx * (a * sc) + l.cx; *vs = l.fy * (b * sc) + l.cy;
+  return true;
+}
+
+inline void lens_map_entry(const sl2_lens& l, const sl2_camera& t, int x, int y, int32_t* X, int32_t* Y) {
+  double a, b, us, vs;
+  *X = SL2_REMAP_BORDER; *Y = 0;
+  if (!lens_target_ray(t, x, y, &a, &b) || !lens_project(l, a, b, &us, &vs)) return;
+  // (a NaN or an infinity fails one of the four comparisons)
+  if (!(us >= -kLensSourceMax && us <= kLensSourceMax && vs >= -kLensSourceMax && vs <= kLensSourceMax)) return;
+  *X = (int32_t)floor(us * 32.0 + 0.5);
+  *Y = (int32_t)floor(vs * 32.0 + 0.5);
+}
+
 }  // namespace sl2

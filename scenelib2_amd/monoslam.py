@@ -836,12 +836,33 @@ class MonoSLAM:
         """What the camera delivers (UsbCamGrabber, usbcamgrabber.cpp:75-113): its size, row pitch in bytes and pixel format
         (convert.SL2_PIX_* or a name of convert.FORMATS: "uyvy", "rgb24", "gray12", "bayer_rggb8" ...).  GoOneStepRaw converts such frames to the engine's grey image on the
         device.  The converter and the device frame are created on the first call."""
+        self._ensure_converter()
+        self._converter.set_sources([dict(width=width, height=height, pitch=pitch, format=format)])
+
+    def _ensure_converter(self):
         from . import convert
         if self._converter is None:
             self._converter = convert.FrameConverter(self._device, 1, self.camera_["width"], self.camera_["height"])
             self._frame_dev = _lib.DeviceBuffer(self._engine.frame_bytes, self._device)
             self._converter.set_filters([self._frame_filter])
-        self._converter.set_sources([dict(width=width, height=height, pitch=pitch, format=format)])
+
+    def SetLens(self, lens, target):
+        """A camera whose lens the filter's model does not describe (OpenCV's k1 k2 p1 p2 k3 [k4 k5 k6], or its fisheye k1 .. k4):
+        GoOneStepRaw then reads every frame through the map from `target` into the lens's image (convert.lens_map), in place of
+        the resize filter, and the filter runs with `target` (SetCameraParameters).  lens: a dict as for convert.make_lens; target:
+        a camera dict of the engine's image size (convert.pinhole_camera gives the obvious one; a target with kd1 > 0 keeps more of
+        a wide lens's field).  Before or after SetFrameSource, whose size must be the lens's."""
+        from . import convert
+        if (int(target["width"]), int(target["height"])) != (self.camera_["width"], self.camera_["height"]):
+            raise ValueError("MonoSLAM.SetLens: the target's size is not the engine's image size")
+        ln = convert.make_lens(lens)
+        xy = convert.lens_map(ln, target)
+        self._ensure_converter()
+        self._converter.set_remaps([-1])                    # (a slot in use keeps its size)
+        self._converter.set_map(0, ln.width, ln.height, xy)
+        self._converter.set_remaps([0])
+        self.SetCameraParameters(target["width"], target["height"], target["fku"], target["fkv"], target["u0"], target["v0"],
+                                 target["kd1"], target["sd"])
 
     def SetFrameFilter(self, filter):
         """How GoOneStepRaw brings the camera's frame to the engine's size: "linear" (the reference's plain INTER_LINEAR, the
