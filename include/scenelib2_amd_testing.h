@@ -32,6 +32,11 @@ int sl2_debug_graph_captures(sl2_engine* e);
  * the product library it differs where a step has no product form - which no engine the product library creates reaches.) */
 int sl2_debug_update_plan(sl2_engine* e, int group, int* out, int n);
 
+/* The covariance of one sequence as the kernels hold it: P [ld][ld] with ld = *ld (the state columns rounded up to 64), the
+ * padding rows and columns and the columns of never-used slots included - what sl2_get_total_covariance leaves out.
+ * capacity_ld: rows and columns of room in P; too few: SL2_ERR_CAPACITY with *ld set.  Synchronises. */
+int sl2_debug_raw_covariance(sl2_engine* e, int seq, double* P, int capacity_ld, int* ld);
+
 /* FP64 epilogue of correlate2_warning (improc.cpp:99-133) evaluated ON THE DEVICE
  * for `count` tuples of the five integer sums: checks IEEE div/sqrt parity. */
 int sl2_debug_ncc_score(int device, const int32_t* sums5, int count, double* score, double* sd0, double* sd1);

@@ -185,7 +185,7 @@ EXPORTED_SYMBOLS = [
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures",
-                "sl2_debug_update_plan"]
+                "sl2_debug_update_plan", "sl2_debug_raw_covariance"]
 TEST_LIB_PATH = os.path.join(_HERE, "libscenelib2_amd_test.so")
 _testlib = None
 
@@ -377,6 +377,7 @@ def load_testing():
     T.sl2_debug_microbench.argtypes = [C.c_int, C.c_int, c_dp]
     T.sl2_debug_graph_captures.argtypes = [vp]
     T.sl2_debug_update_plan.argtypes = [vp, C.c_int, c_ip, C.c_int]
+    T.sl2_debug_raw_covariance.argtypes = [vp, C.c_int, c_dp, C.c_int, c_ip]
     _testlib = T
     return T
 

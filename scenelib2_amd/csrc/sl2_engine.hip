@@ -1442,6 +1442,17 @@ int sl2_get_position_log(sl2_engine* e, int seq0, int nseq, double* out, int cap
 #ifdef SL2_TESTING   // test hook: libscenelib2_amd_test.so only (include/scenelib2_amd_testing.h)
 int sl2_debug_graph_captures(sl2_engine* e) { return e ? (int)e->graph_captures : -1; }
 
+// One sequence's covariance as the kernels hold it: all ld rows of ld doubles, padding and never-used slots included.
+int sl2_debug_raw_covariance(sl2_engine* e, int seq, double* P, int capacity_ld, int* ld) {
+  if (!range_ok(e, seq, 1) || !P || !ld) return SL2_ERR_INVALID;
+  *ld = e->ld;
+  if (e->ld > capacity_ld) return SL2_ERR_CAPACITY;
+  SL2_HIP(hipSetDevice(e->device));
+  { int _rc = e->sync_all(); if (_rc != SL2_OK) return _rc; }
+  SL2_HIP(hipMemcpy(P, e->P + (size_t)seq * e->ld * e->ld, sizeof(double) * e->ld * e->ld, hipMemcpyDeviceToHost));
+  return SL2_OK;
+}
+
 int sl2_set_feature_counters(sl2_engine* e, int seq, int label, int attempted, int successful) {
   if (!range_ok(e, seq, 1) || label < 0) return SL2_ERR_INVALID;
   SL2_HIP(hipSetDevice(e->device));

@@ -1,5 +1,5 @@
 // EKF update, first phase: A = P H^T and S = H A + R in one pass (the algebra and the k-major storage: sl2_ekf_update.hip).
-#include "sl2_common.hpp"
+#include "sl2_update_dev.hpp"
 
 namespace sl2 {
 
@@ -146,6 +146,8 @@ __global__ void __launch_bounds__(1024) k_build_AS(const double* __restrict__ P,
 //     nine to twelve rows per thread are in flight all the time, the waits are counted (vmcnt(N), never 0 in the loop) and the
 //     S phase runs under the next batch's loads.  The body of a full batch with a full batch behind it has no branch; the last
 //     full batch, the partial batch and the padding rows are tails of their own.
+// The rows of P are read once and At is next read by another launch: both are streaming accesses (load_stream / store_stream);
+// the stores of S stay plain, the Cholesky reads them next (profiles/update_streams_ab.json).
 // Same grid, same roles, and every entry of At and St is the expression of k_build_AS term by term (bit-identical:
 // tests/test_gpu_build_as_ahead.py).
 // Registers: 80, no spills - six wavefronts per SIMD, as k_build_AS.  Measured (HISTORY section 8, profiles/build_as_ahead_ab.json):
@@ -185,7 +187,7 @@ __device__ __forceinline__ void ahead_load(AheadRows<BATCH>& w, const double* __
     if (FULL || jj < nb) {
       const int pos = __builtin_amdgcn_readfirstlane(ahead_pos(tab + (j0 + jj) * kAheadEntry));   // (uniform: a scalar row base)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) w.v[jj][c] = *ahead_at(Pb + (size_t)(pos + c) * ld, t);
+      for (int c = 0; c < 3; ++c) w.v[jj][c] = load_stream(ahead_at(Pb + (size_t)(pos + c) * ld, t));
     }
   }
 }
@@ -210,13 +212,13 @@ __device__ __forceinline__ void ahead_rows(AheadRows<BATCH>& w, const double (&p
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc += w.v[jj][c] * ahead_lane(en, 14 + r * 3 + c);
         if (t == ld - 1) acc = ahead_lane(en, 20 + r);
-        *ahead_at(Ab + (size_t)(2 * (j0 + jj) + r) * ld, t) = acc;
+        store_stream(ahead_at(Ab + (size_t)(2 * (j0 + jj) + r) * ld, t), acc);
         sAt[(2 * jj + r) * ld + t] = acc;
       }
       if (REFILL && jj < BATCH - 1) {      // (the last feature's registers are refilled behind the S phase: ahead_refill_last)
         const int pos = __builtin_amdgcn_readfirstlane(ahead_pos(tab + (j0 + BATCH + jj) * kAheadEntry));
 #pragma unroll
-        for (int c = 0; c < 3; ++c) w.v[jj][c] = *ahead_at(Pb + (size_t)(pos + c) * ld, t);
+        for (int c = 0; c < 3; ++c) w.v[jj][c] = load_stream(ahead_at(Pb + (size_t)(pos + c) * ld, t));
       }
     }
   }
@@ -228,7 +230,7 @@ template <int BATCH>
 __device__ __forceinline__ void ahead_refill_last(AheadRows<BATCH>& w, const double* tab, const double* __restrict__ Pb, int j0, int ld, int t) {
   const int pos = __builtin_amdgcn_readfirstlane(ahead_pos(tab + (j0 + 2 * BATCH - 1) * kAheadEntry));
 #pragma unroll
-  for (int c = 0; c < 3; ++c) w.v[BATCH - 1][c] = *ahead_at(Pb + (size_t)(pos + c) * ld, t);
+  for (int c = 0; c < 3; ++c) w.v[BATCH - 1][c] = load_stream(ahead_at(Pb + (size_t)(pos + c) * ld, t));
 }
 
 // columns 2 j0 .. 2 (j0 + nb) - 1 of S from the LDS batch (between the two barriers of a batch)
@@ -309,7 +311,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6, 8)
   // role "column t of At"
   double pc[7];
 #pragma unroll
-  for (int c = 0; c < 7; ++c) pc[c] = (t < 13) ? Pb[(size_t)t * ld + c] : Pb[(size_t)c * ld + t];
+  for (int c = 0; c < 7; ++c) pc[c] = load_stream((t < 13) ? &Pb[(size_t)t * ld + c] : &Pb[(size_t)c * ld + t]);
   __syncthreads();
   const int nfull = cnt / BATCH, rem = cnt - nfull * BATCH;
   AheadRows<BATCH> w;
@@ -331,7 +333,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6, 8)
   }
   // padding: rows of At up to the 32-multiple are zero, S is the identity there
   for (int k = m; k < mp; ++k) {
-    Ab[(size_t)k * ld + t] = 0.0;
+    store_stream(&Ab[(size_t)k * ld + t], 0.0);
     if (t < mp && (t | 31) >= k) Sb[(size_t)k * mld + t] = (t == k) ? 1.0 : 0.0;
   }
 }

@@ -1,5 +1,6 @@
-// Device helpers of the dense EKF update that more than one of its translation units uses (sl2_update_chol.hip,
-// sl2_update_fwdsub.hip, sl2_update_syrk.hip, sl2_update_testing.hip).  A helper with one user lives with that user.
+// Device helpers of the dense EKF update that more than one of its translation units uses (sl2_update_build.hip,
+// sl2_update_chol.hip, sl2_update_fwdsub.hip, sl2_update_syrk.hip, sl2_update_testing.hip).  A helper with one user lives with
+// that user.
 #pragma once
 #include "sl2_common.hpp"
 
@@ -10,6 +11,15 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4d mfma_f64(double a, double b, v4d c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
+
+// Streaming accesses (the `nt` bit of global_load / global_store): for operands a kernel touches exactly once, beside the ones
+// that are re-read (S / L, the V^T panels).  A hint only: no arithmetic and no ordering changes; what it gains is measured site
+// by site (profiles/update_streams_ab.json: the bytes the counters see do not change, the time does).  Any pointer to double or to an ext_vector_type of 2 or 4 doubles (v4d; the HIP double2 / double4 structs are not
+// accepted by the builtins), in any address space.  The policy per stream: DESIGN section 4.
+template <class Ptr>
+__device__ __forceinline__ auto load_stream(Ptr p) { return __builtin_nontemporal_load(p); }
+template <class Ptr, class T>
+__device__ __forceinline__ void store_stream(Ptr p, T v) { __builtin_nontemporal_store(v, p); }
 
 constexpr int kSyrkKC = 16;       // K rows per chunk (k_syrk, k_fwd_gemm, k_chol_syrk)
 

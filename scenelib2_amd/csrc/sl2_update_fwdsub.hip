@@ -58,13 +58,23 @@ __global__ void __launch_bounds__(256, (NB <= 8 ? 3 : 2)) k_fwdsub_lds(const dou
 #define SL2_TILE_PTR(Jv, Kv) \
   (((Kv) < (Jv)) ? (Sb + (size_t)((Kv) * 32 + srow) * mld + (Jv) * 32 + sc4) : (Lb + (size_t)(Jv) * 1024 + srow * 32 + sc4))
   double4 pre = *(const double4*)SL2_TILE_PTR(0, 0);
+  // In the EKF substitution At is read once and Vt is next read by another launch: both are streaming accesses (load_stream /
+  // store_stream).  Measured at NB = 7, medians of five alternated processes (profiles/update_streams_ab.json): 0.306-0.314 ms
+  // against 0.328 with plain accesses; the loads alone 0.323, the stores alone 0.325 - it takes both.  The panel solve runs in
+  // place on the factor, which the following launches re-read, and must stay plain.  The kernel has one symbol per NB whoever
+  // launches it (tests/test_update_units.py), so the instantiations launch_panel_solve names are plain for the EKF substitution
+  // as well.  (A run-time choice between the two uses compiles to plain accesses; both bodies in one kernel cost <8> twenty more
+  // spilled registers and <13> forty.)
+  constexpr bool kStream = (NB != 8 && NB != kCholPanelBlocks);
+  auto load_at = [](const double* p) { if constexpr (kStream) return load_stream(p); else return *p; };
+  auto store_vt = [](double* p, double v) { if constexpr (kStream) store_stream(p, v); else *p = v; };
   v4d V[NB][2];
   v4d at[2];
   const bool half0 = (16 >= m);
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) at[jt][r] = (jt == 1 && half0) ? 0.0 : Ab[(size_t)(16 * jt + hi + 4 * r) * ld + i0 + lo];
+    for (int r = 0; r < 4; ++r) at[jt][r] = (jt == 1 && half0) ? 0.0 : load_at(&Ab[(size_t)(16 * jt + hi + 4 * r) * ld + i0 + lo]);
   int t = 0;   // running tile counter (buffer parity)
 #pragma unroll
   for (int J = 0; J < NB; ++J) {
@@ -100,7 +110,7 @@ __global__ void __launch_bounds__(256, (NB <= 8 ? 3 : 2)) k_fwdsub_lds(const dou
             for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
               for (int r = 0; r < 4; ++r)
-                at[jt][r] = (jt == 1 && halfn) ? 0.0 : Ab[(size_t)((J + 1) * 32 + 16 * jt + hi + 4 * r) * ld + i0 + lo];
+                at[jt][r] = (jt == 1 && halfn) ? 0.0 : load_at(&Ab[(size_t)((J + 1) * 32 + 16 * jt + hi + 4 * r) * ld + i0 + lo]);
           }
           v4d out[2];
           out[0] = (v4d){0, 0, 0, 0};
@@ -117,7 +127,7 @@ __global__ void __launch_bounds__(256, (NB <= 8 ? 3 : 2)) k_fwdsub_lds(const dou
           for (int jt = 0; jt < 2; ++jt) {
             if (jt == 1 && half) continue;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Vb[(size_t)(J * 32 + 16 * jt + hi + 4 * r) * ld + i0 + lo] = out[jt][r];
+            for (int r = 0; r < 4; ++r) store_vt(&Vb[(size_t)(J * 32 + 16 * jt + hi + 4 * r) * ld + i0 + lo], out[jt][r]);
           }
         }
         ++t;

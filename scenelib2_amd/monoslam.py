@@ -581,6 +581,17 @@ class Engine:
         p.update(build=self.BUILD_FORMS[p["build"]], chol=self.CHOL_FORMS[p["chol"]], fwd=self.FWD_FORMS[p["fwd"]])
         return p
 
+    def debug_raw_covariance(self, seq):
+        # test hook (TEST build only): the sequence's P as the kernels hold it, [ld][ld] with padding and never-used slots
+        T = _lib.load_testing()
+        ld = np.zeros(1, dtype=np.int32)
+        P = np.zeros((1, 1))
+        if T.sl2_debug_raw_covariance(self.h, seq, _lib.dp(P), 1, _lib.ip(ld)) != _lib.SL2_ERR_CAPACITY:
+            raise RuntimeError("sl2_debug_raw_covariance: no size reported")
+        P = np.zeros((int(ld[0]), int(ld[0])))
+        _lib.check(T.sl2_debug_raw_covariance(self.h, seq, _lib.dp(P), P.shape[0], _lib.ip(ld)), T)
+        return P
+
     def delete_features(self, labels, seq0=0):
         """mark_feature_by_lab + delete_feature, one label per sequence (-1: none); returns the per-sequence bool."""
         lab = np.ascontiguousarray(labels, dtype=np.int32)
