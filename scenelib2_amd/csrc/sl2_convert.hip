@@ -10,38 +10,15 @@
 // device, a launch each where there are any.
 // k_convert_remap (sl2_convert_remap.hip, a unit of its own so that this unit's device code is the same with and without it): the
 // sequences that follow a per-pixel map (the lens remap), listed likewise; a gather, nothing staged.
+// Which of the five owns a sequence, the lists and every launch's size: sl2_convert_plan.hpp (convert_route, convert_plan).
 #include "sl2_common.hpp"
 #include "sl2_convert_dev.hpp"
+#include "sl2_convert_plan.hpp"
 #include "sl2_convert_remap.hpp"
 
 namespace sl2 {
 
-constexpr int kConvThreads = 256;
-constexpr int kConvBandRows = 8;                              // output rows per workgroup
-constexpr int kConvSlots = 2 * kConvBandRows;                 // source rows staged at once, at most
-// LDS of the staged grey rows: four rows at the width cap (a staged row is shifted by up to 15 bytes so that its 16-byte
-// stores are aligned: kConvertMaxWidth + 16 each), all sixteen of a band up to 1000 pixels.  16.1 KB: the registers, not the
-// LDS, bound the workgroups a CU takes (eight: the launch bound holds the kernel to 64 registers; at 32 KB and four
-// workgroups it was 1.2 to 1.45 times slower, a workgroup's life being a chain of dependent round trips to memory that only
-// other workgroups hide).
-constexpr int kConvLdsBytes = 4 * (kConvertMaxWidth + 16);
-
-// The device copy of a source carries its sequence's filter in its format word (the host copy and the C ABI never see it)
-constexpr int kConvAreaBit = 0x100;
-// ... and whether its format is a deep grey or Bayer one: k_raw_linear's or k_raw_area's sequence, by the filter
-constexpr int kConvRawBit = 0x200;
-constexpr int kConvFormatMask = 0xff;
-// ... and whether it follows a map: k_convert_remap's sequence (kConvRemapBit, sl2_convert_remap.hpp).  Such a record carries the
-// other two bits as well, whatever its filter and format: they are what keeps the four kernels of this unit off it
-// (k_convert_frames leaves a record with either bit set, the listed kernels never see a sequence that is not on their list).
-static_assert(kRemapThreads == kConvThreads && kRemapBandRows == kConvBandRows && kRemapFormatMask == kConvFormatMask &&
-              (kConvRemapBit & (kConvAreaBit | kConvRawBit | kConvFormatMask)) == 0, "sl2_convert_remap.hpp restates this unit's constants");
-
-// Bayer: the grey of a listed row needs raw rows y - 1, y, y + 1, so the raw rows are staged first (as GRAY8 rows, in dynamic LDS
-// sized by the widest Bayer source of the launch) and the grey rows are formed from them, LDS to LDS.  At most kRawSlots raw rows
-// at once (sixteen consecutive grey rows and their halo) and kRawLdsBytes: four raw rows at the width cap, eighteen up to 880.
-constexpr int kRawSlots = 18;
-constexpr int kRawLdsBytes = 4 * (kConvertMaxWidth + 16);
+// (kConvThreads, kConvBandRows, the LDS sizes and the route bits of the device records: sl2_convert_plan.hpp)
 
 struct ConvArgs {
   const sl2_frame_source* src;   // [nseq]
@@ -177,7 +154,7 @@ __device__ __forceinline__ void raw_stage_bayer(ConvShared& sh, const RawStage& 
   const int tid = threadIdx.x;
   RawRows& rr = *rs.rows;
   const int rx0 = xs > 0 ? xs - 1 : 0, rx1 = xs + Wp < W ? xs + Wp : W - 1;      // the raw columns staged
-  const int Wr = rx1 - rx0 + 1, rpad = (Wr + 15 + 15) & ~15;
+  const int Wr = rx1 - rx0 + 1, rpad = conv_row_pad(Wr);
   const int fit = rs.raw_lds / rpad;                                             // raw rows the stage holds: at least 4
   const int rcap = fit < kRawSlots ? fit : kRawSlots;
   const int nslots = sh.nslots;
@@ -275,7 +252,7 @@ __device__ __forceinline__ void conv_linear(ConvShared& sh, const ConvArgs A, in
   if ((src.format & (kConvAreaBit | kConvRawBit)) != (RAW ? kConvRawBit : 0)) return;
   const uint8_t* __restrict__ base = A.raw + src.offset;
   uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride;
-  const int wpad = (W + 15 + 15) & ~15;
+  const int wpad = conv_row_pad(W);
   const int cap = kConvLdsBytes / wpad;                                        // rows the LDS holds: at least 4
   const int rmax = cap / 2 < kConvBandRows ? cap / 2 : kConvBandRows;          // output rows per pass: at least 2
   __syncthreads();
@@ -414,7 +391,7 @@ __device__ __forceinline__ void area_band(ConvShared& sh, uint32_t* __restrict__
     const int xs = convert_area_first(W, A.out_w, p0), xe = convert_area_last(W, A.out_w, p1 - 1);
     const int Wp = xe - xs + 1;                                                // source columns this panel's taps name
     const uint8_t* __restrict__ base = A.raw + src.offset + (size_t)xs * bpp;
-    const int wpad = (Wp + 15 + 15) & ~15;
+    const int wpad = conv_row_pad(Wp);
     const int fit = kConvLdsBytes / wpad;                                      // rows the LDS holds: at least 4
     const int cap = fit < kConvSlots ? fit : kConvSlots;
     // this lane's output columns p0 + tid and p0 + 256 + tid: their taps, once for all rows (further columns, of outputs wider
@@ -548,17 +525,13 @@ struct sl2_converter {
   std::vector<sl2_frame_source> src;
   std::vector<uint8_t> have;
   std::vector<int32_t> filter;           // SL2_RESIZE_* of every sequence
-  std::vector<int32_t> area;             // the sequences with a source and SL2_RESIZE_AREA: k_convert_area's list
-  std::vector<int32_t> raw_linear, raw_area;      // the sequences of a deep grey or Bayer format, by filter: k_raw_linear's and k_raw_area's lists
-  int32_t* d_area = nullptr;             // [nseq]: the three lists and the remap list, one after the other (they share no sequence)
-  size_t area_lds = 0;                   // k_convert_area's dynamic LDS: a word per source column of the widest listed source
-  size_t raw_area_colsum = 0;            // the same for k_raw_area ...
-  int raw_linear_stage = 0, raw_area_stage = 0;      // ... and the raw stage of the two raw kernels: bytes, 0 with no Bayer source listed
+  ConvPlan plan;                         // what sl2_convert_frames launches: converter_upload makes it
+  int32_t* d_lists = nullptr;            // [nseq]: plan.list on the device
   std::vector<uint32_t> taps;            // host copy of one sequence's table while it is built
-  // the lens remap: nseq map slots (d_map nullptr: empty), the slot of every sequence (-1: none), k_convert_remap's list
+  // the lens remap: nseq map slots (d_map nullptr: empty), the slot of every sequence (-1: none)
   struct MapSlot { int width = 0, height = 0, xbits = 0; uint32_t* d_map = nullptr; };
   std::vector<MapSlot> slots;
-  std::vector<int32_t> remap, remap_list;
+  std::vector<int32_t> remap;
   RemapSlotDev* d_slots = nullptr;       // [nseq]
   int32_t* d_remap = nullptr;            // [nseq]
   sl2_frame_source* d_src = nullptr;
@@ -569,8 +542,20 @@ struct sl2_converter {
   bool queued = false;
 };
 
+// an output size the converter and the host forms take
+static bool out_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= kConvertMaxOut && h <= kConvertMaxOut; }
+
+// sequences seq0 .. seq0 + nseq - 1 lie in the converter
+static bool converter_has_range(const sl2_converter* c, int seq0, int nseq) { return seq0 >= 0 && nseq >= 0 && seq0 + nseq <= c->nseq; }
+
+// Wait for the last conversion queued: it keeps the tables, filters, maps, lists and the stage it was queued with
+static int converter_quiesce(sl2_converter* c) {
+  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }
+  return SL2_OK;
+}
+
 extern "C" int sl2_converter_create(int device, int nseq, int out_width, int out_height, sl2_converter** out) {
-  if (!out || nseq < 1 || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+  if (!out || nseq < 1 || !out_size_ok(out_width, out_height)) {
     set_error("sl2_converter_create: nseq >= 1 and an output size of 1 .. 4096 per axis are required");
     return SL2_ERR_INVALID;
   }
@@ -586,7 +571,7 @@ extern "C" int sl2_converter_create(int device, int nseq, int out_width, int out
   c->src.resize(nseq); c->have.assign(nseq, 0); c->taps.assign(c->tap_stride, 0); c->filter.assign(nseq, SL2_RESIZE_LINEAR);
   c->slots.resize(nseq); c->remap.assign(nseq, -1);
   hipError_t e = hipMalloc(&c->d_src, (size_t)nseq * sizeof(sl2_frame_source));
-  if (e == hipSuccess) e = hipMalloc(&c->d_area, (size_t)nseq * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&c->d_lists, (size_t)nseq * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc(&c->d_taps, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->d_taps, 0, (size_t)nseq * c->tap_stride * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&c->d_slots, (size_t)nseq * sizeof(RemapSlotDev));
@@ -610,7 +595,7 @@ extern "C" void sl2_converter_destroy(sl2_converter* c) {
   if (c->done) hipEventDestroy(c->done);
   if (c->d_src) hipFree(c->d_src);
   if (c->d_taps) hipFree(c->d_taps);
-  if (c->d_area) hipFree(c->d_area);
+  if (c->d_lists) hipFree(c->d_lists);
   if (c->stage) hipFree(c->stage);
   for (auto& m : c->slots) if (m.d_map) hipFree(m.d_map);
   if (c->d_slots) hipFree(c->d_slots);
@@ -618,7 +603,7 @@ extern "C" void sl2_converter_destroy(sl2_converter* c) {
   delete c;
 }
 
-// The device copies of sequences seq0 .. seq0 + nseq - 1 (the filter rides in the format word) and the area list.  No
+// The device copies of sequences seq0 .. seq0 + nseq - 1 (the route rides in the format word), the plan and its lists.  No
 // conversion is queued when this runs.
 static int converter_upload(sl2_converter* c, int seq0, int nseq) {
   std::vector<sl2_frame_source> dev;
@@ -630,44 +615,18 @@ static int converter_upload(sl2_converter* c, int seq0, int nseq) {
     }
     if (first < 0) first = s;
     dev.push_back(c->src[s]);
-    if (c->filter[s] == SL2_RESIZE_AREA) dev.back().format |= kConvAreaBit;
-    if (convert_is_raw(c->src[s].format)) dev.back().format |= kConvRawBit;
-    if (c->remap[s] >= 0) dev.back().format |= kConvRemapBit | kConvAreaBit | kConvRawBit;
+    dev.back().format |= convert_route_bits(convert_route(true, c->filter[s], c->src[s].format, c->remap[s]));
   }
   if (first >= 0) SL2_HIP(hipMemcpy(c->d_src + first, dev.data(), dev.size() * sizeof(sl2_frame_source), hipMemcpyHostToDevice));
   if (nseq > 0) SL2_HIP(hipMemcpy(c->d_remap + seq0, c->remap.data() + seq0, (size_t)nseq * sizeof(int32_t), hipMemcpyHostToDevice));
-  c->area.clear(); c->raw_linear.clear(); c->raw_area.clear(); c->remap_list.clear();
-  int widest = 0, raw_widest = 0;
-  c->raw_linear_stage = c->raw_area_stage = 0;
-  for (int s = 0; s < c->nseq; ++s) {
-    if (!c->have[s]) continue;
-    if (c->remap[s] >= 0) { c->remap_list.push_back(s); continue; }      // a mapped sequence is on no other list
-    const sl2_frame_source& src = c->src[s];
-    const bool area = c->filter[s] == SL2_RESIZE_AREA;
-    if (!convert_is_raw(src.format)) {
-      if (area) { c->area.push_back(s); if (src.width > widest) widest = src.width; }
-      continue;
-    }
-    (area ? c->raw_area : c->raw_linear).push_back(s);
-    if (area && src.width > raw_widest) raw_widest = src.width;
-    if (convert_is_bayer(src.format)) {
-      const int want = kRawSlots * ((src.width + 15 + 15) & ~15);
-      int& stage = area ? c->raw_area_stage : c->raw_linear_stage;
-      stage = std::max(stage, std::min(want, kRawLdsBytes));
-    }
-  }
-  c->area_lds = sizeof(uint32_t) * (size_t)round_up(widest, 4);
-  c->raw_area_colsum = sizeof(uint32_t) * (size_t)round_up(raw_widest, 4);
-  std::vector<int32_t> lists(c->area);
-  lists.insert(lists.end(), c->raw_linear.begin(), c->raw_linear.end());
-  lists.insert(lists.end(), c->raw_area.begin(), c->raw_area.end());
-  lists.insert(lists.end(), c->remap_list.begin(), c->remap_list.end());
-  if (!lists.empty()) SL2_HIP(hipMemcpy(c->d_area, lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->plan = convert_plan(c->nseq, c->have.data(), c->src.data(), c->filter.data(), c->remap.data(), c->out_h);
+  const std::vector<int32_t>& list = c->plan.list;
+  if (!list.empty()) SL2_HIP(hipMemcpy(c->d_lists, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   return SL2_OK;
 }
 
 extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, const sl2_frame_source* src) {
-  if (!c || !src || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_set_sources: bad arguments"); return SL2_ERR_INVALID; }
+  if (!c || !src || !converter_has_range(c, seq0, nseq)) { set_error("sl2_converter_set_sources: bad arguments"); return SL2_ERR_INVALID; }
   for (int i = 0; i < nseq; ++i) {
     const char* why = convert_source_fault(src[i], 0, false);
     if (!why && c->filter[seq0 + i] == SL2_RESIZE_AREA) why = convert_area_fault(src[i], c->out_w, c->out_h);
@@ -677,7 +636,7 @@ extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, c
   }
   if (nseq == 0) return SL2_OK;
   SL2_HIP(hipSetDevice(c->device));
-  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its tables
+  if (int rc = converter_quiesce(c)) return rc;      // a queued conversion keeps its tables
   for (int i = 0; i < nseq; ++i) {
     if (!convert_tap_table(src[i].width, src[i].height, c->out_w, c->out_h, c->taps.data(), c->taps.data() + c->col_taps)) {
       set_error("sl2_converter_set_sources: " + seq_text(seq0 + i, "a tap does not fit its packed form"));
@@ -692,7 +651,7 @@ extern "C" int sl2_converter_set_sources(sl2_converter* c, int seq0, int nseq, c
 
 extern "C" int sl2_converter_set_filters(sl2_converter* c, int seq0, int nseq, const int32_t* filters) {
   if (!c || !filters) { set_error("sl2_converter_set_filters: bad arguments"); return SL2_ERR_INVALID; }
-  if (seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) {
+  if (!converter_has_range(c, seq0, nseq)) {
     set_error("sl2_converter_set_filters: " + seq_text(seq0 < 0 ? seq0 : c->nseq, "outside the converter"));
     return SL2_ERR_INVALID;
   }
@@ -704,19 +663,19 @@ extern "C" int sl2_converter_set_filters(sl2_converter* c, int seq0, int nseq, c
   }
   if (nseq == 0) return SL2_OK;
   SL2_HIP(hipSetDevice(c->device));
-  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its filters
+  if (int rc = converter_quiesce(c)) return rc;      // a queued conversion keeps its filters
   for (int i = 0; i < nseq; ++i) c->filter[seq0 + i] = filters[i];
   return converter_upload(c, seq0, nseq);
 }
 
 extern "C" int sl2_converter_get_filters(const sl2_converter* c, int seq0, int nseq, int32_t* filters) {
-  if (!c || !filters || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_get_filters: bad arguments"); return SL2_ERR_INVALID; }
+  if (!c || !filters || !converter_has_range(c, seq0, nseq)) { set_error("sl2_converter_get_filters: bad arguments"); return SL2_ERR_INVALID; }
   for (int i = 0; i < nseq; ++i) filters[i] = c->filter[seq0 + i];
   return SL2_OK;
 }
 
 extern "C" int sl2_converter_get_sources(const sl2_converter* c, int seq0, int nseq, sl2_frame_source* src) {
-  if (!c || !src || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_get_sources: bad arguments"); return SL2_ERR_INVALID; }
+  if (!c || !src || !converter_has_range(c, seq0, nseq)) { set_error("sl2_converter_get_sources: bad arguments"); return SL2_ERR_INVALID; }
   for (int i = 0; i < nseq; ++i) {
     if (!c->have[seq0 + i]) { set_error("sl2_converter_get_sources: " + seq_text(seq0 + i, "its source was never set")); return SL2_ERR_INVALID; }
     src[i] = c->src[seq0 + i];
@@ -739,7 +698,7 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
   const uint8_t* d_raw = (const uint8_t*)raw;
   if (!raw_on_device) {
     if (raw_bytes > c->stage_bytes) {
-      if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion may still read the old one
+      if (int rc = converter_quiesce(c)) return rc;      // a queued conversion may still read the old one
       if (c->stage) { SL2_HIP(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
       SL2_HIP(hipMalloc(&c->stage, raw_bytes));
       c->stage_bytes = raw_bytes;
@@ -747,31 +706,34 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
     SL2_HIP(hipMemcpyAsync(c->stage, raw, raw_bytes, hipMemcpyHostToDevice, st));
     d_raw = c->stage;
   }
+  // a kernel per route that has a sequence: one launch for the reference's webcam, five at most.  The plan says which, on which
+  // part of the lists and with how much dynamic LDS.
+  const ConvPlan& P = c->plan;
+  const auto grid = [&P](ConvRoute r) { return dim3((unsigned)(P.bands * P.count[r])); };
+  const auto list = [&P, c](ConvRoute r) { return (const int32_t*)(c->d_lists + P.start[r]); };
   ConvArgs A;
   A.src = c->d_src; A.taps = c->d_taps; A.raw = d_raw; A.out = d_frames; A.seq_stride = seq_stride;
   A.out_w = c->out_w; A.out_h = c->out_h; A.col_taps = c->col_taps; A.tap_stride = c->tap_stride;
-  A.bands = (c->out_h + kConvBandRows - 1) / kConvBandRows;
-  // a kernel per (format family, filter) that has a sequence: one launch for the reference's webcam, four at most
-  const int listed = (int)(c->area.size() + c->raw_linear.size() + c->raw_area.size() + c->remap_list.size());
-  if (listed < c->nseq) hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(A.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
+  A.bands = P.bands;
+  // (k_convert_frames walks EVERY sequence and leaves the listed ones)
+  if (P.count[kRouteLinear]) hipLaunchKernelGGL(k_convert_frames, dim3((unsigned)(P.bands * c->nseq)), dim3(kConvThreads), 0, st, A);
   AreaArgs B;
-  B.src = c->d_src; B.list = c->d_area; B.raw = d_raw; B.out = d_frames; B.seq_stride = seq_stride;
-  B.out_w = c->out_w; B.out_h = c->out_h; B.bands = A.bands;
-  if (!c->area.empty())
-    hipLaunchKernelGGL(k_convert_area, dim3((unsigned)(B.bands * (int)c->area.size())), dim3(kConvThreads), c->area_lds, st, B);
-  if (!c->raw_linear.empty())
-    hipLaunchKernelGGL(k_raw_linear, dim3((unsigned)(A.bands * (int)c->raw_linear.size())), dim3(kConvThreads), (size_t)c->raw_linear_stage, st,
-                       A, (const int32_t*)(c->d_area + c->area.size()), c->raw_linear_stage);
-  if (!c->raw_area.empty()) {
-    B.list = c->d_area + c->area.size() + c->raw_linear.size();
-    hipLaunchKernelGGL(k_raw_area, dim3((unsigned)(B.bands * (int)c->raw_area.size())), dim3(kConvThreads),
-                       c->raw_area_colsum + (size_t)c->raw_area_stage, st, B, (int)c->raw_area_colsum, c->raw_area_stage);
+  B.src = c->d_src; B.list = list(kRouteArea); B.raw = d_raw; B.out = d_frames; B.seq_stride = seq_stride;
+  B.out_w = c->out_w; B.out_h = c->out_h; B.bands = P.bands;
+  if (P.count[kRouteArea]) hipLaunchKernelGGL(k_convert_area, grid(kRouteArea), dim3(kConvThreads), (size_t)P.lds[kRouteArea], st, B);
+  if (P.count[kRouteRawLinear])
+    hipLaunchKernelGGL(k_raw_linear, grid(kRouteRawLinear), dim3(kConvThreads), (size_t)P.lds[kRouteRawLinear], st, A, list(kRouteRawLinear),
+                       P.lds[kRouteRawLinear]);
+  if (P.count[kRouteRawArea]) {
+    B.list = list(kRouteRawArea);
+    hipLaunchKernelGGL(k_raw_area, grid(kRouteRawArea), dim3(kConvThreads), (size_t)P.lds[kRouteRawArea], st, B, P.raw_area_colsum,
+                       P.lds[kRouteRawArea] - P.raw_area_colsum);
   }
-  if (!c->remap_list.empty()) {
+  if (P.count[kRouteRemap]) {
     RemapArgs R;
-    R.src = c->d_src; R.list = c->d_area + c->area.size() + c->raw_linear.size() + c->raw_area.size(); R.slot_of = c->d_remap; R.slots = c->d_slots;
-    R.raw = d_raw; R.out = d_frames; R.seq_stride = seq_stride; R.out_w = c->out_w; R.out_h = c->out_h; R.bands = A.bands;
-    convert_remap_launch(R, (int)c->remap_list.size(), st);
+    R.src = c->d_src; R.list = list(kRouteRemap); R.slot_of = c->d_remap; R.slots = c->d_slots;
+    R.raw = d_raw; R.out = d_frames; R.seq_stride = seq_stride; R.out_w = c->out_w; R.out_h = c->out_h; R.bands = P.bands;
+    convert_remap_launch(R, P.count[kRouteRemap], st);
   }
   SL2_HIP(hipGetLastError());
   SL2_HIP(hipEventRecord(c->done, st));
@@ -781,7 +743,7 @@ extern "C" int sl2_convert_frames(sl2_converter* c, void* stream, const void* ra
 
 extern "C" int sl2_convert_frame_host(const sl2_frame_source* src, const void* raw, size_t raw_bytes, int out_width, int out_height,
                                       uint8_t* out) {
-  if (!src || !raw || !out || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+  if (!src || !raw || !out || !out_size_ok(out_width, out_height)) {
     set_error("sl2_convert_frame_host: bad arguments");
     return SL2_ERR_INVALID;
   }
@@ -799,7 +761,7 @@ extern "C" int sl2_convert_frame_host_filtered(const sl2_frame_source* src, int 
                                                int out_height, uint8_t* out) {
   if (filter == SL2_RESIZE_LINEAR) return sl2_convert_frame_host(src, raw, raw_bytes, out_width, out_height, out);
   if (filter != SL2_RESIZE_AREA) { set_error("sl2_convert_frame_host_filtered: unknown resize filter"); return SL2_ERR_INVALID; }
-  if (!src || !raw || !out || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+  if (!src || !raw || !out || !out_size_ok(out_width, out_height)) {
     set_error("sl2_convert_frame_host_filtered: bad arguments");
     return SL2_ERR_INVALID;
   }
@@ -855,7 +817,7 @@ extern "C" int sl2_converter_set_map(sl2_converter* c, int slot, int src_width, 
     }
   }
   SL2_HIP(hipSetDevice(c->device));
-  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its map
+  if (int rc = converter_quiesce(c)) return rc;      // a queued conversion keeps its map
   RemapSlotDev dev = {nullptr, 0, 0, 0, 0};
   if (!xy) {
     if (m.d_map) { SL2_HIP(hipFree(m.d_map)); }
@@ -885,7 +847,7 @@ extern "C" int sl2_converter_set_map(sl2_converter* c, int slot, int src_width, 
 
 extern "C" int sl2_converter_set_remaps(sl2_converter* c, int seq0, int nseq, const int32_t* slots) {
   if (!c || !slots) { set_error("sl2_converter_set_remaps: bad arguments"); return SL2_ERR_INVALID; }
-  if (seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) {
+  if (!converter_has_range(c, seq0, nseq)) {
     set_error("sl2_converter_set_remaps: " + seq_text(seq0 < 0 ? seq0 : c->nseq, "outside the converter"));
     return SL2_ERR_INVALID;
   }
@@ -900,20 +862,20 @@ extern "C" int sl2_converter_set_remaps(sl2_converter* c, int seq0, int nseq, co
   }
   if (nseq == 0) return SL2_OK;
   SL2_HIP(hipSetDevice(c->device));
-  if (c->queued) { SL2_HIP(hipEventSynchronize(c->done)); c->queued = false; }      // a queued conversion keeps its lists
+  if (int rc = converter_quiesce(c)) return rc;      // a queued conversion keeps its lists
   for (int i = 0; i < nseq; ++i) c->remap[seq0 + i] = slots[i];
   return converter_upload(c, seq0, nseq);
 }
 
 extern "C" int sl2_converter_get_remaps(const sl2_converter* c, int seq0, int nseq, int32_t* slots) {
-  if (!c || !slots || seq0 < 0 || nseq < 0 || seq0 + nseq > c->nseq) { set_error("sl2_converter_get_remaps: bad arguments"); return SL2_ERR_INVALID; }
+  if (!c || !slots || !converter_has_range(c, seq0, nseq)) { set_error("sl2_converter_get_remaps: bad arguments"); return SL2_ERR_INVALID; }
   for (int i = 0; i < nseq; ++i) slots[i] = c->remap[seq0 + i];
   return SL2_OK;
 }
 
 extern "C" int sl2_remap_frame_host(const sl2_frame_source* src, const int32_t* xy, const void* raw, size_t raw_bytes, int out_width,
                                     int out_height, uint8_t* out) {
-  if (!src || !xy || !raw || !out || out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut) {
+  if (!src || !xy || !raw || !out || !out_size_ok(out_width, out_height)) {
     set_error("sl2_remap_frame_host: bad arguments");
     return SL2_ERR_INVALID;
   }
@@ -932,7 +894,7 @@ static const char* lens_fault(const sl2_lens& l) {
 extern "C" int sl2_lens_map_host(const sl2_lens* lens, const sl2_camera* target, int32_t* xy) {
   if (!lens || !target || !xy) { set_error("sl2_lens_map_host: bad arguments"); return SL2_ERR_INVALID; }
   const char* why = lens_fault(*lens);
-  if (!why && (target->width < 1 || target->height < 1 || target->width > kConvertMaxOut || target->height > kConvertMaxOut))
+  if (!why && !out_size_ok(target->width, target->height))
     why = "a target size of 1 .. 4096 per axis is required";
   if (why) { set_error(std::string("sl2_lens_map_host: ") + why); return SL2_ERR_INVALID; }
   for (int y = 0; y < target->height; ++y)
@@ -946,7 +908,7 @@ extern "C" int sl2_lens_map_host(const sl2_lens* lens, const sl2_camera* target,
 extern "C" int sl2_lens_pinhole_camera(const sl2_lens* lens, int out_width, int out_height, int sd, sl2_camera* out) {
   if (!lens || !out) { set_error("sl2_lens_pinhole_camera: bad arguments"); return SL2_ERR_INVALID; }
   const char* why = lens_fault(*lens);
-  if (!why && (out_width < 1 || out_height < 1 || out_width > kConvertMaxOut || out_height > kConvertMaxOut)) why = "an output size of 1 .. 4096 per axis is required";
+  if (!why && !out_size_ok(out_width, out_height)) why = "an output size of 1 .. 4096 per axis is required";
   if (why) { set_error(std::string("sl2_lens_pinhole_camera: ") + why); return SL2_ERR_INVALID; }
   sl2_camera r;
   r.width = out_width; r.height = out_height;

@@ -1,12 +1,12 @@
 // The lens remap's kernel ("the lens remap"; the arithmetic: sl2_convert_dev.hpp, remap_pixel; the converter
-// that launches it: sl2_convert.hip).  A unit of its own: the device code of the converter's other four kernels is, byte for byte,
-// what it was before this kernel existed.
+// that launches it: sl2_convert.hip; which sequences it is launched for: sl2_convert_plan.hpp, kRouteRemap).  A unit of its own:
+// the device code of the converter's other four kernels is, byte for byte, what it was before this kernel existed.
 #include "sl2_convert_remap.hpp"
 
 namespace sl2 {
 
 // k_convert_remap: the lens remap (sl2_convert_dev.hpp, remap_pixel).  A workgroup owns one sequence of the remap list and a band of
-// kRemapBandRows output rows.  The band's map entries and its outputs are ONE run of rows x out_w consecutive elements each (the
+// kConvBandRows output rows.  The band's map entries and its outputs are ONE run of rows x out_w consecutive elements each (the
 // rows follow each other without a gap), so the kernel has no rows or columns of its own: a wave takes 256 consecutive elements at
 // a time, lane l those at l, l + 64, l + 128 and l + 192.  Every load or store instruction of a wave then covers 64 NEIGHBOURING
 // outputs: the map entries are one coalesced run, and the taps of neighbouring outputs are neighbours in the source, so a gather
@@ -18,7 +18,7 @@ namespace sl2 {
 // flight at once, not one behind the other); Bayer neighbours are reflected in the index: nothing outside the source is ever
 // addressed.  Budget: no LDS, at most 80 registers, six waves a SIMD.  (At the linear kernel's bound of 64 the 4 x 4 Bayer bytes of a
 // lane's four outputs spilled to scratch.)
-__global__ void __launch_bounds__(kRemapThreads, 6) k_convert_remap(const RemapArgs A) {
+__global__ void __launch_bounds__(kConvThreads, 6) k_convert_remap(const RemapArgs A) {
   const int li = blockIdx.x / A.bands, band = blockIdx.x - li * A.bands;
   const int s = A.list[li];
   const int si = A.slot_of[s];
@@ -26,17 +26,17 @@ __global__ void __launch_bounds__(kRemapThreads, 6) k_convert_remap(const RemapA
   if (si < 0 || !(src.format & kConvRemapBit)) return;      // never listed
   const RemapSlotDev slot = A.slots[si];
   if (!slot.map || slot.width != src.width || slot.height != src.height) return;      // never listed (the host refuses both)
-  const int fmt = src.format & kRemapFormatMask, W = src.width, H = src.height, pitch = src.pitch, xbits = slot.xbits;
+  const int fmt = src.format & kConvFormatMask, W = src.width, H = src.height, pitch = src.pitch, xbits = slot.xbits;
   const uint8_t* __restrict__ base = A.raw + src.offset;
-  const int band0 = band * kRemapBandRows;
-  const int band_end = band0 + kRemapBandRows < A.out_h ? band0 + kRemapBandRows : A.out_h;
+  const int band0 = band * kConvBandRows;
+  const int band_end = band0 + kConvBandRows < A.out_h ? band0 + kConvBandRows : A.out_h;
   const size_t e0 = (size_t)band0 * (size_t)A.out_w;                           // the band's first element
   const int n = (band_end - band0) * A.out_w;                                  // its elements: at most 8 x 4096
   const uint32_t* __restrict__ map1 = slot.map + e0;                           // one-word entries ...
   const uint2* __restrict__ map2 = reinterpret_cast<const uint2*>(slot.map) + e0;      // ... or two-word ones (8-byte aligned: hipMalloc)
   uint8_t* __restrict__ out = A.out + (size_t)s * A.seq_stride + e0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int k0 = wave * 256; k0 < n; k0 += kRemapThreads * 4) {
+  for (int k0 = wave * 256; k0 < n; k0 += kConvThreads * 4) {
     int32_t X[4], Y[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(kRemapThreads, 6) k_convert_remap(const RemapA
 }
 
 void convert_remap_launch(const RemapArgs& A, int nlisted, hipStream_t stream) {
-  hipLaunchKernelGGL(k_convert_remap, dim3((unsigned)(A.bands * nlisted)), dim3(kRemapThreads), 0, stream, A);
+  hipLaunchKernelGGL(k_convert_remap, dim3((unsigned)(A.bands * nlisted)), dim3(kConvThreads), 0, stream, A);
 }
 
 }  // namespace sl2

@@ -1,17 +1,11 @@
 // The lens remap's kernel lives in a unit of its own (sl2_convert_remap.hip): what that unit and the converter's host code
-// (sl2_convert.hip) share.  The arithmetic is sl2_convert_dev.hpp's remap_pixel.
+// (sl2_convert.hip) share, beside the constants and the route bits of sl2_convert_plan.hpp.  The arithmetic is
+// sl2_convert_dev.hpp's remap_pixel.
 #pragma once
 #include "sl2_common.hpp"
-#include "sl2_convert_dev.hpp"
+#include "sl2_convert_plan.hpp"
 
 namespace sl2 {
-
-// restated from sl2_convert.hip, which asserts that they agree
-constexpr int kRemapThreads = 256;          // kConvThreads
-constexpr int kRemapBandRows = 8;           // kConvBandRows: output rows per workgroup
-constexpr int kRemapFormatMask = 0xff;      // kConvFormatMask
-// The device copy of a source that follows a map carries this bit in its format word (beside the two that keep the other kernels off it)
-constexpr int kConvRemapBit = 0x400;
 
 struct RemapSlotDev {            // 24 bytes
   const uint32_t* map;           // [out_h][out_w] words (xbits > 0) or [out_h][out_w][2] (xbits == 0); nullptr: an empty slot

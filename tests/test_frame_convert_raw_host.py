@@ -1,7 +1,7 @@
 """Machine-vision frames, host side: both host forms for the deep grey and the Bayer formats against a NumPy restatement of the
 definition (frame_convert_raw_cases.py, written from the header's text; it calls nothing of the library), the exact anchors, the
-phase check that needs no restatement, the refusals, the Python surface, the stand-alone bounds program under AddressSanitizer
-and the descriptors of the two raw kernels.  (The kernels: tests/test_gpu_frame_convert_raw.py.)"""
+phase check that needs no restatement, the refusals, the Python surface and the stand-alone bounds program under AddressSanitizer.
+(The kernels: tests/test_gpu_frame_convert_raw.py; their descriptors: tests/test_frame_convert_kernels.py.)"""
 import ctypes as C
 import os
 import re
@@ -211,36 +211,3 @@ def test_host_bodies_stay_inside_exactly_sized_blocks_under_asan(tmp_path):
     assert res.returncode == 0, res.stdout + res.stderr
     assert res.stdout.startswith("ok ")
 
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
-def test_raw_kernels_do_not_spill_and_their_lds_leaves_the_stated_workgroups_per_cu(tmp_path):
-    """k_raw_linear's and k_raw_area's descriptors: no scratch, no spilled vector register, at most 80 registers (six workgroups a
-    CU by registers), and static LDS that, with the dynamic part DESIGN.md section 8f states - the raw stage, 16448 bytes at
-    most, and for the area kernel a word per source column, 16384 bytes at the cap - still fits a CU's 160 KB three times at the
-    width cap and four times with a 1280-column Bayer source."""
-    csrc = os.path.join(ROOT, "scenelib2_amd", "csrc")
-    out = os.path.join(str(tmp_path), "sl2_convert.s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wno-unused-value",
-                    "-Wno-unused-result", "--cuda-device-only", "-S", os.path.join(csrc, "sl2_convert.hip"), "-o", out],
-                   check=True, capture_output=True, timeout=900)
-    text = open(out).read()
-    src = open(os.path.join(csrc, "sl2_convert.hip")).read()
-    stage_cap = 4 * (4096 + 16)
-    assert re.search(r"constexpr int kRawLdsBytes = 4 \* \(kConvertMaxWidth \+ 16\);", src)
-    stage_1280 = min(18 * ((1280 + 30) & ~15), stage_cap)
-    for name, dyn_cap, dyn_1280 in (("k_raw_linear", stage_cap, stage_1280), ("k_raw_area", stage_cap + 4 * 4096, stage_1280 + 4 * 1280)):
-        assert "k_convert_frames" not in name and "k_convert_area" not in name
-        m = re.search(r"\.name:\s+\S*%s\S*\n" % name, text)
-        assert m, name
-        block = text[text.rfind("- .agpr_count", 0, m.start()):]
-        lds = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
-        assert lds >= 4 * (4096 + 16)                      # four staged grey rows at the width cap: a pass of two output rows
-        assert 3 * (lds + dyn_cap) <= 160 * 1024, (name, lds)
-        assert 4 * (lds + dyn_1280) <= 160 * 1024, (name, lds)
-        assert 6 * lds <= 160 * 1024, (name, lds)          # no Bayer source, deep grey under LINEAR: six workgroups a CU
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1)) == 0
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)) == 0
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1)) <= 80

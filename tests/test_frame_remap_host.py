@@ -1,8 +1,8 @@
 """The lens remap, host side: sl2_remap_frame_host against a NumPy restatement of the pixel rule (frame_remap_cases.py, written from
 the header's text; it calls nothing of the library) over the case table, the properties that need no restatement,
 sl2_lens_map_host against a restatement of "maps from calibrations", its anchors, sl2_lens_pinhole_camera, the refusals, the
-Python surface, the stand-alone bounds program under AddressSanitizer and the descriptor of k_convert_remap.
-(The kernel: tests/test_gpu_frame_remap.py.)"""
+Python surface and the stand-alone bounds program under AddressSanitizer.
+(The kernel: tests/test_gpu_frame_remap.py; its descriptor: tests/test_frame_convert_kernels.py.)"""
 import ctypes as C
 import os
 import re
@@ -293,32 +293,6 @@ def test_host_body_stays_inside_exactly_sized_blocks_under_asan(tmp_path):
     res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout + res.stderr
     assert res.stdout.startswith("ok ")
-
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
-def test_remap_kernel_does_not_spill_and_uses_no_scratch_and_no_lds(tmp_path):
-    """k_convert_remap's descriptor: no scratch, no spilled register, no LDS (a gather: nothing is staged, and no per-lane array
-    may have been moved there), at most 80 registers - six waves a SIMD, the launch bound of its siblings (at 64 registers the
-    sixteen Bayer bytes of each of a lane's four pixels spilled)."""
-    csrc = os.path.join(ROOT, "scenelib2_amd", "csrc")
-    out = os.path.join(str(tmp_path), "sl2_convert_remap.s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wno-unused-value",
-                    "-Wno-unused-result", "--cuda-device-only", "-S", os.path.join(csrc, "sl2_convert_remap.hip"), "-o", out],
-                   check=True, capture_output=True, timeout=900)
-    text = open(out).read()
-    m = re.search(r"\.name:\s+\S*k_convert_remap\S*\n", text)
-    assert m
-    block = text[text.rfind("- .agpr_count", 0, m.start()):]
-    block = block[:block.find("- .agpr_count", 10)] if block.find("- .agpr_count", 10) > 0 else block
-    assert "k_convert_remap" in block
-    assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1)) == 0
-    assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", block).group(1)) == 0
-    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)) == 0
-    assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1)) == 0
-    assert int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1)) <= 80
 
 
 def test_adapters_have_set_lens_and_the_cpp_one_compiles(tmp_path):
