@@ -54,7 +54,11 @@ extern "C" {
  * sl2_view, sl2_view_look_at, sl2_world_items, sl2_world_item_bound, sl2_draw_world, SL2_WORLD_*, sl2_pick_items_batch,
  * sl2_pick_items_host (the world view of GraphicTool::Draw3dScene from a free camera, and GraphicTool::Picker);
  * sl2_converter_set_map, sl2_converter_set_remaps, sl2_converter_get_remaps, sl2_remap_frame_host, SL2_REMAP_BORDER, sl2_lens,
- * SL2_LENS_*, sl2_lens_map_host, sl2_lens_pinhole_camera (the lens remap: OpenCV and fisheye cameras through a per-pixel map). */
+ * SL2_LENS_*, sl2_lens_map_host, sl2_lens_pinhole_camera (the lens remap: OpenCV and fisheye cameras through a per-pixel map);
+ * sl2_frame_monitor_create, sl2_frame_monitor_destroy, sl2_frame_monitor_set_gates, sl2_frame_monitor_get_gates,
+ * sl2_frame_monitor_reset, sl2_examine_frames, sl2_frame_monitor_read, sl2_frame_stats_host, sl2_frame_verdict_host,
+ * sl2_frame_stats, sl2_frame_gate, SL2_FRAME_* (the frame monitor: per-sequence frame statistics and a device-side gate in front
+ * of sl2_set_active_sequences). */
 #define SL2_API_VERSION 5
 
 #define SL2_OK 0
@@ -629,6 +633,82 @@ typedef struct sl2_lens {                /* 112 bytes */
 } sl2_lens;
 int sl2_lens_map_host(const sl2_lens* lens, const sl2_camera* target, int32_t* xy);
 int sl2_lens_pinhole_camera(const sl2_lens* lens, int out_width, int out_height, int sd, sl2_camera* out);
+
+/* ---- the frame monitor (additions within SL2_API_VERSION 5): per-sequence frame statistics and a device-side gate ----
+ * Nothing else looks at a frame before the step.  A monitor is an object beside the engine, like the converter: in two
+ * stream-ordered launches it examines the engine-size grey frames of a whole batch, writes an exact integer record per sequence,
+ * compares it with the sequence's thresholds and writes a verdict word and an `active` byte per sequence - bytes that
+ * sl2_set_active_sequences(.., on_device = 1) takes as they are, so a camera that repeated its buffer or delivered a black frame
+ * sits the step out without a host round trip.  Every rule is off by default; an engine without a monitor launches nothing new.
+ *
+ * A frame is n = width * height bytes f[0 .. n), row-major with pitch = width (the engine's own frame format).  The record:
+ *   sum, sum_sq      of f[i] and of f[i]^2.
+ *   gradient_energy  sum over 1 <= x <= W - 2, 1 <= y <= H - 2 of (f[y][x+1] - f[y][x-1])^2 + (f[y+1][x] - f[y-1][x])^2; 0 when W < 3 or
+ *                    H < 3.
+ *   digest           positional, and a sum, so the order of accumulation does not matter.  Word k, 0 <= k < ceil(n / 8), is the
+ *                    sum over j < 8 with 8 k + j < n of (uint64) f[8 k + j] << 8 j; digest = sum over k of
+ *                    mix64(word_k ^ ((k + 1) * 0x9E3779B97F4A7C15)) mod 2^64, where mix64(z) is
+ *                      z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *                    The word index is relative to the frame: not to the pointer's alignment, not to seq_stride.
+ *   min, max         of f[i].
+ *   hist[16]         hist[f[i] >> 4].
+ * The host form and the kernels meet this text bit for bit (one source: scenelib2_amd/csrc/sl2_frame_monitor_dev.hpp).
+ * The gate of a sequence: every comparison is on integers, the verdict is the OR of the rules that fire, 0 = the frame passes.
+ * Not covered: a difference against the previous frame's PIXELS (a noisy camera that repeats a scene is not REPEATED: the digest
+ * changes with one byte); raw-format frames in front of the converter; statistics per region.  The monitor's state (gates,
+ * previous digests) belongs to the monitor and is in no sequence blob, as the mask belongs to the engine. */
+typedef struct sl2_frame_stats {         /* 104 bytes */
+  uint64_t sum;
+  uint64_t sum_sq;
+  uint64_t gradient_energy;
+  uint64_t digest;
+  uint32_t min, max;
+  uint32_t hist[16];
+} sl2_frame_stats;
+typedef struct sl2_frame_gate {          /* 32 bytes; all zeros = every rule off */
+  uint32_t min_range;                    /* SL2_FRAME_FLAT     when max - min < min_range (0: off) */
+  uint32_t dark_bins;                    /* bins [0, dark_bins) are dark, 0 .. 16 (0: off) */
+  uint32_t max_dark_pixels;              /* SL2_FRAME_DARK     when more dark pixels than this */
+  uint32_t bright_bins;                  /* bins [16 - bright_bins, 16) are bright, 0 .. 16 (0: off) */
+  uint32_t max_bright_pixels;            /* SL2_FRAME_BRIGHT   when more bright pixels than this */
+  uint32_t reject_repeated;              /* SL2_FRAME_REPEATED when digest == digest of the sequence's previous EXAMINED frame (0: off) */
+  uint64_t min_gradient_energy;          /* SL2_FRAME_BLURRED  when gradient_energy < this (0: off) */
+} sl2_frame_gate;
+enum { SL2_FRAME_FLAT = 1, SL2_FRAME_DARK = 2, SL2_FRAME_BRIGHT = 4, SL2_FRAME_BLURRED = 8, SL2_FRAME_REPEATED = 16, SL2_FRAME_SKIPPED = 32 };
+typedef struct sl2_frame_monitor sl2_frame_monitor;
+/* A monitor for `batch` sequences of width x height frames: width, height >= 1 and width * height < 2^31.  It needs no engine.
+ * After creation every gate is all zeros and no sequence has a previous digest. */
+int sl2_frame_monitor_create(int device, int batch, int width, int height, sl2_frame_monitor** out);
+void sl2_frame_monitor_destroy(sl2_frame_monitor* m);
+/* The gates of sequences seq0 .. seq0 + nseq - 1: host memory, consumed before the call returns; the change is ordered on the
+ * stream of the next examination (it rides in front of it, as one small launch per 64 consecutive sequences whose gate was set
+ * since the last examination; an examination with no gate set since then is the two launches alone) and the call never waits.  SL2_ERR_INVALID, and nothing changed: a
+ * NULL, a range outside the batch, dark_bins > 16 or bright_bins > 16 in any gate of the range (the text names the sequence).
+ * sl2_frame_monitor_get_gates returns what was set. */
+int sl2_frame_monitor_set_gates(sl2_frame_monitor* m, int seq0, int nseq, const sl2_frame_gate* gates);
+int sl2_frame_monitor_get_gates(const sl2_frame_monitor* m, int seq0, int nseq, sl2_frame_gate* gates);
+/* Forgets the previous digests of the range (a slot given to another camera): the next examined frame of such a sequence is not
+ * REPEATED.  Ordered like sl2_frame_monitor_set_gates; never waits. */
+int sl2_frame_monitor_reset(sl2_frame_monitor* m, int seq0, int nseq);
+/* Examines frames + b * seq_stride for every sequence b of the batch, asynchronously on `stream` (a hipStream_t): two launches,
+ * k_frame_stats and k_frame_gate; the call never waits for the device.  All pointers are device pointers and every one but
+ * `frames` may be NULL: base_active [batch] bytes (NULL: all ones), stats_out [batch] records, verdict_out [batch] words,
+ * active_out [batch] bytes.  frames + b * seq_stride may have any alignment and seq_stride any value >= width * height; the bytes
+ * between are not read.  A sequence with base_active[b] == 0 is not examined: none of its frame bytes are read, its stats_out
+ * record and its previous digest are left as they were, its verdict is SL2_FRAME_SKIPPED and its active_out[b] is 0.  Otherwise
+ * the verdict is the OR of the rules that fire, active_out[b] = (verdict == 0), and the sequence's previous digest becomes this
+ * frame's, whatever the verdict; the first examined frame of a sequence is never REPEATED.  Every quantity is an integer sum, a
+ * minimum or a maximum: the outputs are the same bytes on every run.  base_active and active_out may be the same array. */
+int sl2_examine_frames(sl2_frame_monitor* m, void* stream, const uint8_t* frames, size_t seq_stride, const uint8_t* base_active,
+                       sl2_frame_stats* stats_out, uint32_t* verdict_out, uint8_t* active_out);
+/* The last examination of the range, to host memory: the record each sequence was last examined with (zeros before the first)
+ * and the last call's verdicts (SL2_FRAME_SKIPPED before the first).  Either pointer may be NULL.  Synchronises. */
+int sl2_frame_monitor_read(sl2_frame_monitor* m, int seq0, int nseq, sl2_frame_stats* stats, uint32_t* verdicts);
+/* The host forms (no GPU needed).  sl2_frame_stats_host: the record of one frame; SL2_ERR_INVALID for a NULL or a size outside
+ * the monitor's.  sl2_frame_verdict_host: the verdict word of a record under a gate; have_previous != 0 = the sequence has a
+ * previous digest, previous_digest.  A NULL or a gate the setter would refuse gives 0xFFFFFFFF (no verdict has those bits). */
+int sl2_frame_stats_host(const uint8_t* frame, int width, int height, sl2_frame_stats* stats);
+uint32_t sl2_frame_verdict_host(const sl2_frame_stats* stats, const sl2_frame_gate* gate, int have_previous, uint64_t previous_digest);
 
 /* ----------------------------------------------------------------- state access */
 

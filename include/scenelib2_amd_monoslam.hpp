@@ -93,6 +93,7 @@ class MonoSLAM {
   ~MonoSLAM() {
     if (converter_) sl2_converter_destroy(converter_);
     if (frame_dev_) sl2_dev_free(device_, frame_dev_);
+    drop_frame_gate();
     if (eng_) sl2_destroy(eng_);
   }
   MonoSLAM(const MonoSLAM&) = delete;
@@ -141,6 +142,7 @@ class MonoSLAM {
     if (sl2_device_count() < 1) throw std::runtime_error("MonoSLAM::Init: no HIP device (the engine has no CPU path)");
     if (converter_) { sl2_converter_destroy(converter_); converter_ = nullptr; }      // (sized by the camera of the last Init)
     if (frame_dev_) { sl2_dev_free(device_, frame_dev_); frame_dev_ = nullptr; }
+    drop_frame_gate();
     if (eng_) { sl2_destroy(eng_); eng_ = nullptr; }
     traj_seen_ = 0; patch_seen_ = 0; patch_cache_.clear(); feature_list_.clear(); trajectory_store_.clear();
     check(sl2_create(&cam, &prm, 1, max_features_, device_, nullptr, &eng_), "sl2_create");
@@ -195,6 +197,7 @@ class MonoSLAM {
   bool GoOneStep(const Frame& frame, bool save_trajectory, bool enable_mapping) {
     if (!eng_ || !frame.data || frame.cols != camera_->width_ || frame.rows != camera_->height_)
       throw std::runtime_error("MonoSLAM::GoOneStep: frame does not match the camera");
+    if (frame_gate_set_) apply_frame_gate(frame);
     const auto t0 = std::chrono::steady_clock::now();
     check(sl2_go_one_step(eng_, frame.data, (size_t)frame.cols * frame.rows, frame.on_device ? 1 : 0, save_trajectory ? 1 : 0,
                           enable_mapping ? 1 : 0),
@@ -202,6 +205,8 @@ class MonoSLAM {
     if (measure_timing_) check(sl2_synchronize(eng_), "sl2_synchronize");   // only to SPLIT the time; costs a second wait
     const auto t1 = std::chrono::steady_clock::now();
     refresh_public_members();
+    if (frame_gate_set_ && frame.on_device)      // (the read-back above has waited for the stream)
+      check(sl2_frame_monitor_read(monitor_, 0, 1, nullptr, &last_frame_verdict_), "sl2_frame_monitor_read");
     const auto t2 = std::chrono::steady_clock::now();
     last_step_us_ = std::chrono::duration<double, std::micro>(t1 - t0).count();
     last_refresh_us_ = std::chrono::duration<double, std::micro>(t2 - t1).count();
@@ -270,6 +275,29 @@ class MonoSLAM {
     frame.data = frame_dev_; frame.cols = camera_->width_; frame.rows = camera_->height_; frame.on_device = true;
     return GoOneStep(frame, save_trajectory, enable_mapping);      // (its read-back waits for the stream: the copy of `raw` is done)
   }
+
+  // A gate in front of every step (sl2_frame_gate; scenelib2_amd.h, "the frame monitor"): from the next GoOneStep / GoOneStepRaw on
+  // the frame is examined first, and a frame the gate rejects - the camera repeated its buffer, delivered a black or saturated
+  // frame, a smeared one - is not shown to the filter: the step leaves it as it was (sl2_set_active_sequences).  A device frame
+  // (GoOneStepRaw's always is one) is examined on the engine's stream and its verdict feeds the mask on the device, with no wait
+  // in between; a host frame goes through sl2_frame_stats_host and sl2_frame_verdict_host.  The previous digest is kept per kind
+  // of frame: after a switch between host and device frames the first frame is not REPEATED.  catch_up: the predict that follows
+  // a rejected frame covers the gap (sl2_set_pause_catch_up) instead of one nominal step.  Without this call nothing changes.
+  void SetFrameGate(const sl2_frame_gate& gate, bool catch_up = false) {
+    if (!eng_) throw std::runtime_error("MonoSLAM::SetFrameGate: call Init first");
+    if (!monitor_) {
+      check(sl2_frame_monitor_create(device_, 1, camera_->width_, camera_->height_, &monitor_), "sl2_frame_monitor_create");
+      void* p = nullptr;
+      check(sl2_dev_malloc(device_, 1, &p), "sl2_dev_malloc");
+      gate_active_dev_ = (uint8_t*)p;
+    }
+    check(sl2_frame_monitor_set_gates(monitor_, 0, 1, &gate), "sl2_frame_monitor_set_gates");
+    check(sl2_set_pause_catch_up(eng_, catch_up ? 1 : 0), "sl2_set_pause_catch_up");
+    frame_gate_ = gate;
+    frame_gate_set_ = true;
+  }
+  // The verdict of the last frame a step was asked to take (SL2_FRAME_* bits; 0: it passed, or no gate is set)
+  uint32_t LastFrameVerdict() const { return last_frame_verdict_; }
 
   // GraphicTool::DrawRawAR (graphic/graphictool.cpp:285-364) without OpenGL: the frame annotated with the search ellipses, the
   // templates, the particle ellipses of a partially initialised feature and the initialisation boxes, drawn on the device
@@ -529,6 +557,27 @@ class MonoSLAM {
   static void check(int rc, const char* what) {
     if (rc != SL2_OK) throw std::runtime_error(std::string(what) + ": " + sl2_last_error());
   }
+  // SetFrameGate's chain in front of a step: the verdict of this frame into the engine's mask
+  void apply_frame_gate(const Frame& frame) {
+    if (frame.on_device) {
+      check(sl2_examine_frames(monitor_, sl2_get_stream(eng_), frame.data, (size_t)frame.cols * frame.rows, nullptr, nullptr, nullptr,
+                               gate_active_dev_),
+            "sl2_examine_frames");
+      check(sl2_set_active_sequences(eng_, 0, 1, gate_active_dev_, 1), "sl2_set_active_sequences");
+      return;
+    }
+    sl2_frame_stats stats;
+    check(sl2_frame_stats_host(frame.data, frame.cols, frame.rows, &stats), "sl2_frame_stats_host");
+    last_frame_verdict_ = sl2_frame_verdict_host(&stats, &frame_gate_, host_have_digest_ ? 1 : 0, host_digest_);
+    host_digest_ = stats.digest; host_have_digest_ = true;
+    const uint8_t active = last_frame_verdict_ == 0 ? 1 : 0;
+    check(sl2_set_active_sequences(eng_, 0, 1, &active, 0), "sl2_set_active_sequences");
+  }
+  void drop_frame_gate() {
+    if (monitor_) { sl2_frame_monitor_destroy(monitor_); monitor_ = nullptr; }
+    if (gate_active_dev_) { sl2_dev_free(device_, gate_active_dev_); gate_active_dev_ = nullptr; }
+    frame_gate_set_ = false; host_have_digest_ = false; last_frame_verdict_ = 0;
+  }
   // The converter and the device frame of GoOneStepRaw, created by whichever of SetFrameSource and SetLens comes first
   void ensure_converter() {
     if (converter_) return;
@@ -691,6 +740,12 @@ class MonoSLAM {
   sl2_converter* converter_ = nullptr;   // SetFrameSource: raw camera frames in front of GoOneStep
   uint8_t* frame_dev_ = nullptr;         // the converted frame, camera_->width_ x camera_->height_, device memory
   int frame_filter_ = SL2_RESIZE_LINEAR; // SetFrameFilter
+  sl2_frame_monitor* monitor_ = nullptr; // SetFrameGate: the gate in front of every step
+  uint8_t* gate_active_dev_ = nullptr;   // the monitor's active byte, device memory: what sl2_set_active_sequences reads
+  sl2_frame_gate frame_gate_{};
+  bool frame_gate_set_ = false, host_have_digest_ = false;
+  uint64_t host_digest_ = 0;             // of the last HOST frame examined
+  uint32_t last_frame_verdict_ = 0;
 };
 
 // Kalman (kalman.h:51-52): the reference's filter object works on the MonoSLAM it is handed; so does this one.

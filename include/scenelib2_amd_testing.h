@@ -49,6 +49,10 @@ int sl2_debug_gemm_kt(int device, const double* XT, int ldx, const double* YT, i
  * TFLOP/s (4 independent accumulators), 1 = dependent chain, 2 = streaming copy GB/s. */
 int sl2_debug_microbench(int device, int which, double* result);
 
+/* Rows of a frame one workgroup of k_frame_stats covers (kFrameBandRows of scenelib2_amd/csrc/sl2_frame_monitor_dev.hpp, which
+ * sl2_frame_monitor.hip checks against this): the tests put image heights one row before, at and one row after a band's end. */
+#define SL2_FRAME_MONITOR_BAND_ROWS 32
+
 #ifdef __cplusplus
 }
 #endif

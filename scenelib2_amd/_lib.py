@@ -115,6 +115,24 @@ class sl2_lens(C.Structure):
 
 
 assert C.sizeof(sl2_lens) == 112
+
+
+class sl2_frame_stats(C.Structure):
+    """One sequence's record of the frame monitor (frame_monitor.FrameMonitor.examine, frame_monitor.frame_stats_host)."""
+    _fields_ = [("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("gradient_energy", C.c_uint64), ("digest", C.c_uint64),
+                ("min", C.c_uint32), ("max", C.c_uint32), ("hist", C.c_uint32 * 16)]
+
+
+class sl2_frame_gate(C.Structure):
+    """One sequence's thresholds (FrameMonitor.set_gates); all zeros = every rule off."""
+    _fields_ = [("min_range", C.c_uint32), ("dark_bins", C.c_uint32), ("max_dark_pixels", C.c_uint32), ("bright_bins", C.c_uint32),
+                ("max_bright_pixels", C.c_uint32), ("reject_repeated", C.c_uint32), ("min_gradient_energy", C.c_uint64)]
+
+
+FRAME_STATS_DTYPE = np.dtype([("sum", np.uint64), ("sum_sq", np.uint64), ("gradient_energy", np.uint64), ("digest", np.uint64),
+                              ("min", np.uint32), ("max", np.uint32), ("hist", np.uint32, (16,))])
+assert C.sizeof(sl2_frame_stats) == 104 and FRAME_STATS_DTYPE.itemsize == 104 and C.sizeof(sl2_frame_gate) == 32
+SL2_FRAME_FLAT, SL2_FRAME_DARK, SL2_FRAME_BRIGHT, SL2_FRAME_BLURRED, SL2_FRAME_REPEATED, SL2_FRAME_SKIPPED = 1, 2, 4, 8, 16, 32
 # sections of a snapshot blob (sl2_snapshot_batch); the header, xv_ and Pxx_ are always present
 SL2_SNAP_POSE, SL2_SNAP_FEATURES, SL2_SNAP_COV, SL2_SNAP_SELECTION, SL2_SNAP_TRAJ, SL2_SNAP_PARTIAL, SL2_SNAP_PATCHES = 0, 1, 2, 4, 8, 16, 32
 SL2_SNAP_ALL = 63
@@ -182,6 +200,8 @@ EXPORTED_SYMBOLS = [
     "sl2_view_look_at", "sl2_world_item_bound", "sl2_world_items", "sl2_draw_world", "sl2_pick_items_batch", "sl2_pick_items_host",
     "sl2_converter_set_map", "sl2_converter_set_remaps", "sl2_converter_get_remaps", "sl2_remap_frame_host",
     "sl2_lens_map_host", "sl2_lens_pinhole_camera",
+    "sl2_frame_monitor_create", "sl2_frame_monitor_destroy", "sl2_frame_monitor_set_gates", "sl2_frame_monitor_get_gates",
+    "sl2_frame_monitor_reset", "sl2_examine_frames", "sl2_frame_monitor_read", "sl2_frame_stats_host", "sl2_frame_verdict_host",
 ]
 # test hooks and micro-benchmarks (include/scenelib2_amd_testing.h): exported by libscenelib2_amd_test.so ONLY
 TEST_SYMBOLS = ["sl2_set_feature_counters", "sl2_debug_set_position_error", "sl2_debug_ncc_score", "sl2_debug_gemm_kt", "sl2_debug_microbench", "sl2_debug_graph_captures",
@@ -354,6 +374,18 @@ def _bind(L):
         L.sl2_draw_world.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int]
         L.sl2_pick_items_batch.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int]
         L.sl2_pick_items_host.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    if "SL2_LIB_PATH" not in os.environ or hasattr(L, "sl2_examine_frames"):
+        L.sl2_frame_monitor_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sl2_frame_monitor_destroy.argtypes = [vp]
+        L.sl2_frame_monitor_destroy.restype = None
+        L.sl2_frame_monitor_set_gates.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sl2_frame_gate)]
+        L.sl2_frame_monitor_get_gates.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sl2_frame_gate)]
+        L.sl2_frame_monitor_reset.argtypes = [vp, C.c_int, C.c_int]
+        L.sl2_examine_frames.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
+        L.sl2_frame_monitor_read.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+        L.sl2_frame_stats_host.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sl2_frame_stats)]
+        L.sl2_frame_verdict_host.argtypes = [C.POINTER(sl2_frame_stats), C.POINTER(sl2_frame_gate), C.c_int, C.c_uint64]
+        L.sl2_frame_verdict_host.restype = C.c_uint32
     return L
 
 

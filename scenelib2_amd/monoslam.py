@@ -782,6 +782,11 @@ class MonoSLAM:
         self._converter = None                      # SetFrameSource: raw camera frames in front of GoOneStep
         self._frame_dev = None
         self._frame_filter = "linear"               # SetFrameFilter
+        self._frame_gate = None                     # SetFrameGate: the gate in front of every step
+        self._monitor = None
+        self._gate_active_dev = None
+        self._host_digest = None                    # of the last HOST frame examined
+        self._last_frame_verdict = 0
 
     # MonoSLAM::Init(config_path) — monoslam.cpp:1574-1969
     def Init(self, config_path, template_dirs=()):
@@ -796,6 +801,7 @@ class MonoSLAM:
         self.kDeltaT_ = params["delta_t"]
         self.kNumberOfFeaturesToSelect_ = params["number_of_features_to_select"]
         self._engine = Engine(cam, params, 1, self._max_features, self._device)
+        self._drop_frame_gate()                     # (sized by the camera of the last Init; the new engine has no catch-up set)
         self._engine.set_vehicle_state(np.asarray(xv).reshape(1, 13), np.asarray(Pxx).reshape(1, 13, 13))
         return self
 
@@ -828,8 +834,44 @@ class MonoSLAM:
         f = np.ascontiguousarray(frame, dtype=np.uint8)
         if f.size != self._engine.frame_bytes:
             raise ValueError("frame must be %d x %d 8-bit single channel" % (self.camera_["width"], self.camera_["height"]))
+        if self._frame_gate is not None:            # a host frame: the two host forms for its one frame
+            from . import frame_monitor
+            rec = frame_monitor.frame_stats_host(f.reshape(-1), self.camera_["width"], self.camera_["height"])
+            self._last_frame_verdict = frame_monitor.frame_verdict_host(rec, self._frame_gate, self._host_digest is not None,
+                                                                        self._host_digest or 0)
+            self._host_digest = int(rec["digest"])
+            self._engine.set_active([self._last_frame_verdict == 0])
         self._engine.go_one_step(f.reshape(1, -1), save_trajectory, enable_mapping)
         return self._after_step(enable_mapping)
+
+    def SetFrameGate(self, gate, catch_up=False):
+        """A gate in front of every step (frame_monitor.make_gate: a dict of its thresholds): from the next GoOneStep / GoOneStepRaw
+        on the frame is examined first, and a frame the gate rejects - the camera repeated its buffer, delivered a black or
+        saturated frame, a smeared one - is not shown to the filter: the step leaves it as it was.  GoOneStepRaw's device frame is
+        examined on the engine's stream and its verdict feeds the mask on the device, with no wait in between; GoOneStep's host
+        frame goes through the host forms.  The previous digest is kept per kind of frame.  catch_up: the predict that follows a
+        rejected frame covers the gap (Engine.set_pause_catch_up).  Without this call nothing changes."""
+        from . import frame_monitor
+        if self._engine is None:
+            raise RuntimeError("MonoSLAM.SetFrameGate: call Init first")
+        g = frame_monitor.make_gate(gate)
+        if self._monitor is None:
+            self._monitor = frame_monitor.FrameMonitor(self._device, 1, self.camera_["width"], self.camera_["height"])
+            self._gate_active_dev = _lib.DeviceBuffer(1, self._device)
+        self._monitor.set_gates([g])
+        self._engine.set_pause_catch_up(bool(catch_up))
+        self._frame_gate = g
+
+    def _drop_frame_gate(self):
+        if self._monitor is not None:
+            self._monitor.close()
+            self._gate_active_dev.free()
+        self._monitor = self._gate_active_dev = self._frame_gate = self._host_digest = None
+        self._last_frame_verdict = 0
+
+    def LastFrameVerdict(self):
+        """The verdict of the last frame a step was asked to take (frame_monitor.SL2_FRAME_* bits; 0: it passed, or no gate)."""
+        return self._last_frame_verdict
 
     def _after_step(self, enable_mapping):
         # the reference's feature_list_ is unbounded; the engine holds at most max_features LIVE features per sequence
@@ -893,9 +935,14 @@ class MonoSLAM:
         if self._converter is None:
             raise RuntimeError("MonoSLAM.GoOneStepRaw: call SetFrameSource first")
         keep = self._converter.convert(raw if not on_device else tuple(raw), self._frame_dev, stream=self._engine.stream)
+        if self._frame_gate is not None:            # examine, then the mask in device form: no wait in between
+            self._monitor.examine(self._frame_dev, active_out=self._gate_active_dev, stream=self._engine.stream)
+            self._engine.set_active((self._gate_active_dev.ptr, 1), on_device=True)
         self._engine.go_one_step(self._frame_dev.ptr, save_trajectory, enable_mapping, on_device=True)
         if keep is not None:
             self._engine.synchronize()  # the host buffer must outlive the copy queued in front of the step
+        if self._frame_gate is not None:
+            self._last_frame_verdict = int(self._monitor.read()[1][0])
         return self._after_step(enable_mapping)
 
     # GraphicTool::DrawRawAR(frame, chk_display_2d_descriptors, chk_display_2d_search_regions, chk_display_initialisation)
